@@ -11,7 +11,9 @@ to rank 0 over RCCL -- strong scaling: the frame is fixed as N grows.
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line (rank 0).  `value` = samples actually taken (inner-loop bodies,
-after ESS/ERT) by all ranks in the K timed frames / wall time, in Msamples/s.
+after ESS/ERT) by all ranks in the K timed frames / wall time, in Msamples/s.  `--full` adds
+the roofline figures, the CPU baseline and the parity check against the oracle;
+`--dump-outputs DIR` writes the last timed frame.
 """
 import argparse
 import json
@@ -96,6 +98,15 @@ def parse():
                          "pass, no CPU baseline): a rocprofv3 --kernel-trace --stats of this command "
                          "holds the timed launches and nothing else after the warm-up")
     ap.add_argument("--out-json", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run everything beyond the headline figure: the same frames one "
+                         "at a time, the phase-timed frame, the roofline figures, the CPU baseline and the parity "
+                         "check against the oracle (a plain run sets up, warms up, times the steps, counts the work of "
+                         "the timed frames that `value` needs and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the image the timed region rendered in its last step (rank 0) to DIR/image.npy, "
+                         "float32 [H, W, 4]; an image above 32 MiB is written as a fixed, seeded sample of its pixels "
+                         "(DIR/image_sample.npy, [n, 4])")
     return ap.parse_args()
 
 
@@ -212,6 +223,22 @@ def find_profile(kind, key, src_hash):
                         "profile_meta": {k: meta.get(k) for k in list(key) + ["source_hash", "head"]},
                         "this_run": dict(key, source_hash=src_hash)}
     return None, near
+
+
+DUMP_MAX_BYTES = 32 << 20
+
+
+def dump_outputs(out_dir, image):
+    """`--dump-outputs`: the frame the timed region rendered last, as the caller receives it (float32 RGBA).  A frame
+    above DUMP_MAX_BYTES (the 2048^2 viewport) is written as a fixed, seeded sample of its pixels in raster order."""
+    os.makedirs(out_dir, exist_ok=True)
+    img = image.detach().cpu().numpy().astype(np.float32, copy=False)
+    if img.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), img)
+        return
+    px = img.reshape(-1, img.shape[-1])
+    pick = np.random.default_rng(0).choice(px.shape[0], DUMP_MAX_BYTES // px[0].nbytes, replace=False)
+    np.save(os.path.join(out_dir, "image_sample.npy"), px[np.sort(pick)])
 
 
 def host_cpu_share():
@@ -467,11 +494,20 @@ def main():
         dist.all_reduce(wall_t, op=dist.ReduceOp.MAX)
     wall = float(wall_t.item())
 
-    # ---- the timed region's own output, copied to the host before anything else renders: the frames the
-    # oracle is asked about below (parity.timed_frames) and what the last timed launch set launched
+    # ---- the timed region's own output, copied to the host before anything else renders: the last timed frame
+    # (--dump-outputs), the frames the oracle is asked about below (parity.timed_frames) and what the last timed
+    # launch set launched
+    if args.dump_outputs and rank == 0:
+        if not multi and throughput:   # the renderer of the last launch set still holds its frames
+            last = lanes[(len(blocks) - 1) % fif][2][len(blocks[-1]) - 1]
+        elif not multi:
+            last = frame
+        else:
+            last = frames[len(chunks[-1]) - 1]
+        dump_outputs(args.dump_outputs, last)
     timed_frames, timed_info = [], None      # [(label, jitter seed, host image)]
     set_frames_used = max(len(b_) for b_ in blocks) if throughput else 1
-    if rank == 0 and technique == 0 and not args.profile_region:
+    if rank == 0 and technique == 0 and args.full and not args.profile_region:
         def pick(label, k, tensor):
             if all(k != k_ for _, k_, _ in timed_frames):
                 timed_frames.append((label, k, tensor.detach().cpu().numpy().copy()))
@@ -525,7 +561,7 @@ def main():
         r.setFrameTiming(True)
     if throughput:
         vr.setRoundBudget(10)      # the single-frame schedule for everything that follows
-    if not multi and throughput:
+    if args.full and not multi and throughput:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream)
         for k in range(args.steps):
@@ -534,7 +570,7 @@ def main():
         torch.cuda.synchronize(dev)
         serial_s = e0.elapsed_time(e1) * 1e-3 / args.steps
         last_kernel_s = vr.getLastExecTime()
-    if technique == 0:   # one more frame with the event between the phases (it costs GPU time: off otherwise)
+    if args.full and technique == 0:   # one more frame with the event between the phases (it costs GPU time: off otherwise)
         vr.setPhaseTiming(True)
         render(seeds[args.warmup + args.steps - 1], args.steps - 1)
         torch.cuda.synchronize(dev)
@@ -557,12 +593,12 @@ def main():
     tot = tot_t.cpu().numpy()
     work = dict(zip(names, [int(x) for x in tot]))
 
-    # ---- untimed: compulsory traffic of ONE launch on rank 0 (first timed seed)
+    # ---- untimed, --full only: compulsory traffic of ONE launch on rank 0 (first timed seed)
     roofline = None
     roofline_valu = None
     cpu = None
     parity = None
-    if rank == 0:
+    if rank == 0 and args.full:
         vr.setSeed(seeds[args.warmup])
         vr.setIteration(0)
         if world == 1:
@@ -754,6 +790,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
+            "full": bool(args.full),   # roofline, cpu_baseline and parity are only measured with --full
             "config": {
                 "workload": "%s: %d^3 %s '%s' field generated in HBM, %dx%d viewport (launch grid "
                             "%dx%d), view %s, TF %s, illumType %d, object-order ESS %s, ERT 0.98, "

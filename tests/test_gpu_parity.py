@@ -2283,7 +2283,7 @@ def test_bench_multi_gpu_path_rehearsed_over_rccl_on_one_gpu(tmp_path):
     for extra in ([], ["--frames-in-flight", "1", "--frames-per-launch", "1"]):
         p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "sphere64", "--viewport", "192",
                             "--steps", "12", "--warmup", "2", "--frames-per-gather", "5", "--cpu-seconds", "0.5",
-                            "--out-json", str(out)] + extra, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+                            "--full", "--out-json", str(out)] + extra, cwd=root, env=env, capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, (p.stdout[-1000:], p.stderr[-3000:])
         d = json.loads(out.read_text())
         assert d["n_gpus"] == 1 and "RCCL gather per 5 frames" in d["config"]["parallelism"]
@@ -2310,7 +2310,7 @@ def test_bench_multi_gpu_path_rehearsed_with_two_ranks_over_gloo(tmp_path):
         p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                             "--master-addr", "127.0.0.1", "--master-port", str(29561 + i), os.path.join(root, "bench.py"),
                             "--gpus", "2", "--workload", "sphere64", "--viewport", "192", "--tile", "32",
-                            "--out-json", str(out)] + extra, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+                            "--full", "--out-json", str(out)] + extra, cwd=root, env=env, capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, (p.stdout[-1000:], p.stderr[-3000:])
         d = json.loads(out.read_text())
         assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["value"] > 0
@@ -2318,6 +2318,45 @@ def test_bench_multi_gpu_path_rehearsed_with_two_ranks_over_gloo(tmp_path):
         assert len(d["parity"]["timed_frames"]) >= 1 and all(c["max_abs_diff"] <= TOL for c in d["parity"]["timed_frames"])
         assert d["cpu_baseline"] is None          # (rank 0 at N = 1 only)
         assert len(d["gather"]["tiles_per_rank"]) == 2
+
+
+def test_bench_plain_run_dumps_its_last_timed_frame(tmp_path):
+    """A plain bench.py run (no --full) prints the headline line without the roofline, CPU baseline and parity legs,
+    and --dump-outputs writes the frame its timed region rendered last -- batched launch sets and one frame at a
+    time alike -- equal to that frame rendered on its own with the same jitter seed."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup, W = 12, 2, 192
+    mt = frontend.Mt19937()
+    seed = [mt() for _ in range(warmup + steps)][-1]
+    ref = VolumeRenderCL()
+    ref.initialize()
+    try:
+        ref.synthVolume("sphere", (64, 64, 64), UCHAR)
+        ref.setTransferFunction(frontend.tff_from_stops())
+        ref.setIllumination(1)
+        ref.setObjEss(True)
+        ref.updateView(frontend.view_matrix(frontend.quat_from_axis_angle((1, 1, 0), 30.0)))
+        ref.setSeed(seed)
+        ref.setIteration(0)
+        want = ref.runRaycastNoGL(W, W)
+    finally:
+        ref.close()
+    for i, extra in enumerate(([], ["--frames-in-flight", "1", "--frames-per-launch", "1"])):
+        dump = tmp_path / ("dump%d" % i)
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "sphere64",
+                            "--viewport", str(W), "--steps", str(steps), "--warmup", str(warmup),
+                            "--dump-outputs", str(dump)] + extra, cwd=root, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, (p.stdout[-1000:], p.stderr[-3000:])
+        d = json.loads(p.stdout.strip().splitlines()[-1])
+        assert d["steps"] == steps and d["ms_per_step"] > 0 and d["value"] > 0 and d["full"] is False
+        assert d["unit"] == "Msamples/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["parity"] is None
+        img = np.load(dump / "image.npy")
+        assert img.dtype == np.float32 and img.shape == (W, W, 4)
+        np.testing.assert_array_equal(img, want)
 
 
 def test_control_blocks_alternate_cleanly(vr):

@@ -1,8 +1,9 @@
-"""The C++ host loader against the REFERENCE's own DatRawReader, live: random .dat/.raw files read by both
-(oracle/_ref/libref_datraw.so, compiled from /root/reference/src/io/datrawreader.cpp by `make -C oracle ref`).
-Runs where that library exists (the build container); the committed fixtures of test_loader_golden.py cover the
-same reader everywhere else."""
-import ctypes as C
+"""The C++ host loader against the REFERENCE's own DatRawReader: random .dat/.raw files against what the reference's
+src/io/datrawreader.cpp (built as oracle/_ref/libref_datraw.so by `make -C oracle ref`) read from the same files,
+recorded in tests/golden/reference_outputs.json by oracle/gen_reference_outputs.py.  The committed fixtures of
+test_loader_golden.py cover hand-made files of the same reader."""
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -11,15 +12,13 @@ import pytest
 from volumerenderercl_amd import datraw
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "libref_datraw.so")
-pytestmark = pytest.mark.skipif(not os.path.exists(REF), reason="compiled reference loader not present")
 
 
-class Result(C.Structure):
-    _fields_ = [("res", C.c_uint * 4), ("thickness", C.c_double * 3), ("format", C.c_int),
-                ("endianness", C.c_int), ("min_value", C.c_float), ("max_value", C.c_float),
-                ("n_timesteps", C.c_ulonglong), ("bytes_per_timestep", C.c_ulonglong),
-                ("channel_order", C.c_char * 16)]
+def recorded(case):
+    """What the reference returned for `case` (read when a test runs: oracle/gen_reference_outputs.py imports this
+    module to write the file)."""
+    with open(os.path.join(HERE, "golden", "reference_outputs.json")) as f:
+        return json.load(f)["loader_random"][case]
 
 
 def _random_dataset(rng, d):
@@ -65,33 +64,41 @@ def _random_dataset(rng, d):
     return dat
 
 
+def write_case(case, d):
+    """The random data set of `case`, written into directory d; returns the .dat's path."""
+    return _random_dataset(np.random.default_rng(44261004 + case), d)
+
+
+def input_sha256(d):
+    """One hash over every file of the data set (names and bytes, in name order)."""
+    h = hashlib.sha256()
+    for name in sorted(os.listdir(d)):
+        with open(os.path.join(d, name), "rb") as f:
+            h.update(name.encode() + b"\0" + f.read())
+    return h.hexdigest()
+
+
 @pytest.mark.parametrize("case", range(64))
 def test_random_files_read_like_the_reference(case, tmp_path):
-    ref = C.CDLL(REF)
-    ref.refdr_error.restype = C.c_char_p
-    rng = np.random.default_rng(44261004 + case)
-    dat = _random_dataset(rng, str(tmp_path))
-    want = Result()
-    rc = ref.refdr_load(dat.encode(), C.byref(want))
+    dat = write_case(case, str(tmp_path))
+    want = recorded(case)
+    assert input_sha256(str(tmp_path)) == want["input_sha256"], "the recorded data set was another"
     r = datraw.DatRawReader()
-    if rc != 0:
+    if want["rc"] != 0:
         with pytest.raises(RuntimeError) as e:
             r.read_files(datraw.Properties(dat))
-        assert str(e.value) == ref.refdr_error().decode()
+        assert str(e.value) == want["error"]
         return
     r.read_files(datraw.Properties(dat))
     p = r.properties()
-    assert p.volume_res == list(want.res)
-    assert p.slice_thickness == list(want.thickness)
-    assert p.format == want.format and p.endianness == want.endianness
-    assert p.image_channel_order == want.channel_order.decode()
-    assert len(r.data()) == want.n_timesteps
+    assert p.volume_res == want["res"]
+    assert p.slice_thickness == want["thickness"]
+    assert p.format == want["format"] and p.endianness == want["endianness"]
+    assert p.image_channel_order == want["channel_order"]
+    assert len(r.data()) == want["n_timesteps"]
     # NaN == NaN here: an all-zero FLOAT field divides 0 by 0 in both readers
-    np.testing.assert_array_equal(np.float32([p.min_value, p.max_value]), np.float32([want.min_value, want.max_value]))
-    for t in range(want.n_timesteps):
-        buf = (C.c_char * want.bytes_per_timestep)()
-        assert ref.refdr_copy_data(t, buf, want.bytes_per_timestep) == 0
-        assert r.data()[t].tobytes() == bytes(buf), "time step %d" % t   # bit-exact
-        h = (C.c_double * 256)()
-        assert ref.refdr_copy_histogram(t, h) == 0
-        np.testing.assert_array_equal(np.asarray(r.histograms()[t], dtype=np.float64), np.asarray(list(h)))
+    np.testing.assert_array_equal(np.float32([p.min_value, p.max_value]), np.float32(want["min_max"]))
+    for t in range(want["n_timesteps"]):
+        assert hashlib.sha256(r.data()[t].tobytes()).hexdigest() == want["data_sha256"][t], "time step %d" % t   # bit-exact
+        hist = np.ascontiguousarray(r.histograms()[t], dtype=np.float64)
+        assert hashlib.sha256(hist.tobytes()).hexdigest() == want["histogram_sha256"][t], "histogram %d" % t

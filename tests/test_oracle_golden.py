@@ -1,19 +1,25 @@
 """Pins the CPU oracle: (1) against the reference itself where it builds with no stand-ins
-(oracle/_ref: random.cl RNG) -- only where /root/reference was available to build it;
-(2) against the known-answer values the compiled reference produced (SURVEY.md App. E,
-tests/golden/survey_kats.json); (3) host-side sizing rules."""
+(oracle/_ref: random.cl RNG), through the outputs recorded from it in tests/golden/reference_outputs.json
+(oracle/gen_reference_outputs.py); (2) against the known-answer values the compiled reference produced
+(tests/golden/survey_kats.json); (3) host-side sizing rules."""
 import ctypes as C
+import hashlib
 import json
 import os
 
 import numpy as np
-import pytest
 
 from oracle import vro
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 KATS = json.load(open(os.path.join(HERE, "golden", "survey_kats.json")))
-REF_RNG = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "libref_rng.so")
+
+
+def recorded(section):
+    """Outputs of the compiled reference (read when a test runs: oracle/gen_reference_outputs.py imports this module
+    to write the file)."""
+    with open(os.path.join(HERE, "golden", "reference_outputs.json")) as f:
+        return json.load(f)[section]
 
 
 def test_rng_kats():
@@ -29,30 +35,30 @@ def test_rng_kats():
     assert [mt() for _ in range(3)] == KATS["mt19937_default_first3"]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_RNG), reason="oracle/_ref not built (no /root/reference)")
-def test_rng_bit_exact_vs_compiled_reference():
-    """random.cl compiled from the reference's own source (no stand-ins, RTLD_LAZY)."""
-    ref = C.CDLL(REF_RNG, mode=1)
-    ref.ParallelRNG.restype = C.c_uint32
-    ref.ParallelRNG.argtypes = [C.c_uint32]
-    ref.ParallelRNG3.restype = C.c_uint32
-    ref.ParallelRNG3.argtypes = [C.c_uint32] * 3
-    ref.mapUintFloat.restype = C.c_float
-    ref.mapUintFloat.argtypes = [C.c_uint32]
-    L = vro.lib()
+def rng_streams(parallel_rng, map_uint_float, parallel_rng3):
+    """sha256 of each function's outputs (uint32 / float32 bytes, in order) over 22003 arguments and 5728 triples."""
+    h = {name: hashlib.sha256() for name in ("ParallelRNG", "mapUintFloat", "ParallelRNG3")}
     rng = np.random.default_rng(1)
     xs = np.concatenate([np.arange(0, 2000), rng.integers(0, 2 ** 32, 20000),
                          [2 ** 32 - 1, 2 ** 31, 2 ** 31 - 1]]).astype(np.uint64)
     for x in xs:
         x = int(x)
-        assert L.vro_parallel_rng(x) == ref.ParallelRNG(x)
-        assert L.vro_map_uint_float(x) == ref.mapUintFloat(x)
+        h["ParallelRNG"].update(np.uint32(parallel_rng(x)).tobytes())
+        h["mapUintFloat"].update(np.float32(map_uint_float(x)).tobytes())
     tr = rng.integers(0, 2 ** 32, (5000, 3))
     for a, b, c in tr:
-        assert L.vro_parallel_rng3(int(a), int(b), int(c)) == ref.ParallelRNG3(int(a), int(b), int(c))
+        h["ParallelRNG3"].update(np.uint32(parallel_rng3(int(a), int(b), int(c))).tobytes())
     for gx in range(0, 1032, 37):
         for gy in range(0, 1032, 41):
-            assert L.vro_parallel_rng3(gx, gy, 3499211612) == ref.ParallelRNG3(gx, gy, 3499211612)
+            h["ParallelRNG3"].update(np.uint32(parallel_rng3(gx, gy, 3499211612)).tobytes())
+    return {name: d.hexdigest() for name, d in h.items()}
+
+
+def test_rng_bit_exact_vs_compiled_reference():
+    """random.cl compiled from the reference's own source (no stand-ins, RTLD_LAZY): the oracle's outputs hash
+    like the reference's on the same arguments."""
+    L = vro.lib()
+    assert rng_streams(L.vro_parallel_rng, L.vro_map_uint_float, L.vro_parallel_rng3) == recorded("rng")
 
 
 def test_intersect_bbox_kat():
@@ -144,7 +150,6 @@ def test_prefix_sum():
 
 
 # ---- the builtin-free functions of the reference's kernel file itself -----------------
-REF_KERNEL = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "libref_kernel.so")
 KFREE = json.load(open(os.path.join(HERE, "golden", "kernel_free.json")))
 
 
@@ -172,58 +177,53 @@ def test_hybrid_rng_and_box_edges_match_the_committed_reference_outputs():
         assert L.vro_check_bounding_box(f3(k["pos"]), f3(k["voxLen"]), k["bound"][0], k["bound"][1]) == k["ret"], k
 
 
-@pytest.mark.skipif(not os.path.exists(REF_KERNEL), reason="oracle/_ref not built (no /root/reference)")
-def test_hybrid_rng_bit_exact_vs_compiled_reference_kernel_file():
-    """volumeraycast.cl compiled from the reference's own source (66 OpenCL builtins left undefined,
-    RTLD_LAZY, nothing stands in for them): the functions that reach none of them, over 10^5 states."""
-    ref = C.CDLL(REF_KERNEL, mode=1)
-    U4 = C.POINTER(C.c_uint32)
-    ref.refk_hybrid_rand.restype = C.c_float
-    ref.refk_hybrid_rand.argtypes = [U4]
-    ref.refk_ui_rand_step.restype = C.c_uint32
-    ref.refk_ui_rand_step.argtypes = [U4, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32]
-    ref.refk_lcg_step.restype = C.c_uint32
-    ref.refk_lcg_step.argtypes = [U4, C.c_uint32, C.c_uint32]
-    ref.refk_check_bounding_box.restype = C.c_int
-    ref.refk_check_bounding_box.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float]
-    for name, n in (("ParallelRNG", 1), ("ParallelRNG3", 3)):   # the #include of random.cl, once more
-        getattr(ref, name).restype = C.c_uint32
-        getattr(ref, name).argtypes = [C.c_uint32] * n
-    L = vro.lib()
+def kernel_free_streams(f):
+    """sha256 of the outputs (and advanced states) of the kernel file's builtin-free functions over 10^5 generator
+    states and 20000 positions around the unit box's edges.  f maps hybrid_rand, ui_rand_step, lcg_step, parallel_rng,
+    parallel_rng3 and check_bounding_box to the oracle's functions or to the compiled reference's."""
+    h = {name: hashlib.sha256() for name in ("hybridui_rand", "steps", "ParallelRNG", "checkBoundingBox")}
     rng = np.random.default_rng(7)
     states = rng.integers(0, 2 ** 32, (100000, 4), dtype=np.uint64)
     states[:64, :] = np.arange(64, dtype=np.uint64)[:, None]           # small states
     states[64:128, 1:] = 0xFFFFFFFF
     for i, st in enumerate(states):
-        a, b = _u4(st), _u4(st)
-        ra, rb = L.vro_hybrid_rand(a), ref.refk_hybrid_rand(b)
-        assert np.float32(ra).tobytes() == np.float32(rb).tobytes() and list(a) == list(b), (i, list(st))
+        a = _u4(st)
+        h["hybridui_rand"].update(np.float32(f["hybrid_rand"](a)).tobytes() + bytes(a))
         if i % 8 == 0:     # a second draw from the advanced state, and the single steps
-            assert np.float32(L.vro_hybrid_rand(a)).tobytes() == np.float32(ref.refk_hybrid_rand(b)).tobytes()
+            h["hybridui_rand"].update(np.float32(f["hybrid_rand"](a)).tobytes())
             for args in ((0, 13, 19, 12, 4294967294), (1, 2, 25, 4, 4294967288), (2, 3, 11, 17, 4294967280)):
-                a, b = _u4(st), _u4(st)
-                assert L.vro_ui_rand_step(a, *args) == ref.refk_ui_rand_step(b, *args) and list(a) == list(b)
-            a, b = _u4(st), _u4(st)
-            assert L.vro_lcg_step(a, 1664525, 1013904223) == ref.refk_lcg_step(b, 1664525, 1013904223)
-            assert list(a) == list(b)
+                a = _u4(st)
+                h["steps"].update(np.uint32(f["ui_rand_step"](a, *args)).tobytes() + bytes(a))
+            a = _u4(st)
+            h["steps"].update(np.uint32(f["lcg_step"](a, 1664525, 1013904223)).tobytes() + bytes(a))
             x, y, z = int(st[0]), int(st[1]), int(st[2])
-            assert L.vro_parallel_rng(x) == ref.ParallelRNG(x)
-            assert L.vro_parallel_rng3(x, y, z) == ref.ParallelRNG3(x, y, z)
+            h["ParallelRNG"].update(np.uint32(f["parallel_rng"](x)).tobytes() +
+                                    np.uint32(f["parallel_rng3"](x, y, z)).tobytes())
     f3 = lambda v: (C.c_float * 3)(*v)
     for _ in range(20000):
         vox = rng.choice([1 / 32, 1 / 48, 1 / 256, 1 / 100], 3).astype(np.float32)
         pos = (rng.choice([0.0, 1.0, 0.5], 3) + rng.normal(0, 1.5, 3) * vox).astype(np.float32)
         b0, b1 = float(np.float32(rng.random() * 0.3)), float(np.float32(0.7 + rng.random() * 0.3))
-        assert L.vro_check_bounding_box(f3(pos), f3(vox), b0, b1) == ref.refk_check_bounding_box(f3(pos), f3(vox), b0, b1)
+        h["checkBoundingBox"].update(np.int32(f["check_bounding_box"](f3(pos), f3(vox), b0, b1)).tobytes())
+    return {name: d.hexdigest() for name, d in h.items()}
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(REF_KERNEL), "ref_kernel.o")),
-                    reason="oracle/_ref not built (no /root/reference)")
+def test_hybrid_rng_bit_exact_vs_compiled_reference_kernel_file():
+    """volumeraycast.cl compiled from the reference's own source (66 OpenCL builtins left undefined,
+    RTLD_LAZY, nothing stands in for them): the functions that reach none of them, over 10^5 states --
+    the oracle's outputs hash like the reference's (recorded in tests/golden/reference_outputs.json)."""
+    L = vro.lib()
+    got = kernel_free_streams({"hybrid_rand": L.vro_hybrid_rand, "ui_rand_step": L.vro_ui_rand_step,
+                               "lcg_step": L.vro_lcg_step, "parallel_rng": L.vro_parallel_rng,
+                               "parallel_rng3": L.vro_parallel_rng3, "check_bounding_box": L.vro_check_bounding_box})
+    assert got == recorded("kernel_free")
+
+
 def test_list_of_builtin_free_reference_functions():
-    """What can be pinned is exactly what oracle/ref_kernel_free.py finds in the compiled object: nothing
-    that needs an OpenCL builtin is executed, and nothing executable is left out."""
-    from oracle import ref_kernel_free
-    res = ref_kernel_free.analyse(os.path.join(os.path.dirname(REF_KERNEL), "ref_kernel.o"))
+    """What can be pinned is exactly what oracle/ref_kernel_free.py finds in the compiled object (its analysis,
+    recorded in tests/golden/reference_outputs.json): nothing that needs an OpenCL builtin is executed, and nothing
+    executable is left out."""
+    res = recorded("kernel_object_analysis")
     free = sorted(f for f, undefined in res.items() if not undefined)
     assert free == sorted(["ParallelRNG", "ParallelRNG2", "ParallelRNG3", "map256", "mapUintFloat", "ui_randStep",
                            "lcgStep", "hybridui_rand", "getf4", "checkBoundingBox"])

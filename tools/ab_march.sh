@@ -9,7 +9,7 @@ for WL in "$@"; do
   for MODE in march old; do
     if [ $MODE = march ]; then export VRHIP_MARCH=1; else unset VRHIP_MARCH; fi
     timeout -k 10 200 python3 $ROOT/bench.py --workload $WL --no-cpu-baseline --steps 32 --warmup 2 --frames-in-flight 1 --frames-per-launch 1 --out-json $OUT/${WL}_${MODE}_single.json > $OUT/${WL}_${MODE}_single.log 2>&1 || exit 1
-    timeout -k 10 200 python3 $ROOT/bench.py --workload $WL --no-cpu-baseline --steps 64 --warmup 2 --out-json $OUT/${WL}_${MODE}_tput.json > $OUT/${WL}_${MODE}_tput.log 2>&1 || exit 1
+    timeout -k 10 200 python3 $ROOT/bench.py --full --workload $WL --no-cpu-baseline --steps 64 --warmup 2 --out-json $OUT/${WL}_${MODE}_tput.json > $OUT/${WL}_${MODE}_tput.log 2>&1 || exit 1
     python3 - <<PY
 import json
 a=json.load(open("$OUT/${WL}_${MODE}_single.json")); b=json.load(open("$OUT/${WL}_${MODE}_tput.json"))

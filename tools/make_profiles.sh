@@ -43,7 +43,7 @@ region shells1024 shells1024 --warmup 4 --steps 64
 fi
 b() {   # NAME ARGS...
   local name=$1; shift
-  timeout -k 10 400 python3 bench.py "$@" --out-json "$OUT/bench_$name.json" > /dev/null 2> "$OUT/bench_$name.err"; echo "$name rc=$?"
+  timeout -k 10 400 python3 bench.py --full "$@" --out-json "$OUT/bench_$name.json" > /dev/null 2> "$OUT/bench_$name.err"; echo "$name rc=$?"
 }
 mkdir -p "$ROOT/profiles/$R"
 cp "$OUT"/pmc_issue_*.json "$OUT"/pmc_traffic_*.json "$ROOT/profiles/$R/" 2>/dev/null   # (the bench lines below look them up)
