@@ -116,6 +116,14 @@ public:
     void renderFramesTiles(size_t width, size_t height, size_t tile_w, size_t tile_h,
                            const std::vector<unsigned int> &tile_ids, const std::vector<unsigned int> &seeds,
                            float *dev_out, size_t frame_stride = 0);
+    // per-frame cameras (vrhip_render_batch_views): frame f rendered from views[f] (row-major, as updateView takes it)
+    // with this renderer's bbox and ortho setting -- a turntable, a fly-through, a replayed camera path;
+    // views.size() == seeds.size()
+    void renderFrames(size_t width, size_t height, const std::vector<unsigned int> &seeds,
+                      const std::vector<std::array<float, 16>> &views, float *dev_out);
+    void renderFramesTiles(size_t width, size_t height, size_t tile_w, size_t tile_h,
+                           const std::vector<unsigned int> &tile_ids, const std::vector<unsigned int> &seeds,
+                           const std::vector<std::array<float, 16>> &views, float *dev_out, size_t frame_stride = 0);
     // the jitter seeds the next n runRaycast calls would use (the default-seeded std::mt19937 member, or the pinned seed)
     std::vector<unsigned int> drawSeeds(size_t n);
     // phase-1 sample rounds per ray (vrhip_set_round_budget): 10 for one frame at a time, 48 for launch sets of

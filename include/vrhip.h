@@ -275,6 +275,14 @@ int vrhip_render_batch(vrhip_renderer *r, uint32_t width, uint32_t height, uint3
                        uint32_t tile_h, const uint32_t *tile_ids, uint32_t n_tiles,
                        const uint32_t *seeds, uint32_t n_frames, float *out_dev,
                        uint32_t out_frame_stride);
+/* The same with a camera per frame: frame f is rendered with cams[f] (n_frames HOST structs: view matrix,
+ * bbox, ortho) instead of the renderer's camera -- a turntable, a fly-through, a replayed camera path in one
+ * set of launches.  Everything else (transfer function, parameters, restrictions) is shared by the frames as
+ * in vrhip_render_batch; cams == NULL is exactly vrhip_render_batch. */
+int vrhip_render_batch_views(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t tile_w,
+                             uint32_t tile_h, const uint32_t *tile_ids, uint32_t n_tiles,
+                             const uint32_t *seeds, const vrhip_camera_params *cams, uint32_t n_frames,
+                             float *out_dev, uint32_t out_frame_stride);
 /* getLastExecTime (volumerendercl.cpp:1053-1056): HIP-event time of the last ray-cast
  * kernel launch, seconds. */
 double vrhip_last_kernel_seconds(const vrhip_renderer *r);
@@ -311,7 +319,8 @@ typedef struct vrhip_launch_info {
     uint32_t extras;         /* 1: the variants with the rarer modes (illumType 2-5, AO, contours, ...) */
     uint32_t patch_classes;  /* 1: the pre-pass used per-patch classes                                  */
     uint32_t sorted_phase2;  /* 1: suspended rays were counting-sorted, longest first                   */
-    uint32_t reserved[17];
+    uint32_t views;          /* 1: per-frame cameras (vrhip_render_batch_views with cams != NULL)       */
+    uint32_t reserved[16];
 } vrhip_launch_info;
 /* VRHIP_ERR_NODATA before the first render call. */
 int vrhip_last_launch_info(const vrhip_renderer *r, vrhip_launch_info *out);

@@ -214,6 +214,11 @@ double TileGather::renderFrame(std::vector<float> &out)
 
 void TileGather::submitFrames(const std::vector<unsigned int> &seeds)
 {
+    submitFrames(seeds, std::vector<std::array<float, 16>>());
+}
+
+void TileGather::submitFrames(const std::vector<unsigned int> &seeds, const std::vector<std::array<float, 16>> &views)
+{
     const size_t n = _ranks.size(), nf = seeds.size();
     if (_B == 0) throw std::runtime_error("TileGather: constructed without batch buffers");
     if (nf == 0 || nf > _B) throw std::invalid_argument("TileGather::submitFrames: 1 .. batch_frames frames per batch");
@@ -230,8 +235,12 @@ void TileGather::submitFrames(const std::vector<unsigned int> &seeds)
             hip_check(hipStreamWaitEvent(rs, static_cast<hipEvent_t>(_ev_sent[b][r]), 0), "hipStreamWaitEvent");
             if (r == 0) hip_check(hipStreamWaitEvent(rs, static_cast<hipEvent_t>(_ev_assembled[b]), 0), "hipStreamWaitEvent");
         }
-        if (!_tiles[r].empty())
-            _ranks[r]->renderFramesTiles(_W, _H, _tile, _tile, _tiles[r], seeds, _btiles[b][r], _cap * P);
+        if (!_tiles[r].empty()) {
+            if (views.empty())
+                _ranks[r]->renderFramesTiles(_W, _H, _tile, _tile, _tiles[r], seeds, _btiles[b][r], _cap * P);
+            else
+                _ranks[r]->renderFramesTiles(_W, _H, _tile, _tile, _tiles[r], seeds, views, _btiles[b][r], _cap * P);
+        }
         if (vrhip_pack_tiles(_ranks[r]->handle(), rs, _btiles[b][r], uint32_t(S), uint32_t(P), _bscratch[b][r], _bmsg[b][r],
                              _bcount[b][r]) != VRHIP_OK)
             throw std::runtime_error(std::string("ERROR: vrhip_pack_tiles (") + vrhip_last_error(_ranks[r]->handle()) + ")");

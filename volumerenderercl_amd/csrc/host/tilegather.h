@@ -16,6 +16,7 @@
 //    set of buffers, and the root assembling a batch straight from the messages (vrhip_message_positions +
 //    vrhip_assemble_batch).
 #pragma once
+#include <array>
 #include <cstddef>
 #include <cstdint>
 #include <deque>
@@ -60,6 +61,8 @@ public:
     // (its counts have reached the host by now, and this batch is already queued on the GPUs).  At most two
     // batches may be pending.
     void submitFrames(const std::vector<unsigned int> &seeds);
+    // the same with a camera per frame (views[f], row-major; VolumeRenderCL::renderFramesTiles): views.size() == seeds.size()
+    void submitFrames(const std::vector<unsigned int> &seeds, const std::vector<std::array<float, 16>> &views);
     // Finishes the oldest pending batch: exchange (if not started yet), assembly on the root; returns the root's
     // device buffer [n][height][width][4] holding its frames -- valid until the batch after the next is submitted --
     // and copies them to *host_out when that is not null.

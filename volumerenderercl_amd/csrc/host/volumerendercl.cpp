@@ -458,6 +458,33 @@ void VolumeRenderCL::renderFramesTiles(size_t width, size_t height, size_t tile_
                                              seeds.data(), uint32_t(seeds.size()), dev_out, uint32_t(frame_stride)));
 }
 
+void VolumeRenderCL::renderFrames(size_t width, size_t height, const std::vector<unsigned int> &seeds,
+                                  const std::vector<std::array<float, 16>> &views, float *dev_out)
+{
+    renderFramesTiles(width, height, 0, 0, std::vector<unsigned int>(), seeds, views, dev_out, 0);
+}
+
+void VolumeRenderCL::renderFramesTiles(size_t width, size_t height, size_t tile_w, size_t tile_h,
+                                       const std::vector<unsigned int> &tile_ids,
+                                       const std::vector<unsigned int> &seeds,
+                                       const std::vector<std::array<float, 16>> &views, float *dev_out,
+                                       size_t frame_stride)
+{
+    if (!_volLoaded) return;
+    if (views.size() != seeds.size()) throw std::invalid_argument("renderFrames: one view per frame");
+    _rendering_params.iteration = 0;
+    pushParams();
+    std::vector<vrhip_camera_params> cams(views.size());
+    for (size_t f = 0; f < views.size(); ++f) {
+        std::memcpy(&cams[f], &_camera_params, sizeof(vrhip_camera_params));
+        for (size_t i = 0; i < 16; ++i) cams[f].viewMat[i] = views[f][i];
+    }
+    check("renderFrames", vrhip_render_batch_views(_r, uint32_t(width), uint32_t(height), uint32_t(tile_w),
+                                                   uint32_t(tile_h), tile_ids.empty() ? nullptr : tile_ids.data(),
+                                                   uint32_t(tile_ids.size()), seeds.data(), cams.data(),
+                                                   uint32_t(seeds.size()), dev_out, uint32_t(frame_stride)));
+}
+
 std::vector<unsigned int> VolumeRenderCL::drawSeeds(size_t n)
 {
     std::vector<unsigned int> out(n);

@@ -187,6 +187,180 @@ std::array<float, 16> view_matrix(const double q[4], const double t[3])
     return m;
 }
 
+// ---- camera paths the GUI records, replayed one frame per camera entry (frontend.py read_view_record,
+// read_interaction_log, orbit_views: the same parse and the same double operations, float for float)
+struct PathEvent {
+    enum Kind { CAMERA, TRANSFER_FUNCTION, TIMESTEP } kind;
+    explicit PathEvent(Kind k) : kind(k) {}
+    std::array<float, 16> view{};
+    std::vector<unsigned char> tff;
+    int timestep = 0;
+};
+
+// QString::toFloat: the recorded numbers are read back as floats
+double parse_f32(const std::string &tok)
+{
+    size_t used = 0;
+    const double v = std::stod(tok, &used);
+    if (used != tok.size()) throw std::invalid_argument("not a number: " + tok);
+    return double(float(v));
+}
+
+std::vector<std::string> split_ws(const std::string &s)
+{
+    std::istringstream in(s);
+    std::vector<std::string> out;
+    std::string tok;
+    while (in >> tok) out.push_back(tok);
+    return out;
+}
+
+// `;`-separated entries of whitespace-separated numbers (recordViewConfig appends `w x y z; ` per view)
+std::vector<std::vector<std::string>> read_entries(const std::string &path)
+{
+    std::ifstream in(path);
+    if (!in) throw std::invalid_argument("Could not open view record " + path);
+    std::string all((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>()), part;
+    std::vector<std::vector<std::string>> out;
+    std::istringstream ss(all);
+    while (std::getline(ss, part, ';')) {
+        std::vector<std::string> e = split_ws(part);
+        if (!e.empty()) out.push_back(e);
+    }
+    return out;
+}
+
+// recordViewConfig (volumerenderwidget.cpp:1030-1048): <prefix>_quat.txt and <prefix>_trans.txt
+std::vector<PathEvent> read_view_record(const std::string &prefix)
+{
+    const auto quats = read_entries(prefix + "_quat.txt"), trans = read_entries(prefix + "_trans.txt");
+    if (quats.size() != trans.size())
+        throw std::invalid_argument("view record " + prefix + ": " + std::to_string(quats.size()) + " rotations but " +
+                                    std::to_string(trans.size()) + " translations");
+    if (quats.empty()) throw std::invalid_argument("view record " + prefix + ": no views");
+    std::vector<PathEvent> out;
+    for (size_t i = 0; i < quats.size(); ++i) {
+        if (quats[i].size() != 4 || trans[i].size() != 3)
+            throw std::invalid_argument("view record " + prefix + ": malformed entry " + std::to_string(i));
+        double q[4], t[3];
+        for (int k = 0; k < 4; ++k) q[k] = parse_f32(quats[i][size_t(k)]);
+        for (int k = 0; k < 3; ++k) t[k] = parse_f32(trans[i][size_t(k)]);
+        PathEvent e(PathEvent::CAMERA);
+        e.view = view_matrix(q, t);
+        out.push_back(e);
+    }
+    return out;
+}
+
+// the interaction log (toggleInteractionLogging / logInteraction, volumerenderwidget.cpp:313-358), parsed as
+// setSequenceStep (:364-408) does: the payload follows the last `;`; tffInterpolation lines are checked and dropped
+// (the logged tables are already sampled)
+std::vector<PathEvent> read_interaction_log(const std::string &path)
+{
+    std::ifstream in(path);
+    if (!in) throw std::invalid_argument("Invalid file name for interaction log: " + path);
+    std::vector<PathEvent> out;
+    std::string line;
+    bool any_camera = false;
+    for (size_t n = 1; std::getline(in, line); ++n) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (split_ws(line).empty()) continue;
+        const size_t pos = line.rfind(';');
+        const std::string where = "interaction log " + path + ", line " + std::to_string(n) + ": ";
+        if (pos == std::string::npos) throw std::invalid_argument(where + "no ';'");
+        const std::string payload = pos + 2 <= line.size() ? line.substr(pos + 2) : std::string();
+        try {
+            if (line.find("camera") != std::string::npos) {
+                std::string p = payload;
+                p.erase(std::remove(p.begin(), p.end(), ','), p.end());
+                const std::vector<std::string> tok = split_ws(p);
+                if (tok.size() != 7) throw std::invalid_argument("a camera entry is 7 numbers");
+                double q[4], t[3];
+                for (int k = 0; k < 4; ++k) q[k] = parse_f32(tok[size_t(k)]);
+                for (int k = 0; k < 3; ++k) t[k] = parse_f32(tok[size_t(4 + k)]);
+                PathEvent e(PathEvent::CAMERA);
+                e.view = view_matrix(q, t);
+                out.push_back(e);
+                any_camera = true;
+            } else if (line.find("timestep") != std::string::npos) {
+                const std::vector<std::string> tok = split_ws(payload);
+                size_t used = 0;
+                if (tok.size() != 1) throw std::invalid_argument("a timestep is one integer");
+                PathEvent e(PathEvent::TIMESTEP);
+                e.timestep = std::stoi(tok[0], &used);
+                if (used != tok[0].size()) throw std::invalid_argument("a timestep is one integer");
+                out.push_back(e);
+            } else if (line.find("transferFunction") != std::string::npos) {
+                PathEvent e(PathEvent::TRANSFER_FUNCTION);
+                for (const std::string &tok : split_ws(payload)) {
+                    size_t used = 0;
+                    const long v = std::stol(tok, &used);
+                    if (used != tok.size()) throw std::invalid_argument("not an integer: " + tok);
+                    e.tff.push_back(static_cast<unsigned char>(v & 0xff));
+                }
+                if (e.tff.empty() || e.tff.size() % 4) throw std::invalid_argument("a transfer function is RGBA8 entries");
+                out.push_back(e);
+            } else if (line.find("tffInterpolation") != std::string::npos) {
+                const std::vector<std::string> tok = split_ws(payload);
+                if (tok.size() != 1 || (tok[0] != "linear" && tok[0] != "quad" && tok[0] != "cubic"))
+                    throw std::invalid_argument("unknown interpolation");
+            } else {
+                throw std::invalid_argument("unknown event");
+            }
+        } catch (const std::logic_error &e) {   // (std::stod / stoi / stol throw invalid_argument or out_of_range)
+            throw std::invalid_argument(where + e.what());
+        }
+    }
+    if (!any_camera) throw std::invalid_argument("interaction log " + path + ": no camera entries");
+    return out;
+}
+
+// a turntable: n views over 360 degrees about `axis`, each step composed onto the start rotation as the GUI's mouse
+// rotation does (_rotQuat * step, volumerenderwidget.cpp:1115); QQuaternion::fromAxisAndAngle as frontend.py states it
+std::vector<PathEvent> orbit_views(const double axis[3], int n, const double q[4], const double t[3])
+{
+    const double l = std::sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
+    const double a[3] = {axis[0] / l, axis[1] / l, axis[2] / l};
+    std::vector<PathEvent> out;
+    for (int k = 0; k < n; ++k) {
+        const double h = (360.0 * k / n * (M_PI / 180.0)) / 2.0, s = std::sin(h);
+        const double p[4] = {std::cos(h), a[0] * s, a[1] * s, a[2] * s};
+        const double r[4] = {q[0] * p[0] - q[1] * p[1] - q[2] * p[2] - q[3] * p[3],
+                             q[0] * p[1] + q[1] * p[0] + q[2] * p[3] - q[3] * p[2],
+                             q[0] * p[2] - q[1] * p[3] + q[2] * p[0] + q[3] * p[1],
+                             q[0] * p[3] + q[1] * p[2] - q[2] * p[1] + q[3] * p[0]};
+        PathEvent e(PathEvent::CAMERA);
+        e.view = view_matrix(r, t);
+        out.push_back(e);
+    }
+    return out;
+}
+
+// A path cut where its transfer function or time step changes: the frames of a segment share both
+struct PathSegment {
+    std::vector<std::array<float, 16>> views;
+    const std::vector<unsigned char> *tff = nullptr;   // the table in force (nullptr: the options' table)
+    int timestep = -1;                                 // the time step in force (-1: the first)
+};
+
+std::vector<PathSegment> path_segments(const std::vector<PathEvent> &ev)
+{
+    std::vector<PathSegment> segs(1);
+    for (const PathEvent &e : ev) {
+        if (e.kind == PathEvent::CAMERA) { segs.back().views.push_back(e.view); continue; }
+        if (!segs.back().views.empty()) {
+            PathSegment next;
+            next.tff = segs.back().tff;
+            next.timestep = segs.back().timestep;
+            segs.push_back(next);
+        }
+        if (e.kind == PathEvent::TRANSFER_FUNCTION) segs.back().tff = &e.tff;
+        else segs.back().timestep = e.timestep;
+    }
+    if (segs.back().views.empty()) segs.pop_back();   // (changes after the last camera entry render nothing)
+    return segs;
+}
+
 void write_ppm(const std::string &path, const std::vector<float> &rgba, size_t w, size_t h)
 {
     std::ofstream f(path, std::ios::binary);
@@ -232,6 +406,13 @@ void write_ppm(const std::string &path, const std::vector<float> &rgba, size_t w
         "                                           budget B (default 48); --bench: one untimed set per renderer, then\n"
         "                                           the N frames timed with HIP events, nothing copied or written but\n"
         "                                           the last frame; --root-share: rank 0's share of a peer's tiles)\n"
+        "         [--camera-path FILE | --orbit AX AY AZ N] [--dump-views FILE]\n"
+        "                                          (one independent frame per camera entry of a path the reference GUI\n"
+        "                                           recorded -- FILE_quat.txt + FILE_trans.txt, or an interaction log\n"
+        "                                           whose transferFunction / timestep lines apply to the frames after\n"
+        "                                           them -- or of an N-view turntable about the axis from the start\n"
+        "                                           camera; --frames is ignored, the frames go to PREFIX.frames.rgba.f32;\n"
+        "                                           --dump-views writes the 16-float matrices and exits, no GPU)\n"
         "writes PREFIX.rgba.f32 (W*H*4 float32, row 0 = top), PREFIX.ppm and prints one JSON line\n";
     std::exit(2);
 }
@@ -260,6 +441,10 @@ int main(int argc, char **argv)
     double root_share = 1.0;
     double rate = 1.5;
     std::array<float, 4> bg = {{1, 1, 1, 1}};
+    std::string camera_path, dump_views;
+    bool have_path_arg = false, have_orbit = false;
+    double orbit_axis[3] = {0, 1, 0};
+    int orbit_n = 0;
 
     auto need = [&](int i, int n) { if (i + n >= argc) usage(); };
     for (int i = 1; i < argc; ++i) {
@@ -310,7 +495,57 @@ int main(int argc, char **argv)
         else if (a == "--round-budget") { need(i, 1); round_budget = std::atoi(argv[++i]); }
         else if (a == "--root-share") { need(i, 1); root_share = std::atof(argv[++i]); }
         else if (a == "--out") { need(i, 1); out = argv[++i]; }
+        else if (a == "--camera-path") { need(i, 1); camera_path = argv[++i]; have_path_arg = true; }
+        else if (a == "--orbit") {
+            need(i, 4);
+            for (int k = 0; k < 3; ++k) orbit_axis[k] = std::atof(argv[++i]);
+            orbit_n = std::atoi(argv[++i]);
+            have_orbit = true;
+        }
+        else if (a == "--dump-views") { need(i, 1); dump_views = argv[++i]; }
         else usage();
+    }
+    if (have_path_arg && (camera_path.empty() || have_orbit)) usage();
+    if (have_orbit && (orbit_n < 1 || orbit_n > 1 << 20 ||
+                       orbit_axis[0] * orbit_axis[0] + orbit_axis[1] * orbit_axis[1] + orbit_axis[2] * orbit_axis[2] == 0.0))
+        usage();
+    if (!dump_views.empty() && !have_path_arg && !have_orbit) usage();
+    // the camera path (--camera-path / --orbit), parsed before anything touches a GPU
+    std::vector<PathEvent> path_events;
+    std::vector<PathSegment> segs;
+    try {
+        if (have_path_arg) {
+            std::ifstream probe(camera_path + "_quat.txt");
+            path_events = probe ? read_view_record(camera_path) : read_interaction_log(camera_path);
+        } else if (have_orbit) {
+            if (!state_file.empty()) {   // (the orbit starts from the camera the options select, --state included)
+                const CamState st = read_cam_state(state_file);
+                if (st.has_rot) for (int k = 0; k < 4; ++k) q[k] = st.q[k];
+                if (st.has_tr) for (int k = 0; k < 3; ++k) tr[k] = st.t[k];
+            }
+            path_events = orbit_views(orbit_axis, orbit_n, q, tr);
+        }
+        if (!dump_views.empty()) {   // front-end formula only: nothing below touches a GPU
+            std::ofstream f(dump_views, std::ios::binary);
+            for (const PathEvent &e : path_events)
+                if (e.kind == PathEvent::CAMERA)
+                    f.write(reinterpret_cast<const char *>(e.view.data()), std::streamsize(16 * sizeof(float)));
+            return f ? 0 : 1;
+        }
+    } catch (const std::exception &e) {
+        std::cerr << e.what() << std::endl;
+        return 1;
+    }
+    const bool use_path = !path_events.empty();
+    if (use_path) {
+        segs = path_segments(path_events);
+        frames = 0;
+        for (const PathSegment &sg : segs) frames += int(sg.views.size());
+        independent = true;
+        if (pathtrace || img_ess) {
+            std::cerr << "--camera-path / --orbit: ray caster only, no image-order ESS" << std::endl;
+            return 1;
+        }
     }
     if (tf_easing != "linear" && tf_easing != "quad" && tf_easing != "cubic") usage();
     // the transfer-function table the options select (TransferFunctionWidget's default stops,
@@ -393,6 +628,37 @@ int main(int argc, char **argv)
         vr.updateView(have_view ? view : view_matrix(q, tr));
         return true;
         };
+        // what segment s of the camera path has in force (transfer function, time step), on renderer vr
+        auto apply_segment = [&](VolumeRenderCL &vr, size_t s) {
+            std::vector<unsigned char> table = segs[s].tff ? *segs[s].tff : make_table();
+            vr.setTransferFunction(table);
+            vr.setTimestep(size_t(segs[s].timestep < 0 ? 0 : segs[s].timestep));
+        };
+        // launch sets of <= K frames per segment (one segment and no views without a path), as many per segment as a
+        // multiple of `mult` renderers and all of (nearly) one size
+        struct LaunchSet { std::vector<unsigned int> seeds; std::vector<std::array<float, 16>> views; size_t seg; };
+        auto make_sets = [&](const std::vector<unsigned int> &seeds, size_t K, size_t mult) {
+            std::vector<LaunchSet> sets;
+            const size_t nseg = use_path ? segs.size() : 1;
+            size_t f0 = 0;
+            for (size_t sg = 0; sg < nseg; ++sg) {
+                const size_t nf = use_path ? segs[sg].views.size() : seeds.size();
+                size_t n_sets = (nf + K - 1) / K;
+                n_sets = std::min(nf, (n_sets + mult - 1) / mult * mult);
+                for (size_t i = 0; i < n_sets; ++i) {
+                    const size_t lo = size_t(std::llround(double(i) * double(nf) / double(n_sets)));
+                    const size_t hi = size_t(std::llround(double(i + 1) * double(nf) / double(n_sets)));
+                    if (hi <= lo) continue;
+                    LaunchSet ls;
+                    ls.seeds.assign(seeds.begin() + long(f0 + lo), seeds.begin() + long(f0 + hi));
+                    if (use_path) ls.views.assign(segs[sg].views.begin() + long(lo), segs[sg].views.begin() + long(hi));
+                    ls.seg = sg;
+                    sets.push_back(ls);
+                }
+                f0 += nf;
+            }
+            return sets;
+        };
 
         if (ranks > 0) {
             // image-tile decomposition over `ranks` GPUs: one renderer per rank, every
@@ -420,22 +686,46 @@ int main(int argc, char **argv)
                 // the throughput path: K independent frames per exchange, one exchange in flight
                 for (auto &v : vrs) { v->setRoundBudget(unsigned(round_budget)); v->setFrameTiming(false); }
                 std::vector<std::vector<unsigned int>> sets;
+                std::vector<std::vector<std::array<float, 16>>> set_views;   // (camera path: per set)
+                std::vector<size_t> set_seg;
                 std::vector<unsigned int> seeds = vrs[0]->drawSeeds(size_t(frames));
-                for (size_t f0 = 0; f0 < seeds.size(); f0 += K)
-                    sets.emplace_back(seeds.begin() + long(f0), seeds.begin() + long(std::min(seeds.size(), f0 + K)));
+                if (!use_path) {
+                    for (size_t f0 = 0; f0 < seeds.size(); f0 += K)
+                        sets.emplace_back(seeds.begin() + long(f0), seeds.begin() + long(std::min(seeds.size(), f0 + K)));
+                } else {   // sets of <= K frames that do not cross a change of transfer function or time step
+                    size_t at = 0;
+                    for (size_t sg = 0; sg < segs.size(); ++sg)
+                        for (size_t f0 = 0; f0 < segs[sg].views.size(); f0 += K) {
+                            const size_t f1 = std::min(segs[sg].views.size(), f0 + K);
+                            sets.emplace_back(seeds.begin() + long(at + f0), seeds.begin() + long(at + f1));
+                            set_views.emplace_back(segs[sg].views.begin() + long(f0), segs[sg].views.begin() + long(f1));
+                            set_seg.push_back(sg);
+                        }
+                    for (const PathSegment &sg : segs) at += sg.views.size();
+                }
                 if (bench) {   // untimed: buffers, work queues, cost maps, communicators
                     std::mt19937 warm(20261004u);
                     std::vector<unsigned int> ws(std::min(K, size_t(frames)));
                     for (int rep = 0; rep < 2; ++rep) {
                         for (auto &x : ws) x = static_cast<unsigned int>(warm());
-                        tg.submitFrames(ws);
+                        if (use_path) tg.submitFrames(std::vector<unsigned int>(ws.begin(), ws.begin() + long(set_views[0].size())), set_views[0]);
+                        else tg.submitFrames(ws);
                     }
                     tg.collectFrames(nullptr);
                     tg.collectFrames(nullptr);
                 }
                 const auto t0 = std::chrono::steady_clock::now();
                 for (size_t k = 0; k < sets.size(); ++k) {
-                    tg.submitFrames(sets[k]);
+                    if (use_path && (k == 0 || set_seg[k] != set_seg[k - 1])) {
+                        // a new transfer function / time step: the batches in flight are finished first
+                        while (tg.pending()) {
+                            tg.collectFrames(bench ? nullptr : &frame);
+                            if (!bench) all_frames.insert(all_frames.end(), frame.begin(), frame.end());
+                        }
+                        for (auto &v : vrs) apply_segment(*v, set_seg[k]);
+                    }
+                    if (use_path) tg.submitFrames(sets[k], set_views[k]);
+                    else tg.submitFrames(sets[k]);
                     if (tg.pending() == 2) {
                         tg.collectFrames(bench ? nullptr : &frame);
                         if (!bench) all_frames.insert(all_frames.end(), frame.begin(), frame.end());
@@ -448,9 +738,19 @@ int main(int argc, char **argv)
                 secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
                 frame.erase(frame.begin(), frame.end() - long(W * H * 4));   // the last frame of the last batch
             } else {
-                for (int f = 0; f < frames; ++f) {
+                for (size_t sg = 0, in_seg = 0, f = 0; f < size_t(frames); ++f, ++in_seg) {
+                    const std::array<float, 16> *pv = &the_view;
+                    if (use_path) {   // frame f of the path: frame in_seg of segment sg
+                        if (f == 0) for (auto &v : vrs) apply_segment(*v, 0);
+                        if (in_seg == segs[sg].views.size()) {
+                            ++sg;
+                            in_seg = 0;
+                            for (auto &v : vrs) apply_segment(*v, sg);
+                        }
+                        pv = &segs[sg].views[in_seg];
+                    }
                     if (independent)
-                        for (auto &v : vrs) v->updateView(the_view);   // (resets the running mean: iteration 0)
+                        for (auto &v : vrs) v->updateView(*pv);   // (resets the running mean: iteration 0)
                     secs += tg.renderFrame(frame);
                     if (independent) all_frames.insert(all_frames.end(), frame.begin(), frame.end());
                 }
@@ -510,21 +810,26 @@ int main(int argc, char **argv)
                 lanes[j]->setFrameTiming(false);   // nobody reads a set's own time: the next set may start under its tail
             }
             const std::vector<unsigned int> seeds = vr.drawSeeds(size_t(frames));
-            // launch sets of <= K frames, as many as a multiple of the renderers and all of (nearly) one size
-            size_t n_sets = (size_t(frames) + K - 1) / K;
-            n_sets = std::min(size_t(frames), (n_sets + F - 1) / F * F);
-            std::vector<std::vector<unsigned int>> sets;
-            for (size_t i = 0; i < n_sets; ++i) {
-                const size_t lo = size_t(std::llround(double(i) * frames / double(n_sets)));
-                const size_t hi = size_t(std::llround(double(i + 1) * frames / double(n_sets)));
-                if (hi > lo) sets.emplace_back(seeds.begin() + long(lo), seeds.begin() + long(hi));
-            }
+            // launch sets of <= K frames, as many as a multiple of the renderers and all of (nearly) one size (per
+            // segment of a camera path: a set never crosses a change of transfer function or time step)
+            const std::vector<LaunchSet> sets = make_sets(seeds, K, F);
+            std::vector<size_t> lane_seg(F, 0);
+            if (use_path)
+                for (size_t j = 0; j < F; ++j) apply_segment(*lanes[j], 0);
+            auto submit = [&](size_t j, const LaunchSet &ls, const std::vector<unsigned int> &sd) {
+                if (use_path && lane_seg[j] != ls.seg) {
+                    apply_segment(*lanes[j], ls.seg);   // (waits for the renderer's stream: its sets in flight)
+                    lane_seg[j] = ls.seg;
+                }
+                if (use_path) lanes[j]->renderFrames(W, H, sd, ls.views, blocks[j]);
+                else lanes[j]->renderFrames(W, H, sd, blocks[j]);
+            };
             if (bench) {   // every renderer once, untimed: buffers, work queue, skip bitmap, cell grid, cost map
                 std::mt19937 warm(20261004u);
                 for (size_t j = 0; j < F; ++j) {
-                    std::vector<unsigned int> ws(sets[0].size());
+                    std::vector<unsigned int> ws(sets[0].seeds.size());
                     for (auto &x : ws) x = static_cast<unsigned int>(warm());
-                    lanes[j]->renderFrames(W, H, ws, blocks[j]);
+                    submit(j, sets[0], ws);
                 }
                 hip_ok(hipDeviceSynchronize(), "hipDeviceSynchronize");
             }
@@ -538,12 +843,12 @@ int main(int argc, char **argv)
             hip_ok(hipEventRecord(ev0, streams[0]), "hipEventRecord");
             for (size_t j = 1; j < F; ++j) hip_ok(hipStreamWaitEvent(streams[j], ev0, 0), "hipStreamWaitEvent");
             for (size_t i = 0; i < sets.size(); ++i) {
-                lanes[i % F]->renderFrames(W, H, sets[i], blocks[i % F]);
+                submit(i % F, sets[i], sets[i].seeds);
                 if (!bench && ((i + 1) % F == 0 || i + 1 == sets.size())) {
                     // the frames of this round of sets to the host, in frame order, before their blocks are reused
                     hip_ok(hipDeviceSynchronize(), "hipDeviceSynchronize");
                     for (size_t k = i / F * F; k <= i; ++k) {
-                        const size_t at = all_frames.size(), nfl = sets[k].size() * W * H * 4;
+                        const size_t at = all_frames.size(), nfl = sets[k].seeds.size() * W * H * 4;
                         all_frames.resize(at + nfl);
                         hip_ok(hipMemcpy(all_frames.data() + at, blocks[k % F], nfl * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy");
                     }
@@ -561,7 +866,7 @@ int main(int argc, char **argv)
             // the last frame of the last set
             const size_t last = sets.size() - 1;
             frame.resize(W * H * 4);
-            hip_ok(hipMemcpy(frame.data(), blocks[last % F] + (sets[last].size() - 1) * W * H * 4, frame.size() * sizeof(float),
+            hip_ok(hipMemcpy(frame.data(), blocks[last % F] + (sets[last].seeds.size() - 1) * W * H * 4, frame.size() * sizeof(float),
                              hipMemcpyDeviceToHost), "hipMemcpy");
             vrhip_launch_info li;
             std::memset(&li, 0, sizeof li);
@@ -581,7 +886,7 @@ int main(int argc, char **argv)
                         "\"clock\": \"HIP events around the region on the first renderer's stream, the other renderers' "
                         "streams joined before the second%s\", \"out\": \"%s.rgba.f32\"}\n",
                         vr.getCurrentDeviceName().c_str(), res[0], res[1], res[2], W, H, frames, F, sets.size(),
-                        sets[0].size(), li.round_budget, li.phase1_waves, li.phase2_waves, li.empty_skip,
+                        sets[0].seeds.size(), li.round_budget, li.phase1_waves, li.phase2_waves, li.empty_skip,
                         double(ms) / frames, wall / frames * 1e3, bench ? "true" : "false",
                         bench ? "" : " (frames copied to the host inside the region)", out.c_str());
             for (float *b : blocks) (void)hipFree(b);
@@ -591,8 +896,17 @@ int main(int argc, char **argv)
             return 0;
         }
         const std::array<float, 16> the_view = have_view ? view : view_matrix(q, tr);
-        for (int f = 0; f < frames; ++f) {
-            if (independent) vr.updateView(the_view);   // (resets the running mean: iteration 0, volumerendercl.cpp:379-390)
+        for (size_t sg = 0, in_seg = 0, f = 0; f < size_t(frames); ++f, ++in_seg) {
+            const std::array<float, 16> *pv = &the_view;
+            if (use_path) {   // frame f of the path: frame in_seg of segment sg
+                if (f == 0) apply_segment(vr, 0);
+                if (in_seg == segs[sg].views.size()) {
+                    apply_segment(vr, ++sg);
+                    in_seg = 0;
+                }
+                pv = &segs[sg].views[in_seg];
+            }
+            if (independent) vr.updateView(*pv);   // (resets the running mean: iteration 0, volumerendercl.cpp:379-390)
             vr.runRaycastNoGL(W, H, frame);   // frames accumulate (running mean), like the reference
             kernel_s += vr.getLastExecTime();
             if (independent) all_frames.insert(all_frames.end(), frame.begin(), frame.end());

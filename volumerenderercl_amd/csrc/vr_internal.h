@@ -152,6 +152,9 @@ struct FrameView {
     uint32_t *cont_head;   // zeroed before each launch
     uint32_t round_budget;
     const uint32_t *seeds; // per frame of a batch (WaveTile frame index), or nullptr: rendering_params.seed
+    // per frame of a batch, like `seeds` (vrhip_render_batch_views): view matrix, box and ortho of frame f, or
+    // nullptr: the launch's camera for every frame.  Read only by the kernels instantiated with VIEWS = true.
+    const vrhip_camera_params *cams;
     uint32_t refill_min;   // phase 2: idle ray slots of a wave before they take new rays (0 = all 16)
     // DDA pre-pass (ESS, un-instrumented): a light, high-occupancy kernel walks every ray to its
     // first non-skipped brick; rays that never reach one get their (background) pixel there and

@@ -207,6 +207,40 @@ VR_DEV void setup_ray(uint32_t gx, uint32_t gy, bool inside, const FrameView &fr
     setup_ray_tail<ESS>(rcp, resf, voxLen, g, c, d, rnd);
 }
 
+// Per-frame cameras (FrameView::cams, kernels instantiated with VIEWS = true): frame f's camera, the fields make_ray
+// reads -- rows 0-2 of the view matrix, the box, ortho -- from the batch's table.  UNIFORM: f is the same in every lane
+// (one patch of one frame per wave) and the values go to scalar registers, as the launch's by-value camera does.
+// The VIEWS = false kernels never call this: they compile as they did before the table existed.
+template <bool UNIFORM>
+VR_DEV vrhip_camera_params load_frame_cam(const vrhip_camera_params *cams, uint32_t f)
+{
+    if (UNIFORM) f = __builtin_amdgcn_readfirstlane(f);
+    const float4 *p = reinterpret_cast<const float4 *>(cams + f);
+    vrhip_camera_params k;
+    float v[18];
+    for (int i = 0; i < 3; ++i) {
+        const float4 row = p[i];
+        v[4 * i] = row.x; v[4 * i + 1] = row.y; v[4 * i + 2] = row.z; v[4 * i + 3] = row.w;
+    }
+    const float4 bl = p[4], tr = p[5];
+    v[12] = bl.x; v[13] = bl.y; v[14] = bl.z;
+    v[15] = tr.x; v[16] = tr.y; v[17] = tr.z;
+    uint32_t ortho = reinterpret_cast<const uint32_t *>(p)[24];
+    if (UNIFORM) {
+        for (int i = 0; i < 18; ++i)
+            v[i] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v[i])));
+        ortho = __builtin_amdgcn_readfirstlane(ortho);
+    }
+    for (int i = 0; i < 12; ++i) k.viewMat[i] = v[i];
+    k.viewMat[12] = k.viewMat[13] = k.viewMat[14] = 0.f;
+    k.viewMat[15] = 1.f;
+    for (int i = 0; i < 3; ++i) { k.bbox_bl[i] = v[12 + i]; k.bbox_tr[i] = v[15 + i]; }
+    k.bbox_bl[3] = k.bbox_tr[3] = 0.f;
+    k.ortho = ortho;
+    for (int i = 0; i < 7; ++i) k._pad[i] = 0u;
+    return k;
+}
+
 // bitmap word of the cell the ray is in (out-of-range cells read the trailing word, which
 // holds the (0,0) decision in every bit)
 VR_DEV void fetch_skip_word(const uint32_t *sb, const Grid &g, RayDyn &d)
@@ -1117,7 +1151,7 @@ __global__ __launch_bounds__(kBlockDim) void vr_patch_class_kernel(SkipView skip
     if (lane == 0) cls[pi] = clear ? 1 : 0;
 }
 
-template <typename VT>
+template <typename VT, bool VIEWS = false>
 __global__ __launch_bounds__(kBlockDim) void vr_dda_prepass_kernel(
     VolView vv, BrickView bricks, SkipView skip, FrameView fr, vrhip_camera_params cam,
     vrhip_rendering_params rp, vrhip_raycast_params rc, Grid grid, f3 voxLen)
@@ -1147,7 +1181,12 @@ __global__ __launch_bounds__(kBlockDim) void vr_dda_prepass_kernel(
     RayCtx c;
     RayDyn d;
     float rnd;
-    setup_ray_head<false>(gx, gy, inside, fr, cam, rp, c, d, seed, rnd);   // (nothing is shaded here)
+    if constexpr (VIEWS) {
+        const vrhip_camera_params fc = load_frame_cam<true>(fr.cams, wt_frame(wt));
+        setup_ray_head<false>(gx, gy, inside, fr, fc, rp, c, d, seed, rnd);
+    } else {
+        setup_ray_head<false>(gx, gy, inside, fr, cam, rp, c, d, seed, rnd);   // (nothing is shaded here)
+    }
     if (rp.imgEss && image_ess_patch(fr, rp, c, wt, lane, inside, gx, gy, out_index)) return;
     if (skip.near_bits && patch_is_clear(skip, grid, c, lane)) {
         // no ray of this patch can meet a brick that is not skipped: what the walk would leave
@@ -1236,7 +1275,7 @@ __global__ __launch_bounds__(kBlockDim) void vr_dda_prepass_kernel(
 // third wave only stretches the chain of the longest rays.  See launch_variant.
 constexpr int kWavesWide = 12;
 
-template <typename VT, bool SKIP_LDS, bool FP, int WAVES = 4>
+template <typename VT, bool SKIP_LDS, bool FP, int WAVES = 4, bool VIEWS = false>
 __global__ __launch_bounds__(WAVES * 64) void vr_raycast_rays_kernel(
     VolView vv, BrickView bricks, TfView tf, SkipView skip, CellView cells, FrameView fr,
     vrhip_camera_params cam, vrhip_rendering_params rp, vrhip_raycast_params rc)
@@ -1333,8 +1372,14 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_rays_kernel(
                             gy = rec.pix >> 16;
                             out_index = rec.out_index;
                             frame_idx = (uint32_t)rec.state >> 8;
-                            setup_ray<true>(gx, gy, true, fr, cam, rp, rc, resf, voxLen, grid, c, d,
-                                            fr.seeds ? fr.seeds[frame_idx] : rp.seed);
+                            if constexpr (VIEWS) {   // (the lanes of a wave may hold rays of different frames)
+                                const vrhip_camera_params fc = load_frame_cam<false>(fr.cams, frame_idx);
+                                setup_ray<true>(gx, gy, true, fr, fc, rp, rc, resf, voxLen, grid, c, d,
+                                                fr.seeds ? fr.seeds[frame_idx] : rp.seed);
+                            } else {
+                                setup_ray<true>(gx, gy, true, fr, cam, rp, rc, resf, voxLen, grid, c, d,
+                                                fr.seeds ? fr.seeds[frame_idx] : rp.seed);
+                            }
                             d.state = rec.state & 0xff;
                             d.t = rec.t; d.t_exit = rec.t_exit; d.alpha = rec.alpha;
                             d.r0 = rec.r0; d.r1 = rec.r1; d.r2 = rec.r2;
@@ -1475,7 +1520,7 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_rays_kernel(
 
 // ------------------------------------------------------------------ phase 1
 
-template <typename VT, bool ESS, int INSTR, bool SKIP_LDS, bool XS, bool FP>
+template <typename VT, bool ESS, int INSTR, bool SKIP_LDS, bool XS, bool FP, bool VIEWS = false>
 __global__ __launch_bounds__(kBlockDim) VR_OCC void vr_raycast_kernel(
     VolView vv, BrickView bricks, TfView tf, SkipView skip, CellView cells, FrameView fr,
     vrhip_camera_params cam, vrhip_rendering_params rp, vrhip_raycast_params rc, DevStats *stats,
@@ -1539,7 +1584,12 @@ __global__ __launch_bounds__(kBlockDim) VR_OCC void vr_raycast_kernel(
 
         RayCtx c;
         RayDyn d;
-        setup_ray<ESS>(gx, gy, inside, fr, cam, rp, rc, resf, voxLen, grid, c, d, seed);
+        if constexpr (VIEWS) {
+            const vrhip_camera_params fc = load_frame_cam<true>(fr.cams, frame_idx);
+            setup_ray<ESS>(gx, gy, inside, fr, fc, rp, rc, resf, voxLen, grid, c, d, seed);
+        } else {
+            setup_ray<ESS>(gx, gy, inside, fr, cam, rp, rc, resf, voxLen, grid, c, d, seed);
+        }
         if (XS && rp.imgEss && !use_live &&   // (with a live list the pre-pass has done this)
             image_ess_patch(fr, rp, c, wt, lane, inside, gx, gy,
                             (size_t)wt.out_base + (size_t)ly * fr.out_stride + lx))
@@ -1680,7 +1730,7 @@ VR_DEV void composite_from(const RayCtx &c, RayDyn &d, const float (&p0)[kBatch]
 // lane replays the compositing of all 16 in ray order, fetching the other lanes' results with
 // in-quad DPP broadcasts -- the fp32 operation sequence per ray is exactly phase 1's (and the
 // reference's), the serial chain of a long ray is 4x shorter.
-template <typename VT, bool ESS, int INSTR, bool SKIP_LDS, bool XS, bool FP, int WAVES = 4>
+template <typename VT, bool ESS, int INSTR, bool SKIP_LDS, bool XS, bool FP, int WAVES = 4, bool VIEWS = false>
 __global__ __launch_bounds__(WAVES * 64) void vr_raycast_split_kernel(
     VolView vv, BrickView bricks, TfView tf, SkipView skip, CellView cells, FrameView fr,
     vrhip_camera_params cam, vrhip_rendering_params rp, vrhip_raycast_params rc, DevStats *stats,
@@ -1783,8 +1833,14 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_split_kernel(
                             gy = rec.pix >> 16;
                             out_index = rec.out_index;
                             const uint32_t f = (uint32_t)rec.state >> 8;
-                            setup_ray<ESS>(gx, gy, true, fr, cam, rp, rc, resf, voxLen, grid, c, d,
-                                           fr.seeds ? fr.seeds[f] : rp.seed);
+                            if constexpr (VIEWS) {   // (per lane: the quads of a wave may hold rays of different frames)
+                                const vrhip_camera_params fc = load_frame_cam<false>(fr.cams, f);
+                                setup_ray<ESS>(gx, gy, true, fr, fc, rp, rc, resf, voxLen, grid, c, d,
+                                               fr.seeds ? fr.seeds[f] : rp.seed);
+                            } else {
+                                setup_ray<ESS>(gx, gy, true, fr, cam, rp, rc, resf, voxLen, grid, c, d,
+                                               fr.seeds ? fr.seeds[f] : rp.seed);
+                            }
                             d.state = rec.state & 0xff;
                             d.t = rec.t; d.t_exit = rec.t_exit; d.alpha = rec.alpha;
                             d.r0 = rec.r0; d.r1 = rec.r1; d.r2 = rec.r2;
@@ -2089,16 +2145,18 @@ inline bool wide_fits_lds(const RaycastLaunch &a) { return march_lds(kWavesWide,
 #endif
 
 
-template <typename VT, bool ESS, int INSTR, bool SKIP_LDS, bool XS, bool FP = false>
+// VIEWS: the kernels that take frame f's camera from FrameView::cams (a batch of per-frame views) instead of the
+// launch's; the VIEWS = false instantiations are the ones every other launch runs, unchanged by the option.
+template <typename VT, bool ESS, int INSTR, bool SKIP_LDS, bool XS, bool FP = false, bool VIEWS = false>
 hipError_t launch_variant(const RaycastLaunch &a, hipStream_t stream)
 {
-    auto k1 = vr_raycast_kernel<VT, ESS, INSTR, SKIP_LDS, XS, FP>;
-    auto k2 = vr_raycast_split_kernel<VT, ESS, INSTR, SKIP_LDS, XS, FP>;
+    auto k1 = vr_raycast_kernel<VT, ESS, INSTR, SKIP_LDS, XS, FP, VIEWS>;
+    auto k2 = vr_raycast_split_kernel<VT, ESS, INSTR, SKIP_LDS, XS, FP, 4, VIEWS>;
     // three waves per SIMD (RaycastLaunch::occ3 / occ3_split): the default kernels on the footprint volume as ONE
     // workgroup of kWavesWide waves per CU (launch_typed keeps SKIP_LDS for them when the bitmap fits beside 12 stages)
     constexpr bool kWide = ESS && INSTR == 0 && !XS && FP;
     const bool wide2 = kWide && a.occ3_split;
-    if (wide2) k2 = vr_raycast_split_kernel<VT, ESS, INSTR, SKIP_LDS, XS, FP, kWide ? kWavesWide : 4>;
+    if (wide2) k2 = vr_raycast_split_kernel<VT, ESS, INSTR, SKIP_LDS, XS, FP, kWide ? kWavesWide : 4, VIEWS>;
     const int waves2 = wide2 ? kWavesWide : 4;
     const size_t lds = march_lds(4, a, ESS && SKIP_LDS);
     const size_t lds2 = march_lds(waves2, a, ESS && SKIP_LDS);
@@ -2144,12 +2202,13 @@ hipError_t launch_variant(const RaycastLaunch &a, hipStream_t stream)
         hg.brickDia = sqrtf(((hg.bl0 * hg.bl0) + (hg.bl1 * hg.bl1)) + (hg.bl2 * hg.bl2)) * 2.f;
         f3 hv;
         hv.x = 1.f / a.vol.fw; hv.y = 1.f / a.vol.fh; hv.z = 1.f / a.vol.fd;
-        vr_launch_kernel(vr_dda_prepass_kernel<VT>, dim3(want), block, 0, stream, start_ev, nullptr, a.vol, a.bricks,
+        vr_launch_kernel(vr_dda_prepass_kernel<VT, VIEWS>, dim3(want), block, 0, stream, start_ev, nullptr, a.vol, a.bricks,
                          a.skip, frame, a.cam, a.render, a.raycast, hg, hv);
         hipError_t pe = hipGetLastError();
         if (pe != hipSuccess) return pe;
         if (start_ev) { *a.start_bound = true; start_ev = nullptr; }
         if (a.info) { a.info->prepass = 1; a.info->patch_classes = frame.patch_class ? 1u : 0u; }
+        if (VIEWS && frame.patch_class) return hipErrorInvalidValue;   // (classes hold for one camera: the host turns them off)
     } else {
         frame.live = nullptr;
     }
@@ -2159,6 +2218,7 @@ hipError_t launch_variant(const RaycastLaunch &a, hipStream_t stream)
     const bool p1_last = a.frame.round_budget == 0;
     const hipEvent_t p1_ev = !a.bind_events ? nullptr : (p1_last && bind_stop) ? a.stop_event : a.mid_event;
 #ifdef VR_EXPERIMENTS
+    if (VIEWS && frame.march) return hipErrorNotSupported;   // (the experiment kernels take one camera per launch)
     if (ESS && INSTR == 0 && !XS && frame.live && frame.live_rays && frame.march && !a.raycast.contours &&
         !a.raycast.aerial) {
         if (start_ev && hipEventRecord(start_ev, stream) == hipSuccess) *a.start_bound = true;
@@ -2172,12 +2232,12 @@ hipError_t launch_variant(const RaycastLaunch &a, hipStream_t stream)
         const bool r3 = kWideR && a.occ3;
         const bool rlds = a.skip.in_lds != 0 && (!r3 || wide_fits_lds(a));
         const int waves_r = r3 ? kWavesWide : 4;
-        auto kr = vr_raycast_rays_kernel<VT, false, FP>;
+        auto kr = vr_raycast_rays_kernel<VT, false, FP, 4, VIEWS>;
         if (r3) {
-            kr = vr_raycast_rays_kernel<VT, false, FP, kWideR ? kWavesWide : 4>;
-            if (rlds) kr = vr_raycast_rays_kernel<VT, true, FP, kWideR ? kWavesWide : 4>;
+            kr = vr_raycast_rays_kernel<VT, false, FP, kWideR ? kWavesWide : 4, VIEWS>;
+            if (rlds) kr = vr_raycast_rays_kernel<VT, true, FP, kWideR ? kWavesWide : 4, VIEWS>;
         } else if (rlds) {
-            kr = vr_raycast_rays_kernel<VT, true, FP>;
+            kr = vr_raycast_rays_kernel<VT, true, FP, 4, VIEWS>;
         }
         const size_t lds_r = march_lds(waves_r, a, rlds);
         int nbr = 0;
@@ -2213,7 +2273,7 @@ hipError_t launch_variant(const RaycastLaunch &a, hipStream_t stream)
     return e;
 }
 
-template <typename VT>
+template <typename VT, bool VIEWS>
 hipError_t launch_typed(const RaycastLaunch &a, hipStream_t stream)
 {
     // (phase 2 and the patch kernels; phase 1 on the ray list: launch_variant)
@@ -2224,30 +2284,33 @@ hipError_t launch_typed(const RaycastLaunch &a, hipStream_t stream)
                     a.render.imgEss != 0 || a.vol.channels > 1 || a.raycast.contours != 0 ||
                     a.raycast.aerial != 0 || a.render.useLinear == 0;
 #ifdef VR_EXPERIMENTS
+    if (VIEWS && a.frame.lds_stage) return hipErrorNotSupported;
     if (a.frame.lds_stage && !xs && a.instr == 0 && a.use_ess && sizeof(VT) == 1 && !a.raycast.contours &&
         !a.raycast.aerial && a.frame.n_wave_tiles) {
         if (a.bind_events && a.start_bound && hipEventRecord(a.start_event, stream) == hipSuccess) *a.start_bound = true;
         return launch_staged(a, stream);
     }
 #endif
+    // the traffic pass (instr 2: vrhip_count_touched) renders one camera
+    if (VIEWS && a.instr >= 2) return hipErrorNotSupported;
     // the default kernels read the footprint volume when the host has provided one for this frame
     if (!xs && a.instr == 0 && a.vol.fp) {
-        if (!a.use_ess) return launch_variant<VT, false, 0, false, false, true>(a, stream);
-        return lds ? launch_variant<VT, true, 0, true, false, true>(a, stream)
-                   : launch_variant<VT, true, 0, false, false, true>(a, stream);
+        if (!a.use_ess) return launch_variant<VT, false, 0, false, false, true, VIEWS>(a, stream);
+        return lds ? launch_variant<VT, true, 0, true, false, true, VIEWS>(a, stream)
+                   : launch_variant<VT, true, 0, false, false, true, VIEWS>(a, stream);
     }
     if (a.use_ess) {
         if (lds) {
-            if (a.instr == 0) return xs ? launch_variant<VT, true, 0, true, true>(a, stream) : launch_variant<VT, true, 0, true, false>(a, stream);
-            if (a.instr == 1) return xs ? launch_variant<VT, true, 1, true, true>(a, stream) : launch_variant<VT, true, 1, true, false>(a, stream);
+            if (a.instr == 0) return xs ? launch_variant<VT, true, 0, true, true, false, VIEWS>(a, stream) : launch_variant<VT, true, 0, true, false, false, VIEWS>(a, stream);
+            if (a.instr == 1) return xs ? launch_variant<VT, true, 1, true, true, false, VIEWS>(a, stream) : launch_variant<VT, true, 1, true, false, false, VIEWS>(a, stream);
             return xs ? launch_variant<VT, true, 2, true, true>(a, stream) : launch_variant<VT, true, 2, true, false>(a, stream);
         }
-        if (a.instr == 0) return xs ? launch_variant<VT, true, 0, false, true>(a, stream) : launch_variant<VT, true, 0, false, false>(a, stream);
-        if (a.instr == 1) return xs ? launch_variant<VT, true, 1, false, true>(a, stream) : launch_variant<VT, true, 1, false, false>(a, stream);
+        if (a.instr == 0) return xs ? launch_variant<VT, true, 0, false, true, false, VIEWS>(a, stream) : launch_variant<VT, true, 0, false, false, false, VIEWS>(a, stream);
+        if (a.instr == 1) return xs ? launch_variant<VT, true, 1, false, true, false, VIEWS>(a, stream) : launch_variant<VT, true, 1, false, false, false, VIEWS>(a, stream);
         return xs ? launch_variant<VT, true, 2, false, true>(a, stream) : launch_variant<VT, true, 2, false, false>(a, stream);
     }
-    if (a.instr == 0) return xs ? launch_variant<VT, false, 0, false, true>(a, stream) : launch_variant<VT, false, 0, false, false>(a, stream);
-    if (a.instr == 1) return xs ? launch_variant<VT, false, 1, false, true>(a, stream) : launch_variant<VT, false, 1, false, false>(a, stream);
+    if (a.instr == 0) return xs ? launch_variant<VT, false, 0, false, true, false, VIEWS>(a, stream) : launch_variant<VT, false, 0, false, false, false, VIEWS>(a, stream);
+    if (a.instr == 1) return xs ? launch_variant<VT, false, 1, false, true, false, VIEWS>(a, stream) : launch_variant<VT, false, 1, false, false, false, VIEWS>(a, stream);
     return xs ? launch_variant<VT, false, 2, false, true>(a, stream) : launch_variant<VT, false, 2, false, false>(a, stream);
 }
 
@@ -2299,9 +2362,9 @@ hipError_t vr_launch_raycast(const RaycastLaunch &a, hipStream_t stream)
 {
     hipError_t e;
     switch (a.format) {
-    case VRHIP_UCHAR: e = launch_typed<uint8_t>(a, stream); break;
-    case VRHIP_USHORT: e = launch_typed<uint16_t>(a, stream); break;
-    case VRHIP_FLOAT: e = launch_typed<float>(a, stream); break;
+    case VRHIP_UCHAR: e = a.frame.cams ? launch_typed<uint8_t, true>(a, stream) : launch_typed<uint8_t, false>(a, stream); break;
+    case VRHIP_USHORT: e = a.frame.cams ? launch_typed<uint16_t, true>(a, stream) : launch_typed<uint16_t, false>(a, stream); break;
+    case VRHIP_FLOAT: e = a.frame.cams ? launch_typed<float, true>(a, stream) : launch_typed<float, false>(a, stream); break;
     default: return hipErrorInvalidValue;
     }
     if (e == hipSuccess && a.render.imgEss && a.hit_out && a.frame.n_wave_tiles) {

@@ -127,6 +127,7 @@ struct vrhip_renderer {
     uint32_t lds_stage = 0;           // VRHIP_LDS_STAGE=1|2: the LDS brick staging experiment (vr_raycast_staged_kernel)
     uint32_t march_micro = 0, march_fill = 0;   // VRHIP_MARCH_MICRO / VRHIP_MARCH_FILL (0 = built-in)
     uint32_t *seeds_dev = nullptr;    // kMaxBatchFrames jitter seeds of a batch of frames
+    vrhip_camera_params *cams_dev = nullptr;   // kMaxBatchFrames cameras of a batch of per-frame views
     bool sort_cont = true;            // VRHIP_NO_SORT=1 disables
     LiveTile *live = nullptr;         // DDA pre-pass output: patches with rays that sample
     bool prepass = true;              // VRHIP_NO_PREPASS=1 disables
@@ -955,7 +956,8 @@ int ensure_patch_classes(vrhip_renderer *r, RaycastLaunch *a)
     a->frame.patch_class = nullptr;
     a->frame.set_frames = r->queue_frames;
     const vrhip_rendering_params &rp = a->render;
-    if (!r->use_patch_classes || rp.technique != 0 || !a->use_ess || a->instr != 0 || !a->frame.live || !a->skip.near_bits ||
+    // (a batch of per-frame views runs without: classes hold for one camera -- DESIGN.md "Per-frame cameras")
+    if (!r->use_patch_classes || a->frame.cams || rp.technique != 0 || !a->use_ess || a->instr != 0 || !a->frame.live || !a->skip.near_bits ||
         rp.useGradient || a->frame.env || rp.showEss || rp.imgEss || rp.iteration != 0 || a->frame.lds_stage)
         return VRHIP_OK;
     const uint32_t n_patches = r->queue_n / r->queue_frames;
@@ -1032,6 +1034,7 @@ int launch_timed(vrhip_renderer *r, const RaycastLaunch &a)
     }
     std::memset(&r->last_info, 0, sizeof r->last_info);
     r->last_info.frames = b.frame.seeds ? r->queue_frames : 1u;
+    r->last_info.views = b.frame.cams ? 1u : 0u;
     b.info = &r->last_info;
     r->have_info = false;
     VR_HIP(r, vr_launch_frame(b, r->stream));
@@ -1426,6 +1429,7 @@ void vrhip_destroy(vrhip_renderer *r)
         if (p) (void)hipFree(p);
     if (r->env) (void)hipFree(r->env);
     if (r->seeds_dev) (void)hipFree(r->seeds_dev);
+    if (r->cams_dev) (void)hipFree(r->cams_dev);
     if (r->fp) (void)hipFree(r->fp);
     if (r->live) (void)hipFree(r->live);
     if (r->order) (void)hipFree(r->order);
@@ -1995,6 +1999,15 @@ int vrhip_render_batch(vrhip_renderer *r, uint32_t width, uint32_t height, uint3
                        const uint32_t *seeds, uint32_t n_frames, float *out_dev,
                        uint32_t out_frame_stride)
 {
+    return vrhip_render_batch_views(r, width, height, tile_w, tile_h, tile_ids, n_tiles, seeds, nullptr, n_frames,
+                                    out_dev, out_frame_stride);
+}
+
+int vrhip_render_batch_views(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t tile_w,
+                             uint32_t tile_h, const uint32_t *tile_ids, uint32_t n_tiles,
+                             const uint32_t *seeds, const vrhip_camera_params *cams, uint32_t n_frames,
+                             float *out_dev, uint32_t out_frame_stride)
+{
     if (!r) return VRHIP_ERR_INVALID;
     if (set_device(r)) return VRHIP_ERR_HIP;
     VR_REQUIRE(r, out_dev && seeds, VRHIP_ERR_INVALID, "vrhip_render_batch: NULL argument");
@@ -2009,6 +2022,9 @@ int vrhip_render_batch(vrhip_renderer *r, uint32_t width, uint32_t height, uint3
     VR_REQUIRE(r, rp.technique == 0 && rp.iteration == 0 && !rp.imgEss && !r->raycast.useAO,
                VRHIP_ERR_UNSUPPORTED,
                "vrhip_render_batch: ray caster only, iteration 0, no image-order ESS, no ambient occlusion");
+    // (the opt-in experiment kernels of the A/B builds take one camera per launch)
+    VR_REQUIRE(r, !cams || (!r->march && !r->lds_stage), VRHIP_ERR_UNSUPPORTED,
+               "vrhip_render_batch_views: per-frame cameras are not supported by the experiment kernels");
     const uint32_t packed = tile_ids ? n_tiles * tile_w * tile_h : width * height;
     VR_REQUIRE(r, out_frame_stride == 0 || out_frame_stride >= packed, VRHIP_ERR_INVALID,
                "vrhip_render_batch: frame stride smaller than a frame");
@@ -2020,10 +2036,17 @@ int vrhip_render_batch(vrhip_renderer *r, uint32_t width, uint32_t height, uint3
     if (!r->seeds_dev) VR_HIP(r, hipMalloc((void **)&r->seeds_dev, kMaxBatchFrames * sizeof(uint32_t)));
     VR_HIP(r, hipMemcpyAsync(r->seeds_dev, seeds, n_frames * sizeof(uint32_t), hipMemcpyHostToDevice,
                              r->stream));
+    if (cams) {
+        if (!r->cams_dev)
+            VR_HIP(r, hipMalloc((void **)&r->cams_dev, kMaxBatchFrames * sizeof(vrhip_camera_params)));
+        VR_HIP(r, hipMemcpyAsync(r->cams_dev, cams, n_frames * sizeof(vrhip_camera_params), hipMemcpyHostToDevice,
+                                 r->stream));
+    }
     RaycastLaunch a;
     fill_launch(r, width, height, tile_ids ? tile_w : width, &a);
     a.frame.out = (float4 *)out_dev;
     a.frame.seeds = r->seeds_dev;
+    a.frame.cams = cams ? r->cams_dev : nullptr;
     return launch_timed(r, a);
 }
 

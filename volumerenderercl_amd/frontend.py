@@ -272,3 +272,83 @@ def apply_cam_state(vr, state):
         vr.setAmbientOcclusion(state["useAO"])
     if state.get("showBox"):
         vr.setShowESS(True)
+
+
+# ---- camera paths recorded by the GUI, replayed headless (one frame per camera entry)
+
+def _f32(text):
+    """QString::toFloat: the recorded numbers are read back as floats."""
+    return float(np.float32(float(text)))
+
+
+def _split_entries(path):
+    with open(path) as f:
+        return [e.split() for e in f.read().split(";") if e.strip()]
+
+
+def read_view_record(prefix):
+    """recordViewConfig (volumerenderwidget.cpp:1030-1048): `<prefix>_quat.txt` holds `w x y z; ` and
+    `<prefix>_trans.txt` `x y z; ` per recorded view, appended to one line.  Returns the view matrices
+    (16 floats each, view_matrix), in recording order."""
+    quats, trans = _split_entries(prefix + "_quat.txt"), _split_entries(prefix + "_trans.txt")
+    if len(quats) != len(trans):
+        raise ValueError("view record %s: %d rotations but %d translations" % (prefix, len(quats), len(trans)))
+    views = []
+    for q, t in zip(quats, trans):
+        if len(q) != 4 or len(t) != 3:
+            raise ValueError("view record %s: malformed entry %r / %r" % (prefix, " ".join(q), " ".join(t)))
+        views.append(view_matrix(tuple(_f32(v) for v in q), tuple(_f32(v) for v in t)))
+    if not views:
+        raise ValueError("view record %s: no views" % prefix)
+    return views
+
+
+def read_interaction_log(path):
+    """Interaction log (toggleInteractionLogging / logInteraction, volumerenderwidget.cpp:313-358), parsed
+    as setSequenceStep (:364-408) does -- the payload follows the last `;`.  Returns the events in order:
+    ("camera", 16-float view matrix) for `<ms>; camera; w x y z, tx ty tz`, ("transferFunction", uint8
+    RGBA8 table), ("timestep", int).  `tffInterpolation` lines are parsed and dropped: the tables in the log
+    are already sampled.  A line of none of these kinds, or one whose payload does not parse, is an error."""
+    events = []
+    with open(path) as f:
+        lines = f.read().splitlines()
+    for n, line in enumerate(lines, 1):
+        if not line.strip():
+            continue
+        pos = line.rfind(";")
+        payload = line[pos + 2:] if pos >= 0 else ""
+        try:
+            if pos < 0:
+                raise ValueError("no ';'")
+            if "camera" in line:
+                v = [_f32(x) for x in payload.replace(",", "").split()]
+                if len(v) != 7:
+                    raise ValueError("a camera entry is 7 numbers")
+                events.append(("camera", view_matrix(tuple(v[:4]), tuple(v[4:]))))
+            elif "timestep" in line:
+                events.append(("timestep", int(payload.strip())))
+            elif "transferFunction" in line:
+                vals = [int(x) & 0xFF for x in payload.split()]
+                if not vals or len(vals) % 4:
+                    raise ValueError("a transfer function is RGBA8 entries")
+                events.append(("transferFunction", np.array(vals, dtype=np.uint8)))
+            elif "tffInterpolation" in line:
+                if payload.strip() not in ("linear", "quad", "cubic"):
+                    raise ValueError("unknown interpolation")
+            else:
+                raise ValueError("unknown event")
+        except ValueError as e:
+            raise ValueError("interaction log %s, line %d: %s" % (path, n, e))
+    if not any(k == "camera" for k, _ in events):
+        raise ValueError("interaction log %s: no camera entries" % path)
+    return events
+
+
+def orbit_views(axis, n, rotation=DEFAULT_ROTATION, translation=DEFAULT_TRANSLATION):
+    """A turntable: n views evenly spaced over 360 degrees about `axis`, each step composed onto the start
+    rotation the way the GUI's mouse rotation is (_rotQuat * step, volumerenderwidget.cpp:1115); the
+    translation stays."""
+    if int(n) < 1:
+        raise ValueError("orbit_views: n >= 1")
+    return [view_matrix(quat_mul(rotation, quat_from_axis_angle(axis, 360.0 * k / int(n))), translation)
+            for k in range(int(n))]

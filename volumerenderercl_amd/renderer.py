@@ -252,21 +252,36 @@ class VolumeRenderCL:
                                                  int(ids.size), C.c_void_p(out_dev_ptr)))
 
     def render_batch(self, width, height, seeds, out_dev_ptr, tile_w=0, tile_h=0, tile_ids=None,
-                     frame_stride=0):
+                     frame_stride=0, views=None):
         """len(seeds) <= 256 independent frames (frame f jittered by seeds[f]) in one set of
         launches (vrhip_render_batch): whole frames into out[f][height][width][4], or -- with
         tile_ids -- the tile subset into out[f][n_tiles][tile_h][tile_w][4] (device memory);
-        frame_stride: pixels between the frames of `out` when they are not packed."""
+        frame_stride: pixels between the frames of `out` when they are not packed.
+        views: one row-major 16-float view matrix per frame (as updateView takes it): frame f is
+        rendered from views[f] with the renderer's bbox and ortho setting (vrhip_render_batch_views);
+        None: every frame from the renderer's view."""
         if not self._vol_loaded:
             return
         self._rendering.iteration = 0
         self._push_params()
         sd = np.ascontiguousarray(seeds, dtype=np.uint32)
         ids = None if tile_ids is None else np.ascontiguousarray(tile_ids, dtype=np.uint32)
-        self._check(self._lib.vrhip_render_batch(
+        cams = None
+        if views is not None:
+            if len(views) != sd.size:
+                raise ValueError("render_batch: one view per frame (%d views, %d seeds)" % (len(views), sd.size))
+            cams = (CameraParams * max(1, sd.size))()
+            for f, v in enumerate(views):
+                m = [float(x) for x in np.asarray(v, dtype=np.float64).reshape(-1)]
+                if len(m) != 16:
+                    raise ValueError("render_batch: a view is 16 floats")
+                C.memmove(C.byref(cams[f]), C.byref(self._camera), C.sizeof(CameraParams))
+                cams[f].viewMat[:] = m
+        self._check(self._lib.vrhip_render_batch_views(
             self._h, int(width), int(height), int(tile_w), int(tile_h),
             None if ids is None else ids.ctypes.data_as(C.c_void_p), 0 if ids is None else int(ids.size),
-            sd.ctypes.data_as(C.c_void_p), int(sd.size), C.c_void_p(out_dev_ptr), int(frame_stride)))
+            sd.ctypes.data_as(C.c_void_p), None if cams is None else C.cast(cams, C.c_void_p), int(sd.size),
+            C.c_void_p(out_dev_ptr), int(frame_stride)))
 
     # ---- volume
     def loadVolumeData(self, props):

@@ -238,12 +238,16 @@ class TileDriver:
         self._after_render(streams, cur)    # the gather follows every renderer's frames
         self._start_gather(b, n)
 
-    def submit_frames(self, seeds):
+    def submit_frames(self, seeds, views=None):
         """len(seeds) <= batch independent frames (frame i jittered by seeds[i]) rendered in as few
         launch sets as there are renderers on this rank (VolumeRenderCL.render_batch: the rank's
-        tile share of several frames in one work queue), then ONE gather for all of them."""
+        tile share of several frames in one work queue), then ONE gather for all of them.
+        views: one 16-float view matrix per frame (frame i rendered from views[i]; the stand-in
+        renderer receives it as view=), or None: every frame from the renderer's view."""
         s = self.split
         n = len(seeds)
+        if views is not None and len(views) != n:
+            raise ValueError("submit_frames: one view per frame (%d views, %d seeds)" % (len(views), n))
         if not self.gathering:
             raise RuntimeError("submit/collect are for world > 1; use render_frame")
         if not 1 <= n <= self.batch:
@@ -257,7 +261,10 @@ class TileDriver:
         stride = s.cap * s.th * s.tw
         if self.render_tiles_fn is not None:      # stand-in renderer (CPU tests): frame by frame
             for i in range(n):
-                self.render_tiles_fn(s.my_tiles, self.local[b][i], seed=seeds[i])
+                if views is None:
+                    self.render_tiles_fn(s.my_tiles, self.local[b][i], seed=seeds[i])
+                else:
+                    self.render_tiles_fn(s.my_tiles, self.local[b][i], seed=seeds[i], view=views[i])
             lanes = []
         streams = [self._stream_of(r, ls) for r, ls in lanes]
         cur = self._before_render(streams)
@@ -266,7 +273,7 @@ class TileDriver:
             if lo >= hi:
                 break
             r.render_batch(s.W, s.H, seeds[lo:hi], self.local[b][lo].data_ptr(), s.tw, s.th,
-                           s.my_tiles, frame_stride=stride)
+                           s.my_tiles, frame_stride=stride, views=None if views is None else views[lo:hi])
         self._after_render(streams, cur)
         self._start_gather(b, n)
 
