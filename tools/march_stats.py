@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""tools/march_stats.py [WORKLOAD] -- round statistics of the march kernel from a -DVR_MARCH_STATS
-build (tools/mkvariant.sh mstats -DVR_MARCH_STATS; run on the GPU box): one frame, one renderer."""
+"""tools/march_stats.py [WORKLOAD] -- round statistics of phase 1 on the ray list and of the pre-pass from a
+-DVR_MARCH_STATS build (tools/mkvariant.sh mstats -DVR_MARCH_STATS; run on the GPU box): one frame, one renderer."""
 import ctypes as C
 import os
 import sys
@@ -31,13 +31,7 @@ for k in range(3):
     vr.setIteration(0)
     vr.runRaycast(1024, 1024)
     f(out, 1)
-names = ["rounds", "live lanes x rounds", "A iterations", "  with DDA step", "  lanes in DDA", "  with sample step",
-         "  lanes stepping", "samples queued", "B1 passes", "samples evaluated in vain", "opaque samples", "B2 passes"]
 v = list(out)
-for n, x in zip(names, v):
-    print("%-28s %12d" % (n, x))
-print("live lanes per round %.1f; DDA lanes per DDA exec %.1f; stepping lanes per exec %.1f; samples per B1 pass %.1f, per B2 pass %.1f" % (
-    v[1] / max(v[0], 1), v[4] / max(v[3], 1), v[6] / max(v[5], 1), v[7] / max(v[8], 1), v[10] / max(v[11], 1)))
 
 if any(v[16:]):
     names1 = ["rounds", "live lanes x rounds", "DDA step executions", "  lanes in them", "lookahead executions", "  lanes in them",

@@ -20,8 +20,7 @@ import sys
 from collections import defaultdict
 
 PASS = ("vr_dda_prepass_kernel", "vr_raycast_rays_kernel", "vr_raycast_kernel", "vr_raycast_split_kernel",
-        "vr_cont_hist_kernel", "vr_cont_scatter_kernel", "vr_march_kernel", "vr_pathtrace_kernel",
-        "vr_raycast_staged_kernel")
+        "vr_cont_hist_kernel", "vr_cont_scatter_kernel", "vr_pathtrace_kernel")
 
 
 def short(name):

@@ -8,7 +8,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# VRHIP_LIB_PATH selects an alternative build of the same library (A/B kernel experiments)
+# VRHIP_LIB_PATH selects an alternative build of the same library (tools/mkvariant.sh: -D variants for A/B runs)
 LIB_PATH = os.environ.get("VRHIP_LIB_PATH") or os.path.join(_HERE, "libvrhip.so")
 
 OK, ERR_INVALID, ERR_HIP, ERR_NODATA, ERR_UNSUPPORTED = range(5)

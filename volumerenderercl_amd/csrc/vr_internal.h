@@ -167,11 +167,10 @@ struct FrameView {
     // reached; live_count counts them) and phase 1 runs on that list, one lane per ray, lanes
     // refilled as rays end (vr_raycast_rays_kernel).  nullptr: the patch list above.
     ContRec *live_rays;
-    // 1: the default modes march the ray list with vr_march_kernel (stepping / dense evaluation /
-    // compositing as stages of a round) instead of the two-phase march; a schedule, not a result
-    uint32_t march;
-    uint32_t lds_stage;   // experiment (VRHIP_LDS_STAGE): 1 = patch kernel with LDS-staged voxel boxes, 2 = same without
-    uint32_t march_micro, march_fill;   // tuning (0 = built-in): micro-steps per round, queue fill that ends stage A
+    // Unused: FrameView and CellView are kernel arguments, and these words keep the offsets of the arguments behind
+    // them where they were.  The phase-1 kernel at three waves per SIMD, register-bound, is sensitive to them: with
+    // the arguments moved it spilled differently and the benchmark took 0.5 % longer.
+    uint32_t arg_pad[4];
     // Phase-2 scheduling: `cost` keeps, per pixel, the phase-2 rounds the pixel's ray needed in the
     // previous frame.  Suspended rays are sorted by it, longest first (counting sort into
     // `order`), so that the longest chains start first and the 16 rays of a group are alike.
@@ -197,11 +196,7 @@ constexpr uint32_t kSortBins = 256;
 // work items, so their appends meet at kLiveLists addresses instead of one (one counter: 193 us of a 20-frame set's
 // 580 us of pre-pass).  Phase 1 reads the lists interleaved, 64 rays from each in turn (vr_raycast_rays_kernel), which
 // keeps the queue's order: all lists grow at the same pace.  List k sits at live_rays + k * live_list_cap(items).
-#ifdef VR_EXPERIMENTS   // (the opt-in march kernel of the A/B builds reads one list)
-constexpr uint32_t kLiveLists = 1, kLiveStride = 32;
-#else
 constexpr uint32_t kLiveLists = 8, kLiveStride = 32;
-#endif
 constexpr uint32_t kLiveBase = 4 + 2 * kSortBins;        // first list counter, in control words
 // ... and the persistent kernels draw their work through kDrawCounters counters instead of one (FrameView::draw_count, a
 // cache line each): counter k hands out the work units G + kDrawCounters j + k behind the G units the waves own by
@@ -240,12 +235,8 @@ struct CellView {
     int shift;
     int ecx, ecy, ecz;
     int eshift;
-    // The empty bits once more, per ESS brick (the march kernel keeps the words of the bricks a ray
-    // is in in registers): brick (bx, by, bz) of the bw x bh x bd brick grid, x fastest, is cut into
-    // 4 x 4 x 4 sub-blocks of (edge / 4) voxels; bit i + 4 j + 16 k of its word is set when every
-    // cell that overlaps sub-block (i, j, k) is empty.  nullptr: not available (brick edge < 4).
-    const unsigned long long *bmask;
-    int bex, bey, bez;      // log2 of the brick edge per axis (>= 2)
+    const void *arg_pad0;   // unused (see FrameView::arg_pad)
+    int arg_pad1[3];
     // The bounds once more, per macro cell of 4 x 4 x 4 cells (kLeapShift): the maximum of its cells' bounds -- what
     // lets a tracking walk leap over all its steps inside a macro cell at once (vr_pathtrace.hip).  ccx * ccy * ccz
     // floats, x fastest; nullptr = no leaps.
@@ -313,8 +304,6 @@ hipError_t vr_launch_raycast(const RaycastLaunch &a, hipStream_t stream);
 // p of frame 0); the launch's camera, parameters, skip bitmaps and queue must be those of the frames to come
 hipError_t vr_launch_patch_classes(const RaycastLaunch &a, uint32_t n_patches, uint32_t set_frames, uint8_t *cls,
                                    hipStream_t stream);
-// 1 when vr_raycast.hip was built with the opt-in experiment kernels (-DVR_EXPERIMENTS: A/B builds only)
-int vr_experiments_built();
 // fills the footprint volume vol.fp of `vol`: (w+1)(h+1)(d+1) entries rounded up to
 // whole micro-bricks, 8 values of the volume's type each; vr_bricks.hip
 hipError_t vr_launch_build_footprint(const VolView &vol, int format, hipStream_t stream);
@@ -346,9 +335,6 @@ constexpr int kLeapLevels = 7, kLeapRadius = 15;
 // alternate between); returns in *result the buffer that holds the table at the end
 hipError_t vr_launch_cell_leap_radius(const CellView &grid, const float *cbound, uint8_t *dist, const uint8_t **result,
                                       hipStream_t stream);
-// CellView::bmask from CellView::empty for the bw x bh x bd brick grid (grid.bex.. set)
-hipError_t vr_launch_cell_bmask(const VolView &vol, const CellView &grid, int bw, int bh, int bd,
-                                unsigned long long *bmask, hipStream_t stream);
 // the frame launch for a.render.technique
 inline hipError_t vr_launch_frame(const RaycastLaunch &a, hipStream_t stream)
 {

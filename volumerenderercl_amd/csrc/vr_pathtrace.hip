@@ -499,11 +499,7 @@ __global__ __launch_bounds__(kBlockDim) VR_PT_OCC void vr_pathtrace_kernel(
                     px.hit_pos = px.apos;
                     const f3 sp = mk3(px.apos.x * 0.5f + 0.5f, px.apos.y * 0.5f + 0.5f,
                                       px.apos.z * 0.5f + 0.5f);
-#ifdef VR_DIAG_NO_GRAD   // diagnostic build (wrong image): what do the gradient neighbourhoods of the interactions cost?
-                    const float4 gq = make_float4(sp.x, sp.y, sp.z, 0.f);
-#else
                     const float4 gq = gradient_tff<VT, VI>(vol, s_tff, tffn, sp);
-#endif
                     const float g0 = -gq.x, g1 = -gq.y, g2 = -gq.z, g3 = -gq.w;
                     const float glen = sqrtf((((g0 * g0) + (g1 * g1)) + (g2 * g2)) + (g3 * g3));
                     if (glen > 0.5f) {   // :483-486 high gradient: Phong

@@ -34,22 +34,12 @@
 
 #include "vr_sampling.h"
 
-// A/B builds (tools/mkvariant.sh NAME -DVR_EXPERIMENTS [-DVR_LEAP_STEPPING]) add the kernels that lost their
-// A/B in round 2 -- vr_march_kernel (decoupled march), vr_raycast_staged_kernel (LDS brick staging), leap
-// stepping inside the two-phase kernels -- from vr_experiments_*.inc; the product library has none of them.
-#if defined(VR_EXPERIMENTS) && defined(VR_LEAP_STEPPING)
-#define VR_LEAP 1
-#endif
-#ifdef VR_EXPERIMENTS
-#include "vr_leap.h"
-#endif
-
 namespace {
 
 constexpr int kSplit = 4;            // lanes per ray in phase 2 (x kBatch samples per lane)
 
 #ifdef VR_MARCH_STATS   // diagnostic build: what the waves of the marching kernels spend their rounds on
-__device__ unsigned long long g_march_stats[32];   // [0, 16) march kernel, [16, 32) phase 1 on the ray list
+__device__ unsigned long long g_march_stats[32];   // [16, 26) phase 1 on the ray list, [28, 32) pre-pass; [0, 16) unused
 #define VR_MS(i, v) ms_acc[i] += (unsigned long long)(v)
 #else
 #define VR_MS(i, v)
@@ -768,10 +758,6 @@ VR_DEV bool lookahead_pays(bool sampling, bool guess_empty)
     return n_g > 0 && VR_LOOK_NUM * n_g >= n_s;
 }
 
-#ifdef VR_EXPERIMENTS   // exact O(1) leaps over empty runs: opt-in experiments only (vr_experiments_leap.inc)
-#include "vr_experiments_leap.inc"
-#endif
-
 // One front-to-back compositing step (:865-879) with the sample's colour*opacity (q0..q2),
 // opacity qo and ray parameter ti.
 VR_DEV void composite(const RayCtx &c, RayDyn &d, float q0, float q1, float q2, float qo, float ti)
@@ -951,10 +937,10 @@ VR_DEV void write_pixel(const FrameView &fr, const vrhip_rendering_params &rp, c
         fr.hit_any[(size_t)(gy >> 3) * fr.hit_w + (gx >> 3)] = 1;
 }
 
-template <typename VT, int INSTR, bool FP, bool LS = false>
-VR_DEV Vol<VT, INSTR, FP, LS> make_vol(const VolView &vv, uint32_t *touched)
+template <typename VT, int INSTR, bool FP>
+VR_DEV Vol<VT, INSTR, FP> make_vol(const VolView &vv, uint32_t *touched)
 {
-    Vol<VT, INSTR, FP, LS> vol;
+    Vol<VT, INSTR, FP> vol;
     vol.p = (const VT *)vv.data;
     vol.w1 = vv.w - 1; vol.h1 = vv.h - 1; vol.d1 = vv.d - 1;
     vol.fw = vv.fw; vol.fh = vv.fh; vol.fd = vv.fd;
@@ -1226,13 +1212,9 @@ __global__ __launch_bounds__(kBlockDim) void vr_dda_prepass_kernel(
             // (list q % kLiveLists: vr_internal.h)
             const uint32_t list = q % kLiveLists;
             uint32_t base = 0;
-#ifdef VR_DIAG_NO_LIVE_ATOMIC   // diagnostic build (WRONG frames: the lists are not compact and their counts stay 0, so the
-            base = (q / kLiveLists) * 64u;   // marching kernels leave at once): what does the pre-pass cost without its counters?
-#else
             if (lane == (uint32_t)__builtin_ctzll(m))
                 base = atomicAdd(fr.live_list_count + list * kLiveStride, (uint32_t)__builtin_popcountll(m));
             base = __shfl(base, __builtin_ctzll(m), 64);
-#endif
             base += list * live_list_cap(fr.n_wave_tiles);
             if (live) {
                 ContRec r;
@@ -1312,10 +1294,6 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_rays_kernel(
     const Grid grid = make_grid(bricks, rc, skip.n_words, true);
     const uint32_t *sb = SKIP_LDS ? s_skip : skip.bits;
     const bool skip_empty = cells.empty != nullptr && rp.useLinear != 0;
-#ifdef VR_LEAP   // A/B build (VR_EXPERIMENTS + VR_LEAP_STEPPING); VRHIP_MARCH_MICRO = leap steps per round
-    const bool use_mask = skip_empty && cells.bmask != nullptr && fr.march_micro != 0;
-    const uint32_t leap_iters = fr.march_micro;
-#endif
     const uint32_t budget = fr.round_budget ? fr.round_budget : 0xffffffffu;
     const uint32_t kRefillLanes = (fr.refill_min ? fr.refill_min : 16u) * 4u;   // idle lanes before a refill
 
@@ -1324,10 +1302,6 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_rays_kernel(
     uint32_t gx = 0, gy = 0, out_index = 0, my_rounds = 0, frame_idx = 0;
     bool guess_empty = true;
     uint32_t cool = 0;   // evaluation batches before the ray guesses "empty" again (see the lookahead below)
-#ifdef VR_LEAP
-    LeapCache lc;
-    lc.key0 = lc.key1 = 0xffffffffu; lc.m0 = lc.m1 = 0ull; lc.du = lc.dv = lc.ds = lc.inv_step = 0.f;
-#endif
 #ifdef VR_MARCH_STATS
     unsigned long long ms_acc[16] = {0};
 #endif
@@ -1389,9 +1363,6 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_rays_kernel(
                             my_rounds = 0;
                             guess_empty = true;
                             cool = 0;
-#ifdef VR_LEAP
-                            leap_reset(lc, c, vol.fw, vol.fh, vol.fd);
-#endif
                         }
                     }
                 }
@@ -1443,20 +1414,6 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_rays_kernel(
         VR_MARK("R_look");
         if (__ballot(d.state == S_SAMPLE)) my_rounds += d.state == S_SAMPLE ? 1u : 0u;
         bool more_empty = false;
-#ifdef VR_LEAP
-        if (use_mask) {
-            // steps over runs of empty samples (leap_step) until the ray stands at a sample to evaluate;
-            // rays that leave their segment go on with the DDA in the same pass
-            bool ready = false;
-            for (uint32_t it = 0; it < leap_iters; ++it) {
-                const bool act = d.state == S_SAMPLE && !ready;
-                if (!__ballot(act)) break;
-                if (act) ready = leap_step<true>(cells, vol, grid, c, d, lc, false, n0);
-                if (__ballot(d.state == S_BRICK)) dda_step<0>(sb, grid, c, d, n0, n1);
-            }
-            more_empty = !ready;
-        } else
-#endif
         if (skip_empty && lookahead_pays(d.state == S_SAMPLE, guess_empty)) {
             VR_MS(4, 1);                                                       // lookahead executions
             VR_MS(5, __builtin_popcountll(__ballot(d.state == S_SAMPLE)));     // lanes in them
@@ -1762,14 +1719,6 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_split_kernel(
     const uint32_t *sb = SKIP_LDS ? s_skip : skip.bits;
     const bool skip_empty = INSTR != 2 && cells.empty != nullptr && rp.useLinear != 0 &&
                             !(XS && rp.illumType == 4);
-#ifdef VR_LEAP   // A/B build (VR_EXPERIMENTS + VR_LEAP_STEPPING); VRHIP_MARCH_MICRO = leap steps per round
-    const bool use_mask = skip_empty && cells.bmask != nullptr && fr.march_micro != 0;
-    const uint32_t leap_iters = fr.march_micro;
-#endif
-#ifdef VR_LEAP
-    LeapCache lc;
-    lc.key0 = lc.key1 = 0xffffffffu; lc.m0 = lc.m1 = 0ull; lc.du = lc.dv = lc.ds = lc.inv_step = 0.f;
-#endif
     // Rays are handed out one by one from the sorted list: when `refill_min` ray slots (quads) of
     // the wave are idle they retire their rays and take the next ones (their set-up runs
     // together).  With the default, 16, a wave refills when all its rays are done, but draws as
@@ -1853,9 +1802,6 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_split_kernel(
                             my_rounds = 0;
                             guess_empty = true;
                             cool = 0;
-#ifdef VR_LEAP
-                            leap_reset(lc, c, vol.fw, vol.fh, vol.fd);
-#endif
                         }
                     }
                 }
@@ -1872,14 +1818,6 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_split_kernel(
                     if (!__ballot(d.state == S_BRICK)) break;
                     if (it >= kMaxBrickSteps && __ballot(d.state == S_SAMPLE)) break;
                     VR_COUNT(9);
-#ifdef VR_DDA_TWICE   // diagnostic build: what does a phase-2 DDA step cost?
-                    {
-                        RayDyn d2 = d;
-                        dda_step<0>(sb, grid, c, d2, dummy0, dummy1);
-                        asm volatile("" ::"v"(d2.t), "v"(d2.state), "v"(d2.skw), "v"(d2.tv0), "v"(d2.tv1),
-                                     "v"(d2.tv2), "v"(d2.c0), "v"(d2.c1), "v"(d2.c2), "v"(d2.t_exit));
-                    }
-#endif
                     if (count) dda_step<INSTR>(sb, grid, c, d, c_bricks, c_skipped);
                     else dda_step<0>(sb, grid, c, d, dummy0, dummy1);
                 }
@@ -1888,38 +1826,13 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_split_kernel(
             if (!__ballot(d.state != S_DONE)) continue;
             VR_COUNT(10);
             my_rounds += d.state != S_DONE ? 1u : 0u;
-#ifdef VR_CAP_ROUNDS   // diagnostic build (wrong image): is phase 2 bound by its longest rays?
-            if (my_rounds >= VR_CAP_ROUNDS) d.state = S_DONE;
-#endif
             bool more_empty = false;
-#ifdef VR_LEAP
-            if (use_mask) {
-                // (the four lanes of a ray hold the same state and cache and take the same steps)
-                bool ready = false;
-                for (uint32_t it = 0; it < leap_iters; ++it) {
-                    const bool act = d.state == S_SAMPLE && !ready;
-                    if (!__ballot(act)) break;
-                    if (act) ready = leap_step<ESS>(cells, vol, grid, c, d, lc, count, c_taken);
-                    if (ESS && __ballot(d.state == S_BRICK)) {
-                        if (count) dda_step<INSTR>(sb, grid, c, d, c_bricks, c_skipped);
-                        else dda_step<0>(sb, grid, c, d, dummy0, dummy1);
-                    }
-                }
-                more_empty = !ready;
-            } else
-#endif
             if (skip_empty && lookahead_pays(d.state == S_SAMPLE, guess_empty)) {
                 if (d.state == S_SAMPLE) {
                     // the four lanes of a ray hold the same state and take the same decisions;
                     // lane `slot` looks at samples [kLook2 * slot, kLook2 * (slot + 1)) of the run
                     // (its window start is approximate, which is all the cell lookup needs)
                     const float t_win = d.t + (float)(kLook2 * (int)slot) * c.stepSize;
-#ifdef VR_TWICE_LOOK   // diagnostic build: sensitivity to the lookahead's cost
-                    {
-                        const int em2 = (int)empty_mask<VT, INSTR, kLook2>(cells, vol, c, t_win + 1e-7f);
-                        asm volatile("" ::"v"(em2));
-                    }
-#endif
                     const int em = (int)empty_mask<VT, INSTR, kLook2>(cells, vol, c, t_win);
                     const uint32_t m4[4] = {(uint32_t)quad_bcast<0>(em), (uint32_t)quad_bcast<1>(em),
                                             (uint32_t)quad_bcast<2>(em), (uint32_t)quad_bcast<3>(em)};
@@ -1996,35 +1909,12 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_split_kernel(
                 }
                 float p0[kBatch], p1[kBatch], p2[kBatch], opk[kBatch];
                 bool litk[kBatch];
-#ifdef VR_TWICE_EVAL   // diagnostic build: sensitivity of the frame time to the evaluation's cost
-                {
-                    float tk2[kBatch];
-#pragma unroll
-                    for (int k = 0; k < kBatch; ++k) tk2[k] = tk[k] + 1e-7f;
-                    eval_batch<VT, INSTR, XS, FP>(vol, s_tff, tffn, s_stage, c, rp, rc, refInterval, tk2, vk, p0, p1,
-                                          p2, opk, litk);
-                    asm volatile("" ::"v"(p0[0]), "v"(p0[1]), "v"(p0[2]), "v"(p0[3]), "v"(p1[0]), "v"(p1[1]),
-                                 "v"(p1[2]), "v"(p1[3]), "v"(p2[0]), "v"(p2[1]), "v"(p2[2]), "v"(p2[3]),
-                                 "v"(opk[0]), "v"(opk[1]), "v"(opk[2]), "v"(opk[3]));
-                }
-#endif
                 eval_batch<VT, INSTR, XS, FP>(vol, s_tff, tffn, s_stage, c, rp, rc, refInterval, tk, vk, p0, p1, p2,
                                       opk, litk);
                 VR_STAMP(3);
                 int fl[kBatch];
 #pragma unroll
                 for (int k = 0; k < kBatch; ++k) fl[k] = (vk[k] ? 1 : 0) | (litk[k] ? 2 : 0);
-#ifdef VR_TWICE_COMP   // diagnostic build: sensitivity to the compositing replay's cost
-                {
-                    RayDyn d2 = d;
-                    unsigned long long z0 = 0, z1 = 0;
-                    composite_from<0>(c, d2, p0, p1, p2, opk, tk, fl, false, z0, z1);
-                    composite_from<1>(c, d2, p0, p1, p2, opk, tk, fl, false, z0, z1);
-                    composite_from<2>(c, d2, p0, p1, p2, opk, tk, fl, false, z0, z1);
-                    composite_from<3>(c, d2, p0, p1, p2, opk, tk, fl, false, z0, z1);
-                    asm volatile("" ::"v"(d2.t), "v"(d2.state), "v"(d2.alpha), "v"(d2.r0), "v"(d2.r1), "v"(d2.r2));
-                }
-#endif
                 composite_from<0>(c, d, p0, p1, p2, opk, tk, fl, count, c_taken, c_shaded);
                 composite_from<1>(c, d, p0, p1, p2, opk, tk, fl, count, c_taken, c_shaded);
                 composite_from<2>(c, d, p0, p1, p2, opk, tk, fl, count, c_taken, c_shaded);
@@ -2140,11 +2030,6 @@ inline size_t march_lds(int waves, const RaycastLaunch &a, bool skip_lds)
 // does a workgroup of kWavesWide waves with the skip bitmap fit a CU's LDS?
 inline bool wide_fits_lds(const RaycastLaunch &a) { return march_lds(kWavesWide, a, true) <= (size_t)160 * 1024; }
 
-#ifdef VR_EXPERIMENTS   // vr_march_kernel, vr_raycast_staged_kernel and their launchers: A/B builds only
-#include "vr_experiments_kernels.inc"
-#endif
-
-
 // VIEWS: the kernels that take frame f's camera from FrameView::cams (a batch of per-frame views) instead of the
 // launch's; the VIEWS = false instantiations are the ones every other launch runs, unchanged by the option.
 template <typename VT, bool ESS, int INSTR, bool SKIP_LDS, bool XS, bool FP = false, bool VIEWS = false>
@@ -2217,14 +2102,6 @@ hipError_t launch_variant(const RaycastLaunch &a, hipStream_t stream)
     const bool bind_stop = a.bind_events && a.stop_event && a.stop_bound && !resolve_follows;
     const bool p1_last = a.frame.round_budget == 0;
     const hipEvent_t p1_ev = !a.bind_events ? nullptr : (p1_last && bind_stop) ? a.stop_event : a.mid_event;
-#ifdef VR_EXPERIMENTS
-    if (VIEWS && frame.march) return hipErrorNotSupported;   // (the experiment kernels take one camera per launch)
-    if (ESS && INSTR == 0 && !XS && frame.live && frame.live_rays && frame.march && !a.raycast.contours &&
-        !a.raycast.aerial) {
-        if (start_ev && hipEventRecord(start_ev, stream) == hipSuccess) *a.start_bound = true;
-        return launch_march<VT, SKIP_LDS, FP>(a, frame, block, cus, stream);   // the whole frame in one launch
-    }
-#endif
     if (ESS && INSTR == 0 && !XS && frame.live && frame.live_rays) {   // phase 1 on the ray list
         // phase 1 picks its own schedule: two or three waves per SIMD (three: footprint volume only), the skip
         // bitmap in LDS whenever it fits
@@ -2283,14 +2160,6 @@ hipError_t launch_typed(const RaycastLaunch &a, hipStream_t stream)
     const bool xs = a.render.illumType >= 2 || a.raycast.useAO != 0 || a.render.showEss != 0 ||
                     a.render.imgEss != 0 || a.vol.channels > 1 || a.raycast.contours != 0 ||
                     a.raycast.aerial != 0 || a.render.useLinear == 0;
-#ifdef VR_EXPERIMENTS
-    if (VIEWS && a.frame.lds_stage) return hipErrorNotSupported;
-    if (a.frame.lds_stage && !xs && a.instr == 0 && a.use_ess && sizeof(VT) == 1 && !a.raycast.contours &&
-        !a.raycast.aerial && a.frame.n_wave_tiles) {
-        if (a.bind_events && a.start_bound && hipEventRecord(a.start_event, stream) == hipSuccess) *a.start_bound = true;
-        return launch_staged(a, stream);
-    }
-#endif
     // the traffic pass (instr 2: vrhip_count_touched) renders one camera
     if (VIEWS && a.instr >= 2) return hipErrorNotSupported;
     // the default kernels read the footprint volume when the host has provided one for this frame
@@ -2317,7 +2186,7 @@ hipError_t launch_typed(const RaycastLaunch &a, hipStream_t stream)
 } // namespace
 
 #ifdef VR_MARCH_STATS
-// diagnostic builds only: read (and optionally clear) the march kernel's round statistics
+// diagnostic builds only: read (and optionally clear) the round statistics of phase 1 and the pre-pass
 extern "C" int vrhip_debug_march_stats(unsigned long long out[32], int reset)
 {
     if (hipDeviceSynchronize() != hipSuccess) return -1;
@@ -2466,14 +2335,4 @@ hipError_t vr_launch_patch_classes(const RaycastLaunch &a, uint32_t n_patches, u
     hipLaunchKernelGGL(vr_patch_class_kernel, dim3((n_patches + 3u) / 4u), dim3(kBlockDim), 0, stream, a.skip, a.frame,
                        a.cam, a.render, hg, n_patches, set_frames, cls);
     return hipGetLastError();
-}
-
-// 1 when this library was built with the opt-in experiment kernels (VRHIP_MARCH, VRHIP_LDS_STAGE, VRHIP_MARCH_MICRO)
-int vr_experiments_built()
-{
-#ifdef VR_EXPERIMENTS
-    return 1;
-#else
-    return 0;
-#endif
 }

@@ -70,9 +70,7 @@ struct vrhip_renderer {
 
     // cell grid of the current timestep + TF (CellView, vr_internal.h): opacity bound for the
     // path tracer, empty bits for the ray caster
-    CellView cells = {nullptr, nullptr, 0, 0, 0, 3, 0, 0, 0, 3, nullptr, 0, 0, 0};
-    unsigned long long *cell_bmask = nullptr;   // CellView::bmask (per ESS brick)
-    size_t bmask_cap = 0;
+    CellView cells = {nullptr, nullptr, 0, 0, 0, 3, 0, 0, 0, 3};
     float *cell_bound = nullptr;
     uint32_t *cell_empty = nullptr;
     float *cell_sparse = nullptr;  // 13 x 4096 floats of scratch for the TF range-max table
@@ -123,9 +121,6 @@ struct vrhip_renderer {
     uint32_t *order = nullptr;        // sorted permutation of the suspended rays
     ContRec *live_rays = nullptr;     // pre-pass output: live rays with their DDA state (phase 1's list)
     bool ray_list = true;             // VRHIP_NO_RAYLIST=1: phase 1 walks the live patches instead
-    bool march = false;               // VRHIP_MARCH=1: vr_march_kernel instead of the two-phase march (measured, not faster)
-    uint32_t lds_stage = 0;           // VRHIP_LDS_STAGE=1|2: the LDS brick staging experiment (vr_raycast_staged_kernel)
-    uint32_t march_micro = 0, march_fill = 0;   // VRHIP_MARCH_MICRO / VRHIP_MARCH_FILL (0 = built-in)
     uint32_t *seeds_dev = nullptr;    // kMaxBatchFrames jitter seeds of a batch of frames
     vrhip_camera_params *cams_dev = nullptr;   // kMaxBatchFrames cameras of a batch of per-frame views
     bool sort_cont = true;            // VRHIP_NO_SORT=1 disables
@@ -514,7 +509,7 @@ int ensure_footprint(vrhip_renderer *r)
 {
     r->fp_active = false;
     const vrhip_rendering_params &rp = r->render;
-    if (!r->use_fp || r->lds_stage || r->channels > 1 || r->stats_enabled || rp.technique != 0 || rp.illumType >= 2 ||
+    if (!r->use_fp || r->channels > 1 || r->stats_enabled || rp.technique != 0 || rp.illumType >= 2 ||
         r->raycast.useAO || rp.showEss || rp.imgEss)
         return VRHIP_OK;   // (the launcher uses it in the default kernels only)
     const VolView v = make_vol_view(r, r->vols[r->timestep].dev);
@@ -733,37 +728,8 @@ int ensure_cells(vrhip_renderer *r, bool need_bound, bool need_empty)
                                         make_tf_view(r), r->cell_sparse, nullptr, r->cell_empty, r->stream));
         r->cells_have_empty = true;
         g.empty = r->cell_empty;
-        // the empty bits per ESS brick, for the march kernel (ESS bricks of >= 4 voxels per axis); only
-        // the opt-in kernels read them (VRHIP_MARCH, leap stepping), so the default path does not pay the
-        // 0.2 ms per transfer-function change
-        g.bmask = nullptr;
-        g.bex = g.bey = g.bez = 0;
-        if (r->bricks_valid && (r->march || r->march_micro)) {
-            int lg[3];
-            bool ok = true;
-            for (int i = 0; i < 3; ++i) {
-                lg[i] = 0;
-                while ((1u << lg[i]) < r->brick_edge[i]) ++lg[i];
-                ok = ok && lg[i] >= 2 && r->brick_tex[i] <= 256u;
-            }
-            if (ok) {
-                const size_t nb = (size_t)r->brick_tex[0] * r->brick_tex[1] * r->brick_tex[2];
-                if (nb > r->bmask_cap) {
-                    VR_HIP(r, hipStreamSynchronize(r->stream));
-                    if (r->cell_bmask) VR_HIP(r, hipFree(r->cell_bmask));
-                    r->cell_bmask = nullptr;
-                    r->bmask_cap = 0;
-                    VR_HIP(r, hipMalloc((void **)&r->cell_bmask, nb * sizeof(unsigned long long)));
-                    r->bmask_cap = nb;
-                }
-                g.bex = lg[0]; g.bey = lg[1]; g.bez = lg[2];
-                VR_HIP(r, vr_launch_cell_bmask(make_vol_view(r, s.dev), g, (int)r->brick_tex[0], (int)r->brick_tex[1],
-                                               (int)r->brick_tex[2], r->cell_bmask, r->stream));
-                g.bmask = r->cell_bmask;
-            }
-        }
     }
-    if (!r->cells_have_empty) { g.empty = nullptr; g.bmask = nullptr; }
+    if (!r->cells_have_empty) g.empty = nullptr;
     r->cells = g;
     return VRHIP_OK;
 }
@@ -896,10 +862,6 @@ void fill_launch(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t ou
     a->frame.refill_min = r->refill_min;
     a->frame.live = r->prepass ? r->live : nullptr;
     a->frame.live_rays = (r->prepass && r->ray_list) ? r->live_rays : nullptr;
-    a->frame.march = r->march ? 1u : 0u;
-    a->frame.lds_stage = r->lds_stage;
-    a->frame.march_micro = r->march_micro;
-    a->frame.march_fill = r->march_fill;
     a->frame.live_count = ctrl + 3;
     a->frame.live_list_count = ctrl + kLiveBase;
     a->frame.draw_count = ctrl + kDrawBase;
@@ -927,7 +889,7 @@ void fill_launch(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t ou
     a->cells = r->cells;
     if (!r->pt_cull) { a->cells.bound = a->cells.cbound = nullptr; a->cells.cdist = nullptr; }
     // the empty bits are those of TF(channel 0): not what a CL_RG / CL_RGBA sample's opacity is
-    if (!ray_skip_empty(r)) { a->cells.empty = nullptr; a->cells.bmask = nullptr; }
+    if (!ray_skip_empty(r)) a->cells.empty = nullptr;
     a->format = r->format;
     a->use_ess = r->use_ess ? 1 : 0;
     a->instr = r->stats_enabled ? 1 : 0;
@@ -958,7 +920,7 @@ int ensure_patch_classes(vrhip_renderer *r, RaycastLaunch *a)
     const vrhip_rendering_params &rp = a->render;
     // (a batch of per-frame views runs without: classes hold for one camera -- DESIGN.md "Per-frame cameras")
     if (!r->use_patch_classes || a->frame.cams || rp.technique != 0 || !a->use_ess || a->instr != 0 || !a->frame.live || !a->skip.near_bits ||
-        rp.useGradient || a->frame.env || rp.showEss || rp.imgEss || rp.iteration != 0 || a->frame.lds_stage)
+        rp.useGradient || a->frame.env || rp.showEss || rp.imgEss || rp.iteration != 0)
         return VRHIP_OK;
     const uint32_t n_patches = r->queue_n / r->queue_frames;
     std::vector<uint8_t> key;
@@ -1012,7 +974,7 @@ int launch_timed(vrhip_renderer *r, const RaycastLaunch &a)
     // The frame's events are bound to its launches (hipExtLaunchKernelGGL: the first launch's start, phase 1's end, the
     // last launch's end) -- a RECORDED event is a marker packet of its own between two launches, ~6 us of GPU time
     // each; VRHIP_EVENT_BIND=0 records them (A/B), =1 binds the ends only.  What the launchers did not bind -- no
-    // launch at all, an experiment's launcher -- is recorded here.
+    // launch at all -- is recorded here.
     bool start_bound = false, stop_bound = false;
     b.bind_events = r->event_bind;
     if (r->frame_timing) {
@@ -1361,25 +1323,20 @@ int vrhip_create(int device_id, vrhip_renderer **out)
         return fail(nullptr, VRHIP_ERR_HIP, msg);
     }
     r->stream = r->own_stream;
-    // the opt-in experiment kernels exist in A/B builds only (tools/mkvariant.sh NAME -DVR_EXPERIMENTS): asking
-    // the product library for them fails loudly instead of silently rendering with the default kernels
-    if (!vr_experiments_built() && (getenv("VRHIP_MARCH") || getenv("VRHIP_LDS_STAGE") || getenv("VRHIP_MARCH_MICRO"))) {
+    // the switches of the removed experiment kernels fail loudly instead of silently rendering with the default ones
+    if (getenv("VRHIP_MARCH") || getenv("VRHIP_LDS_STAGE") || getenv("VRHIP_MARCH_MICRO")) {
         vrhip_destroy(r);
         return fail(nullptr, VRHIP_ERR_UNSUPPORTED,
-                    "VRHIP_MARCH / VRHIP_LDS_STAGE / VRHIP_MARCH_MICRO need a library built with -DVR_EXPERIMENTS "
-                    "(tools/mkvariant.sh experiments -DVR_EXPERIMENTS; VRHIP_LIB_PATH selects it)");
+                    "VRHIP_MARCH / VRHIP_LDS_STAGE / VRHIP_MARCH_MICRO: the VR_EXPERIMENTS kernels were removed "
+                    "(commit 858be18 holds them)");
     }
     if (const char *b = getenv("VRHIP_ROUND_BUDGET")) r->round_budget = (uint32_t)atoi(b);   // tuning
     if (getenv("VRHIP_NO_PREPASS")) r->prepass = false;        // experiments: phase 1 walks every patch
     if (getenv("VRHIP_NO_RAYLIST")) r->ray_list = false;       // experiments: phase 1 on live patches
-    if (getenv("VRHIP_MARCH")) r->march = true;                // experiments / A-B: the decoupled march kernel
-    if (const char *e = getenv("VRHIP_LDS_STAGE")) r->lds_stage = (uint32_t)atoi(e);
     if (const char *e = getenv("VRHIP_CULL_RADIUS")) {
         const int v = atoi(e);
         if (v >= 0 && v <= 64) r->cull_radius = (uint32_t)v;
     }
-    if (const char *e = getenv("VRHIP_MARCH_MICRO")) r->march_micro = (uint32_t)atoi(e);
-    if (const char *e = getenv("VRHIP_MARCH_FILL")) r->march_fill = (uint32_t)atoi(e);
     if (getenv("VRHIP_NO_SORT")) r->sort_cont = false;         // experiments: phase 2 in append order
     if (getenv("VRHIP_NO_PATCH_CLASS")) r->use_patch_classes = false;   // A/B: every patch sets up its rays
     auto occ_env = [](const char *name, int dflt) {
@@ -1442,7 +1399,6 @@ void vrhip_destroy(vrhip_renderer *r)
     if (r->cell_dist) (void)hipFree(r->cell_dist);
     if (r->cell_empty) (void)hipFree(r->cell_empty);
     if (r->cell_sparse) (void)hipFree(r->cell_sparse);
-    if (r->cell_bmask) (void)hipFree(r->cell_bmask);
     if (r->ev0) (void)hipEventDestroy(r->ev0);
     if (r->ev1) (void)hipEventDestroy(r->ev1);
     if (r->evm) (void)hipEventDestroy(r->evm);
@@ -2022,9 +1978,6 @@ int vrhip_render_batch_views(vrhip_renderer *r, uint32_t width, uint32_t height,
     VR_REQUIRE(r, rp.technique == 0 && rp.iteration == 0 && !rp.imgEss && !r->raycast.useAO,
                VRHIP_ERR_UNSUPPORTED,
                "vrhip_render_batch: ray caster only, iteration 0, no image-order ESS, no ambient occlusion");
-    // (the opt-in experiment kernels of the A/B builds take one camera per launch)
-    VR_REQUIRE(r, !cams || (!r->march && !r->lds_stage), VRHIP_ERR_UNSUPPORTED,
-               "vrhip_render_batch_views: per-frame cameras are not supported by the experiment kernels");
     const uint32_t packed = tile_ids ? n_tiles * tile_w * tile_h : width * height;
     VR_REQUIRE(r, out_frame_stride == 0 || out_frame_stride >= packed, VRHIP_ERR_INVALID,
                "vrhip_render_batch: frame stride smaller than a frame");
