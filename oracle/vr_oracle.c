@@ -331,11 +331,13 @@ static float vol_nearest(const vol_t *v, float px, float py, float pz)
 }
 
 /* TF read: read_imagef(tffData, linearSmp, x) on the RGBA8 1-D image
- * (volumeraycast.cl:777,808); UNORM8 -> c / 255.0f. */
+ * (volumeraycast.cl:777,808); UNORM8 -> c / 255.0f.  x is first clamped to [-1, 2]: every x
+ * outside reads TF[0] or TF[n-1] exactly, as CLAMP_TO_EDGE does for x <= 0 and x >= 1, and the
+ * index stays far inside int range.  NaN reads as -1 (fmaxf): TF[0]. */
 static void tff_linear(const vro_scene *s, float x, float out[4])
 {
     int n = (int)s->tff_n;
-    float ub = x * (float)n - 0.5f;
+    float ub = fminf(fmaxf(x, -1.0f), 2.0f) * (float)n - 0.5f;
     float fl = floorf(ub);
     float a = ub - fl;
     int i = (int)fl;
@@ -345,6 +347,15 @@ static void tff_linear(const vro_scene *s, float x, float out[4])
         float t1 = (float)s->tff[4 * (size_t)i1 + c] / 255.0f;
         out[c] = g_literal ? (1.0f - a) * t0 + a * t1 : lerpf(t0, t1, a);
     }
+}
+
+void vro_tff_linear(const uint8_t *tff_rgba, uint32_t n, float x, float out[4])
+{
+    vro_scene s;
+    memset(&s, 0, sizeof s);
+    s.tff = tff_rgba;
+    s.tff_n = n;
+    tff_linear(&s, x, out);
 }
 
 /* read_imageui(tffPrefix, nearestSmp, x).x (volumeraycast.cl:780-781): normalised,

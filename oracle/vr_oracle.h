@@ -126,6 +126,8 @@ void vro_brick_layout(const uint32_t res[3], uint32_t edge[3], float brick_res_f
 void vro_calc_scaling(const uint32_t res[3], const double thickness[3], float model_scale[3]);
 /* volumerendercl.cpp:879-884 */
 void vro_prefix_sum(const uint8_t *tff_rgba, uint32_t n, uint32_t *prefix);
+/* the renderer's TF read (read_imagef(tffData, linearSmp, x)) on an n-entry RGBA8 table */
+void vro_tff_linear(const uint8_t *tff_rgba, uint32_t n, float x, float out[4]);
 
 /* generateBricks kernel, volumeraycast.cl:932-961. `out` holds 2*tex[0]*tex[1]*tex[2]
  * values of the volume's own type. */

@@ -150,6 +150,17 @@ def prefix_sum(tff):
     return out
 
 
+def tff_linear(tff, x):
+    """The renderer's TF read at density x on the RGBA8 table tff ([n, 4] uint8): float32[4]."""
+    tff = np.ascontiguousarray(tff, dtype=np.uint8).reshape(-1)
+    out = np.zeros(4, dtype=np.float32)
+    f = lib().vro_tff_linear
+    f.restype = None
+    f.argtypes = [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]
+    f(tff.ctypes.data_as(C.c_void_p), C.c_uint32(tff.size // 4), C.c_float(x), out.ctypes.data_as(C.c_void_p))
+    return out
+
+
 def generate_bricks(vol, fmt):
     """vol: ndarray [z, y, x] of the format's dtype. Returns ndarray [bz, by, bx, 2]."""
     vol = np.ascontiguousarray(vol, dtype=_NP_DTYPE[fmt])

@@ -118,6 +118,39 @@ def oracle_params(res, view, kw, seed=SEED):
     return cam, rp, rc, pt
 
 
+FLOAT_PALETTES = ("hu", "straddle", "huge", "negative", "specials")
+
+
+def float_volume(palette, res, seed=7, nch=1):
+    """A FLOAT volume [z, y, x] (or [z, y, x, nch]) of raw values outside [0, 1], from the unit noise field v:
+    hu        v * 4095 - 1024                   CT Hounsfield units
+    straddle  v * 2 - 0.5                       both sides of [0, 1]
+    huge      v * 3e7 + 1                       x * n far above 2^31 for every table size
+    negative  -(v * 1000) - 0.5                 all below 0
+    specials  straddle, 3 % of the voxels replaced by NaN, +-inf, -0.0, denormals and +-3e38"""
+    planes = []
+    for c in range(nch):
+        v = common.noise_volume(res, FLOAT, seed=seed + c, smooth=False).astype(np.float64)
+        if palette == "hu":
+            f = v * 4095.0 - 1024.0
+        elif palette in ("straddle", "specials"):
+            f = v * 2.0 - 0.5
+        elif palette == "huge":
+            f = v * 3e7 + 1.0
+        elif palette == "negative":
+            f = -(v * 1000.0) - 0.5
+        else:
+            raise ValueError(palette)
+        f = f.astype(np.float32)
+        if palette == "specials":
+            rng = np.random.default_rng(seed + 100 + c)
+            special = np.array([np.nan, np.inf, -np.inf, -0.0, 1e-40, -1e-41, 3e38, -3e38], np.float32)
+            pick = rng.random(f.shape) < 0.03
+            f[pick] = special[rng.integers(0, special.size, int(pick.sum()))]
+        planes.append(f)
+    return planes[0] if nch == 1 else np.stack(planes, axis=-1)
+
+
 def multichannel_volume(fmt, nch, res):
     planes = [common.noise_volume(res, fmt, seed=20 + c, smooth=False) for c in range(nch)]
     vol = np.stack(planes, axis=-1)

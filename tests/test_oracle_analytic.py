@@ -287,3 +287,40 @@ def test_rgba_and_rg_volumes_closed_form():
     off, _, _ = vro.render_tile(rg, vro.UCHAR, tff, cam, rp, rc, use_ess=False, W=40, H=40)
     assert st_on["samples_taken"] == 0 and np.all(on[..., :3] == 1.0)
     assert np.array_equal(off, img2)
+
+
+def test_float_outside_unit_range_reads_tf_edges():
+    """FLOAT volumes are raw values (a CT volume in Hounsfield units reaches the kernel as it is).
+    read_imagef(tffData, linearSmp, x) with CLAMP_TO_EDGE (OpenCL 1.2 8.2) gives TF[n-1] for every
+    x >= 1 and TF[0] for every x <= 0.  A constant volume of such a value then follows the closed form
+    of test_constant_density_closed_form with that entry's colour and opacity -- also where x * n
+    passes 2^31, which an unclamped float -> int index conversion wraps -- and equals the frame of a
+    constant 1.0 or 0.0 volume, with ESS on and off and for tables of 1024 and 4096 entries."""
+    flt_max = float(np.finfo(np.float32).max)
+    high = [1.0, 1.7, 1e3, 2.0e6, 2.2e6, 5e6, 1e30, flt_max]
+    low = [0.0, -0.0, -3.0, -5e6, -flt_max]
+    res = (16, 16, 16)
+    cam, rp, rc = _params(rate=1.5, res=res)
+    for n in (1024, 4096):
+        tff = np.zeros((n, 4), np.uint8)
+        tff[:] = [0, 0, 255, 3]          # interior: never read by these volumes
+        tff[0] = [0, 255, 0, 5]          # TF[0]: green, alpha 5 / 255
+        tff[-1] = [255, 0, 0, 9]         # TF[n-1]: red, alpha 9 / 255
+        for ess in (True, False):
+            for values, a8, rgb in ((high, 9, (1, 0, 0)), (low, 5, (0, 1, 0))):
+                frames = {}
+                for v in values:
+                    vol = np.full(res[::-1], v, np.float32)
+                    img, st, _ = vro.render_tile(vol, vro.FLOAT, tff, cam, rp, rc, use_ess=ess, W=32, H=32)
+                    frames[v] = img
+                    hit = img[..., 3] > 0
+                    assert hit.sum() == st["rays_hit"] > 0, (n, ess, v)
+                    a = np.float64(np.float32(a8) / np.float32(255))
+                    alpha = img[..., 3][hit].astype(np.float64)
+                    n_ray = np.log1p(-alpha) / np.log1p(-a) * 1.5
+                    assert np.all(np.abs(n_ray - np.round(n_ray)) < 2e-3), (n, ess, v)
+                    for c in range(3):   # background 1: 1 - (1 - c) * alpha
+                        np.testing.assert_allclose(img[..., c][hit], 1.0 - (1.0 - rgb[c]) * alpha, atol=2e-6,
+                                                   err_msg="n=%d ess=%s v=%r" % (n, ess, v))
+                for v in values[1:]:
+                    np.testing.assert_array_equal(frames[v], frames[values[0]], err_msg="n=%d ess=%s v=%r" % (n, ess, v))

@@ -107,3 +107,30 @@ def test_powr_definition_against_libm():
             worst = max(worst, abs(float(L.vro_powr(float(x), float(y))) - ref))
     print("max |vro_powr - pow| on [0, 1]: %.3g" % worst)
     assert worst <= 2e-7
+
+
+FLOAT_RANGE_CASES = [
+    # palette (tests/scenes.float_volume), channels, res, (W, H), view, tff, kwargs -- finite FLOAT values
+    # outside [0, 1]; the reference is undefined for NaN and +-inf, so those scenes are not here
+    ("hu", 1, (40, 40, 40), (64, 56), "rot30", "default", {}),
+    ("straddle", 1, (40, 40, 40), (64, 56), "close", "opaque", {"illum": 2}),
+    ("hu", 1, (36, 36, 36), (64, 48), "rot30", "haze", {"ess": False, "illum": 0, "ao": True}),
+    ("straddle", 1, (36, 36, 36), (64, 48), "inside", "default", {"illum": 5, "contours": True}),
+    ("straddle", 2, (36, 40, 32), (64, 48), "rot30", "default", {}),
+    ("straddle", 4, (32, 32, 32), (64, 48), "close", "default", {"ess": False}),   # (colours of a few units:
+                                                                                   # 1e-4 is absolute)
+]
+
+
+@pytest.mark.parametrize("i", range(len(FLOAT_RANGE_CASES)))
+def test_float_range_scene(i):
+    """FLOAT volumes of CT values (v * 4095 - 1024) and of values on both sides of [0, 1] (v * 2 - 0.5):
+    the TF reads at TF[0] / TF[n-1] beyond the table, the brick start values and the prefix read's border
+    0 all take part."""
+    palette, nch, res, size, view, tff, kw = FLOAT_RANGE_CASES[i]
+    vol = scenes.float_volume(palette, res, seed=13, nch=nch)
+    if nch == 4:   # keep the opacity channel moderate (and finite after the opacity correction)
+        vol[..., 3] = np.abs(vol[..., 3]) * np.float32(0.2)
+    a, b, sa, sb = _both(vol, vro.FLOAT, common.tffs()[tff], scenes.oracle_params(res, view, kw), size[0], size[1],
+                         kw.get("ess", True))
+    _check("FLOAT_RANGE_CASES[%d]" % i, a, b, sa, sb)

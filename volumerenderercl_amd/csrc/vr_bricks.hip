@@ -18,13 +18,20 @@ namespace {
 
 constexpr int kThreads = 256;
 
-template <typename VT> struct Key;   // order-preserving map VT -> uint32
+// Order-preserving map VT -> uint32.  enc_min / enc_max are the keys a voxel enters the brick's min / max
+// with: NaN enters neither (the neutral keys ~0 and 0), as OpenCL's min / max of a number and NaN keep the
+// number (volumeraycast.cl:955-956, DESIGN.md "Numerics").  -0.0 ranks below +0.0; the two compare equal.
+template <typename VT> struct Key;
 template <> struct Key<uint8_t> {
+    static __device__ uint32_t enc_min(uint8_t v) { return v; }
+    static __device__ uint32_t enc_max(uint8_t v) { return v; }
     static __device__ uint32_t enc(uint8_t v) { return v; }
     static __device__ uint8_t dec(uint32_t k) { return (uint8_t)k; }
     static __device__ uint8_t top() { return 255; }          // 1.0 as UNORM8
 };
 template <> struct Key<uint16_t> {
+    static __device__ uint32_t enc_min(uint16_t v) { return v; }
+    static __device__ uint32_t enc_max(uint16_t v) { return v; }
     static __device__ uint32_t enc(uint16_t v) { return v; }
     static __device__ uint16_t dec(uint32_t k) { return (uint16_t)k; }
     static __device__ uint16_t top() { return 65535; }
@@ -39,6 +46,8 @@ template <> struct Key<float> {
     {
         return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
     }
+    static __device__ uint32_t enc_min(float v) { return v == v ? enc(v) : 0xffffffffu; }
+    static __device__ uint32_t enc_max(float v) { return v == v ? enc(v) : 0u; }
     static __device__ float top() { return 1.0f; }
 };
 
@@ -86,9 +95,9 @@ __global__ __launch_bounds__(kThreads) void vr_build_bricks_kernel(VolView vol, 
                             if (y < ylo || y >= yhi) continue;   // block-uniform
 #pragma unroll
                             for (int dx = 0; dx < 4; ++dx) {
-                                uint32_t k = Key<VT>::enc(v[dz * 16 + dy * 4 + dx]);
-                                kmin[dx] = min(kmin[dx], k);
-                                kmax[dx] = max(kmax[dx], k);
+                                const VT e = v[dz * 16 + dy * 4 + dx];
+                                kmin[dx] = min(kmin[dx], Key<VT>::enc_min(e));
+                                kmax[dx] = max(kmax[dx], Key<VT>::enc_max(e));
                             }
                         }
                     }

@@ -14,7 +14,8 @@ constexpr int kSparseLevels = 13;   // 2^12 = 4096 >= max transfer function entr
 // (min, max) of the raw voxel values of every cell with its halo: voxels
 // [(c << s) - 1, ((c + 1) << s) + 1] per axis, clamped to the volume.  One wave per cell; the
 // lanes sweep the (2^s + 3)^2 voxels of a slice (gathers inside a handful of micro-bricks).
-// NaN voxels (FLOAT volumes) mark the cell min > max: never culled, never empty.
+// A NaN voxel (FLOAT volumes) makes the cell (-inf, +inf), as in the streaming build below: a record that
+// survives every later min / max and that vr_cell_bounds_kernel never culls and never marks empty.
 template <typename VT>
 __global__ __launch_bounds__(kThreads) void vr_cell_minmax_kernel(VolView vv, CellView grid,
                                                                   float2 *out, size_t cell0)
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(kThreads) void vr_cell_minmax_kernel(VolView vv, Ce
         mx = omx > mx ? omx : mx;
     }
     const bool any_bad = __ballot(bad) != 0ull;
-    if (lane == 0) out[cell] = any_bad ? make_float2(1.f, 0.f) : make_float2(mn, mx);
+    if (lane == 0) out[cell] = any_bad ? make_float2(-__builtin_inff(), __builtin_inff()) : make_float2(mn, mx);
 }
 
 // ---- the same (min, max) by separable streaming passes (cells of 4, 8 or 16 voxels)
@@ -318,6 +319,10 @@ __global__ __launch_bounds__(kThreads) void vr_cell_sparse_kernel(TfView tf, flo
 // adjacent entries, so its opacity is at most the larger of them up to an ulp, and exactly 0 when
 // both are 0.  One extra table entry on either side of the index range and a relative margin of
 // 1e-6 (8 ulps) on the bound cover the roundings.
+// All of that needs finite samples.  A cell with a NaN voxel ((-inf, +inf) from either build), an infinite one,
+// or one beyond +-FLT_MAX / 2 (where the fetch's q - p can overflow) can sample NaN or +-inf, which the TF read
+// takes to TF[0] or TF[n-1] whatever the cell's range: such a cell gets bound 2 -- never culled, never empty --
+// whatever the TF (DESIGN.md "Numerics").  Below FLT_MAX / 2 a fetch stays finite and within [min, max].
 __global__ __launch_bounds__(kThreads) void vr_cell_bounds_kernel(const float2 *minmax,
                                                                   size_t n_cells, float inv_max,
                                                                   int n, const float *T,
@@ -327,7 +332,8 @@ __global__ __launch_bounds__(kThreads) void vr_cell_bounds_kernel(const float2 *
     float b = 2.0f;   // above every threshold: never cull
     if (c < n_cells) {
         const float2 mm = minmax[c];
-        if (mm.x <= mm.y) {
+        constexpr float kHalfMax = 0x1.fffffep126f;   // FLT_MAX / 2
+        if (mm.x <= mm.y && fabsf(mm.x) <= kHalfMax && fabsf(mm.y) <= kHalfMax) {
             const float fn = (float)n;
             float flo = floorf((mm.x * inv_max) * fn - 0.5f) - 1.0f;
             float fhi = floorf((mm.y * inv_max) * fn - 0.5f) + 2.0f;

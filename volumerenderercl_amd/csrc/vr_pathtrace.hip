@@ -325,7 +325,7 @@ __global__ __launch_bounds__(kBlockDim) VR_PT_OCC void vr_pathtrace_kernel(
                 // (the opacity only matters where the step was fetched: :432 below tests `need` first)
 #pragma unroll
                 for (int k = 0; k < B; ++k)
-                    if (need[k] || !cull) al[k] = tff_linear_alpha(s_tff, tffn, dens[k]);
+                    if (need[k] || !cull) al[k] = tff_linear_alpha<kRawDensity<VT>>(s_tff, tffn, dens[k]);
             }
             PT_STAMP(2);   // fetch + TF
             // the walk's exit conditions, in step order -- as selects, not branches (the bodies are assignments; as
@@ -494,7 +494,7 @@ __global__ __launch_bounds__(kBlockDim) VR_PT_OCC void vr_pathtrace_kernel(
                 if (!px.accepted) {
                     state = P_WRITE;   // no interaction: the background colour, w = 1
                 } else {
-                    const float4 col = tff_linear(s_tff, tffn, px.adens);
+                    const float4 col = tff_linear<kRawDensity<VT>>(s_tff, tffn, px.adens);
                     px.c0 = col.x; px.c1 = col.y; px.c2 = col.z;
                     px.hit_pos = px.apos;
                     const f3 sp = mk3(px.apos.x * 0.5f + 0.5f, px.apos.y * 0.5f + 0.5f,
@@ -518,7 +518,7 @@ __global__ __launch_bounds__(kBlockDim) VR_PT_OCC void vr_pathtrace_kernel(
             } else if (ended == P_SCATTER) {
                 float s0 = px.env0, s1 = px.env1, s2 = px.env2;
                 if (px.accepted) {
-                    const float4 col = tff_linear(s_tff, tffn, px.adens);
+                    const float4 col = tff_linear<kRawDensity<VT>>(s_tff, tffn, px.adens);
                     s0 = col.x; s1 = col.y; s2 = col.z;
                 }
                 px.c0 = px.c0 + (s0 - px.c0) * 0.5f;   // mix(color, scatterColor, 0.5f), :493

@@ -345,7 +345,7 @@ VR_DEV void eval_batch(const V &vol, const float4 *s_tff, int tffn, float *s_sta
     VR_MARK("E_tf");
     float4 tfc[kBatch];
 #pragma unroll
-    for (int k = 0; k < kBatch; ++k) tfc[k] = tff_linear(s_tff, tffn, dens[k]);
+    for (int k = 0; k < kBatch; ++k) tfc[k] = tff_linear<kRawDensity<VT>>(s_tff, tffn, dens[k]);
 
     // CL_RGBA / CL_RG volumes (:838-855): the voxel is the colour (RGBA) or (r, g) -> colour
     // (r, 0, 0) with opacity TF(|g|); neither is shaded.  dens[] holds channel 0 already.
@@ -361,7 +361,7 @@ VR_DEV void eval_batch(const V &vol, const float4 *s_tff, int tffn, float *s_sta
                                          : vc.nearest(pk[k].x, pk[k].y, pk[k].z);
             }
             if (vol.channels == 4) tfc[k] = make_float4(dens[k], ch[0], ch[1], ch[2]);
-            else tfc[k] = make_float4(dens[k], 0.f, 0.f, tff_linear(s_tff, tffn, fabsf(ch[0] / 1.f)).w);
+            else tfc[k] = make_float4(dens[k], 0.f, 0.f, tff_linear<kRawDensity<VT>>(s_tff, tffn, fabsf(ch[0] / 1.f)).w);
         }
     }
 
@@ -527,7 +527,7 @@ VR_DEV uint32_t eval_front(const V &vol, const float4 *s_tff, int tffn, float *s
         for (int k = 0; k < kBatch; ++k) dens[k] = vol.linear(pk[k].x, pk[k].y, pk[k].z);
     }
 #pragma unroll
-    for (int k = 0; k < kBatch; ++k) ef.tfc[k] = tff_linear(s_tff, tffn, dens[k]);
+    for (int k = 0; k < kBatch; ++k) ef.tfc[k] = tff_linear<kRawDensity<VT>>(s_tff, tffn, dens[k]);
     const bool shade_mode = rp.illumType == 1;   // :809
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t n_slots = 0;
@@ -838,7 +838,7 @@ VR_DEV void apply_ao(const V &vol, const float4 *s_tff, int tffn, const RayCtx &
         while ((float)cnt * stepSize < r) {
             ++cnt;
             const f3 p = add3(pos, scale3(scale3(dir, (float)cnt), stepSize));
-            sample += tff_linear_alpha(s_tff, tffn, vol.linear(p.x, p.y, p.z));
+            sample += tff_linear_alpha<kRawDensity<VT>>(s_tff, tffn, vol.linear(p.x, p.y, p.z));
             if (sample > 0.98f) break;
         }
         sample /= (float)cnt;

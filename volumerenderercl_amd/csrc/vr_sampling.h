@@ -5,6 +5,7 @@
 #pragma once
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "vr_device_math.h"
 #include "vr_internal.h"
@@ -365,10 +366,27 @@ struct Vol {
     }
 };
 
-// read_imagef(tffData, linearSmp, x) on the float4 table
+// Can a density of voxel type VT lie outside [0, 1]?  UNORM voxels (UCHAR, USHORT) cannot; FLOAT voxels are raw
+// values (a CT volume in Hounsfield units, any simulation field), including +-inf and NaN.
+template <typename VT>
+constexpr bool kRawDensity = !(std::is_same<VT, uint8_t>::value || std::is_same<VT, uint16_t>::value);
+
+// The TF read's coordinate.  Every x outside [-1, 2] reads what x = -1 or x = 2 reads: TF[0] or TF[n-1] exactly
+// (both taps on the edge entry, lerp(t, t, a) = t), which CLAMP_TO_EDGE gives for every x <= 0 and x >= 1.  The
+// clamp keeps x * n - 0.5 and its floor far inside int range (an unclamped 2^31 / n or +inf saturates the
+// conversion and wraps the index) and leaves every x in [-1, 2] -- every UNORM density -- bit-identical.
+// NaN reads as -1 (fmaxf returns the other operand): TF[0].  DESIGN.md "Numerics", SURVEY.md B.3.
+template <bool RAW>
+VR_DEV float tff_coord(float x)
+{
+    return RAW ? fminf(fmaxf(x, -1.0f), 2.0f) : x;
+}
+
+// read_imagef(tffData, linearSmp, x) on the float4 table; RAW: x may lie outside [0, 1] (kRawDensity)
+template <bool RAW>
 VR_DEV float4 tff_linear(const float4 *tff, int n, float x)
 {
-    float ub = x * (float)n - 0.5f;
+    float ub = tff_coord<RAW>(x) * (float)n - 0.5f;
     float fl = floorf(ub);
     float a = ub - fl;
     int i = (int)fl;
@@ -381,9 +399,10 @@ VR_DEV float4 tff_linear(const float4 *tff, int n, float x)
     r.w = lerpf(t0.w, t1.w, a);
     return r;
 }
+template <bool RAW>
 VR_DEV float tff_linear_alpha(const float4 *tff, int n, float x)
 {
-    float ub = x * (float)n - 0.5f;
+    float ub = tff_coord<RAW>(x) * (float)n - 0.5f;
     float fl = floorf(ub);
     float a = ub - fl;
     int i = (int)fl;
@@ -398,12 +417,12 @@ VR_DEV float4 gradient_tff(const V &vol, const float4 *s_tff, int tffn, f3 p)
 {
     const f3 off = mk3(1.0f / vol.fw, 1.0f / vol.fh, 1.0f / vol.fd);
     f3 s1, s2;
-    s1.x = tff_linear_alpha(s_tff, tffn, vol.linear(p.x + (-off.x), p.y + 0.0f, p.z + 0.0f));
-    s1.y = tff_linear_alpha(s_tff, tffn, vol.linear(p.x + 0.0f, p.y + (-off.y), p.z + 0.0f));
-    s1.z = tff_linear_alpha(s_tff, tffn, vol.linear(p.x + 0.0f, p.y + 0.0f, p.z + (-off.z)));
-    s2.x = tff_linear_alpha(s_tff, tffn, vol.linear(p.x + off.x, p.y + 0.0f, p.z + 0.0f));
-    s2.y = tff_linear_alpha(s_tff, tffn, vol.linear(p.x + 0.0f, p.y + off.y, p.z + 0.0f));
-    s2.z = tff_linear_alpha(s_tff, tffn, vol.linear(p.x + 0.0f, p.y + 0.0f, p.z + off.z));
+    s1.x = tff_linear_alpha<kRawDensity<VT>>(s_tff, tffn, vol.linear(p.x + (-off.x), p.y + 0.0f, p.z + 0.0f));
+    s1.y = tff_linear_alpha<kRawDensity<VT>>(s_tff, tffn, vol.linear(p.x + 0.0f, p.y + (-off.y), p.z + 0.0f));
+    s1.z = tff_linear_alpha<kRawDensity<VT>>(s_tff, tffn, vol.linear(p.x + 0.0f, p.y + 0.0f, p.z + (-off.z)));
+    s2.x = tff_linear_alpha<kRawDensity<VT>>(s_tff, tffn, vol.linear(p.x + off.x, p.y + 0.0f, p.z + 0.0f));
+    s2.y = tff_linear_alpha<kRawDensity<VT>>(s_tff, tffn, vol.linear(p.x + 0.0f, p.y + off.y, p.z + 0.0f));
+    s2.z = tff_linear_alpha<kRawDensity<VT>>(s_tff, tffn, vol.linear(p.x + 0.0f, p.y + 0.0f, p.z + off.z));
     const f3 g = sub3(s2, s1);
     f3 n = normalize3(g);
     if (dot3(g, g) == 0.0f) n = mk3(0.57735f, 0.57735f, 0.57735f);
@@ -421,7 +440,8 @@ VR_DEV uint32_t prefix_nearest(const uint32_t *prefix, uint32_t n, float x)
 // The reference's per-brick skip test (volumeraycast.cl:777-787) on one (min,max) pair.
 VR_DEV bool skip_test(const TfView &tf, float mn, float mx)
 {
-    float alphaMax = tff_linear_alpha(tf.tff, (int)tf.tff_n, mx);
+    // (the table is in global memory here: the read is clamped for every voxel type)
+    float alphaMax = tff_linear_alpha<true>(tf.tff, (int)tf.tff_n, mx);
     if (!(alphaMax < 1e-6f)) return false;
     return prefix_nearest(tf.prefix, tf.prefix_n, mn) == prefix_nearest(tf.prefix, tf.prefix_n, mx);
 }
