@@ -124,6 +124,22 @@ public:
     void renderFramesTiles(size_t width, size_t height, size_t tile_w, size_t tile_h,
                            const std::vector<unsigned int> &tile_ids, const std::vector<unsigned int> &seeds,
                            const std::vector<std::array<float, 16>> &views, float *dev_out, size_t frame_stride = 0);
+    // ---- the progressive path tracer (technique 1), many samples per call (vrhip_render_samples): seeds.size()
+    // consecutive iterations of the accumulated image -- sample k with jitter seed seeds[k] at iteration
+    // (current iteration + k) -- in as few launch sets as possible, bit for bit what seeds.size() runRaycastNoGL calls
+    // with those seeds leave in the frame buffer.  Advances the iteration by seeds.size(), as runRaycastNoGL advances
+    // it by one.  samplesPerLaunch: samples per launch set (0 = the library's default).
+    // `output` receives the accumulated frame (width*height*4 floats, row 0 = top) ...
+    void renderSamples(size_t width, size_t height, const std::vector<unsigned int> &seeds, std::vector<float> &output,
+                       unsigned int samplesPerLaunch = 0);
+    // ... or DEVICE memory dev_out[height][width][4] does (nullptr: the image stays in the frame buffer); returns
+    // without waiting
+    void renderSamples(size_t width, size_t height, const std::vector<unsigned int> &seeds, float *dev_out,
+                       unsigned int samplesPerLaunch = 0);
+    // the same for a tile subset, as renderTiles: dev_out[n_tiles][tile_h][tile_w][4]
+    void renderSamples(size_t width, size_t height, size_t tile_w, size_t tile_h,
+                       const std::vector<unsigned int> &tile_ids, const std::vector<unsigned int> &seeds,
+                       float *dev_out, unsigned int samplesPerLaunch = 0);
     // the jitter seeds the next n runRaycast calls would use (the default-seeded std::mt19937 member, or the pinned seed)
     std::vector<unsigned int> drawSeeds(size_t n);
     // phase-1 sample rounds per ray (vrhip_set_round_budget): 10 for one frame at a time, 48 for launch sets of

@@ -283,6 +283,27 @@ int vrhip_render_batch_views(vrhip_renderer *r, uint32_t width, uint32_t height,
                              uint32_t tile_h, const uint32_t *tile_ids, uint32_t n_tiles,
                              const uint32_t *seeds, const vrhip_camera_params *cams, uint32_t n_frames,
                              float *out_dev, uint32_t out_frame_stride);
+/* Progressive path tracer (technique 1): n_samples CONSECUTIVE iterations of the accumulated image in as few sets
+ * of launches as possible.  Sample k is traced with jitter seed seeds[k] (rendering_params.seed is not used) at
+ * iteration rendering_params.iteration + k, and the renderer's frame buffer ends up bit for bit where n_samples
+ * calls of vrhip_render_frame with those seeds and iterations would have left it: the running mean
+ * prev + (cur - prev) / (iteration + 1) per colour channel, alpha 1, a sample whose ray misses the box replacing
+ * the pixel with the background (volumeraycast.cl:677-704).  With iteration 0 the first sample is written, not
+ * averaged; with iteration > 0 the call carries on from the frame buffer as it stands.  Like every entry point
+ * here it does NOT advance rendering_params.iteration.
+ * A set holds samples_per_launch samples (0: the default; at most 256, and fewer where a set would exceed 2^32
+ * pixels): one launch of the sample kernel -- the work queue holds every 8x8 patch once per sample -- and one
+ * streaming fold, in sample order, of the set's per-sample records (17 bytes per pixel and sample of scratch,
+ * allocated on first use, kept, freed with the renderer).  A larger n_samples is a chain of such sets.
+ * tile_ids == NULL: the whole frame, out_rgba[height][width][4]; else the tile subset as in vrhip_render_tiles,
+ * out_rgba[n_tiles][tile_h][tile_w][4].  out_rgba may be NULL (the image stays in the frame buffer), host memory or
+ * (out_is_device) device memory.  vrhip_get_stats: the sums over all samples; vrhip_last_kernel_seconds and
+ * vrhip_last_launch_info: the last set, its fold included (with phase timing on, phase 2 is the fold).
+ * Technique 0: VRHIP_ERR_UNSUPPORTED.  n_samples == 0 or seeds == NULL: VRHIP_ERR_INVALID. */
+int vrhip_render_samples(vrhip_renderer *r, uint32_t width, uint32_t height,
+                         uint32_t tile_w, uint32_t tile_h, const uint32_t *tile_ids, uint32_t n_tiles,
+                         const uint32_t *seeds, uint32_t n_samples, uint32_t samples_per_launch /* 0 = default */,
+                         float *out_rgba, int out_is_device);
 /* getLastExecTime (volumerendercl.cpp:1053-1056): HIP-event time of the last ray-cast
  * kernel launch, seconds. */
 double vrhip_last_kernel_seconds(const vrhip_renderer *r);
@@ -320,7 +341,8 @@ typedef struct vrhip_launch_info {
     uint32_t patch_classes;  /* 1: the pre-pass used per-patch classes                                  */
     uint32_t sorted_phase2;  /* 1: suspended rays were counting-sorted, longest first                   */
     uint32_t views;          /* 1: per-frame cameras (vrhip_render_batch_views with cams != NULL)       */
-    uint32_t reserved[16];
+    uint32_t samples;        /* 1: the sample variant of the path tracer and its fold (vrhip_render_samples) */
+    uint32_t reserved[15];
 } vrhip_launch_info;
 /* VRHIP_ERR_NODATA before the first render call. */
 int vrhip_last_launch_info(const vrhip_renderer *r, vrhip_launch_info *out);

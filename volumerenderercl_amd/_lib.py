@@ -54,7 +54,7 @@ class LaunchInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in (
         "technique", "frames", "work_items", "prepass", "ray_list", "phase1_waves", "phase2_waves", "round_budget",
         "footprint", "empty_skip", "skip_in_lds", "instrumented", "extras", "patch_classes", "sorted_phase2",
-        "views")] + [("reserved", C.c_uint32 * 16)]
+        "views", "samples")] + [("reserved", C.c_uint32 * 15)]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
@@ -96,6 +96,8 @@ SYMBOLS = {
     "vrhip_render_batch_views": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                            C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                            C.c_uint32]),
+    "vrhip_render_samples": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                       C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int]),
     "vrhip_set_round_budget": (C.c_int, [_H, C.c_uint32]),
     "vrhip_upload_volume_device": (C.c_int, [_H, C.c_void_p, _U3, C.c_int, C.c_uint32]),
     "vrhip_synth_volume": (C.c_int, [_H, C.c_int, _U3, C.c_int, C.c_uint32]),

@@ -485,6 +485,41 @@ void VolumeRenderCL::renderFramesTiles(size_t width, size_t height, size_t tile_
                                                    uint32_t(seeds.size()), dev_out, uint32_t(frame_stride)));
 }
 
+// ---- the progressive path tracer, many samples per call (vrhip_render_samples)
+
+void VolumeRenderCL::renderSamples(size_t width, size_t height, const std::vector<unsigned int> &seeds,
+                                   std::vector<float> &output, unsigned int samplesPerLaunch)
+{
+    if (!_volLoaded) return;
+    pushParams();
+    output.resize(width * height * 4);
+    check("renderSamples", vrhip_render_samples(_r, uint32_t(width), uint32_t(height), 0, 0, nullptr, 0, seeds.data(),
+                                                uint32_t(seeds.size()), samplesPerLaunch, output.data(), 0));
+    _rendering_params.iteration += static_cast<unsigned int>(seeds.size());
+}
+
+void VolumeRenderCL::renderSamples(size_t width, size_t height, const std::vector<unsigned int> &seeds, float *dev_out,
+                                   unsigned int samplesPerLaunch)
+{
+    if (!_volLoaded) return;
+    pushParams();
+    check("renderSamples", vrhip_render_samples(_r, uint32_t(width), uint32_t(height), 0, 0, nullptr, 0, seeds.data(),
+                                                uint32_t(seeds.size()), samplesPerLaunch, dev_out, 1));
+    _rendering_params.iteration += static_cast<unsigned int>(seeds.size());
+}
+
+void VolumeRenderCL::renderSamples(size_t width, size_t height, size_t tile_w, size_t tile_h,
+                                   const std::vector<unsigned int> &tile_ids, const std::vector<unsigned int> &seeds,
+                                   float *dev_out, unsigned int samplesPerLaunch)
+{
+    if (!_volLoaded) return;
+    pushParams();
+    check("renderSamples", vrhip_render_samples(_r, uint32_t(width), uint32_t(height), uint32_t(tile_w), uint32_t(tile_h),
+                                                tile_ids.data(), uint32_t(tile_ids.size()), seeds.data(),
+                                                uint32_t(seeds.size()), samplesPerLaunch, dev_out, 1));
+    _rendering_params.iteration += static_cast<unsigned int>(seeds.size());
+}
+
 std::vector<unsigned int> VolumeRenderCL::drawSeeds(size_t n)
 {
     std::vector<unsigned int> out(n);

@@ -384,6 +384,10 @@ void write_ppm(const std::string &path, const std::vector<float> &rgba, size_t w
         "         [--tf default|FILE] [--illum N] [--no-ess] [--ortho] [--nearest] [--rate R]\n"
         "         [--bg R G B] [--gradient-bg] [--seed S] [--frames N] [--device D] --out PREFIX\n"
         "         [--pathtrace] [--extinction E]   (technique 1; --frames = samples per pixel)\n"
+        "         [--samples-per-launch K]         (--pathtrace: the N samples in launch sets of K -- vrhip_render_samples,\n"
+        "                                           the same image bit for bit; 0 = the library's default set size, the\n"
+        "                                           default; 1 = one launch per sample, as before; with --bench: one\n"
+        "                                           untimed image, then the N samples timed with HIP events, ms per sample)\n"
         "         [--downsample FACTOR]            (volumeDownsampling: writes <dat>_<N>.raw/.dat, no frame)\n"
         "         [--state FILE.json] [--tf-stops FILE.tff]   (files saved by the reference GUI)\n"
         "         [--tf-easing linear|quad|cubic] [--dump-tf FILE]   (interpolation between the stops; --dump-tf\n"
@@ -437,7 +441,7 @@ int main(int argc, char **argv)
     size_t tile = 64;
     bool loopback = false, force_gather = false;
     bool independent = false, bench = false;
-    int frames_per_launch = 0, frames_in_flight = 2, round_budget = 48;
+    int frames_per_launch = 0, frames_in_flight = 2, round_budget = 48, samples_per_launch = 0;
     double root_share = 1.0;
     double rate = 1.5;
     std::array<float, 4> bg = {{1, 1, 1, 1}};
@@ -491,6 +495,7 @@ int main(int argc, char **argv)
         else if (a == "--independent") independent = true;
         else if (a == "--bench") bench = true;
         else if (a == "--frames-per-launch") { need(i, 1); frames_per_launch = std::atoi(argv[++i]); }
+        else if (a == "--samples-per-launch") { need(i, 1); samples_per_launch = std::atoi(argv[++i]); if (samples_per_launch < 0) usage(); }
         else if (a == "--frames-in-flight") { need(i, 1); frames_in_flight = std::atoi(argv[++i]); }
         else if (a == "--round-budget") { need(i, 1); round_budget = std::atoi(argv[++i]); }
         else if (a == "--root-share") { need(i, 1); root_share = std::atof(argv[++i]); }
@@ -896,6 +901,61 @@ int main(int argc, char **argv)
             return 0;
         }
         const std::array<float, 16> the_view = have_view ? view : view_matrix(q, tr);
+        if (pathtrace && !independent && !use_path && frames >= 1 && (samples_per_launch != 1 || bench)) {
+            // the progressive image's N samples: in launch sets of K (VolumeRenderCL::renderSamples), or -- K = 1 under
+            // --bench -- one launch per sample without the copy to the host between them.  The seeds are the ones the
+            // per-sample loop below draws: the written image is the same bit for bit.
+            const std::vector<unsigned int> seeds = vr.drawSeeds(size_t(frames));
+            auto render = [&](bool to_host) {
+                vr.updateView(the_view);   // iteration 0
+                if (samples_per_launch == 1) {
+                    for (size_t k = 0; k < seeds.size(); ++k) {
+                        vr.setSeed(seeds[k]);
+                        if (to_host && k + 1 == seeds.size()) vr.runRaycastNoGL(W, H, frame);
+                        else vr.runRaycast(W, H);
+                    }
+                } else if (to_host) {
+                    vr.renderSamples(W, H, seeds, frame, unsigned(samples_per_launch));
+                } else {
+                    vr.renderSamples(W, H, seeds, static_cast<float *>(nullptr), unsigned(samples_per_launch));
+                }
+            };
+            double ms_per_sample = 0.0;
+            if (bench) {
+                auto hip_ok = [](hipError_t e, const char *what) {
+                    if (e != hipSuccess) throw std::runtime_error(std::string("ERROR: ") + what + " (" + hipGetErrorString(e) + ")");
+                };
+                render(false);   // untimed: buffers, work queue, cell grid, scratch
+                hipStream_t st = static_cast<hipStream_t>(vr.stream());
+                hipEvent_t e0, e1;
+                hip_ok(hipEventCreate(&e0), "hipEventCreate");
+                hip_ok(hipEventCreate(&e1), "hipEventCreate");
+                hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize");
+                hip_ok(hipEventRecord(e0, st), "hipEventRecord");
+                render(false);
+                hip_ok(hipEventRecord(e1, st), "hipEventRecord");
+                hip_ok(hipEventSynchronize(e1), "hipEventSynchronize");
+                float ms = 0.f;
+                hip_ok(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
+                ms_per_sample = double(ms) / frames;
+                (void)hipEventDestroy(e0);
+                (void)hipEventDestroy(e1);
+            }
+            render(true);
+            vrhip_launch_info li;
+            std::memset(&li, 0, sizeof li);
+            (void)vrhip_last_launch_info(vr.handle(), &li);
+            std::ofstream raw(out + ".rgba.f32", std::ios::binary);
+            raw.write(reinterpret_cast<const char *>(frame.data()), std::streamsize(frame.size() * sizeof(float)));
+            write_ppm(out + ".ppm", frame, W, H);
+            auto res = vr.getResolution();
+            std::printf("{\"device\": \"%s\", \"volume\": [%u, %u, %u], \"width\": %zu, \"height\": %zu, "
+                        "\"samples\": %d, \"samples_per_launch\": %u, \"sample_kernel\": %s, \"bench\": %s, "
+                        "\"ms_per_sample\": %.5f, \"out\": \"%s.rgba.f32\"}\n",
+                        vr.getCurrentDeviceName().c_str(), res[0], res[1], res[2], W, H, frames, li.frames,
+                        li.samples ? "true" : "false", bench ? "true" : "false", ms_per_sample, out.c_str());
+            return 0;
+        }
         for (size_t sg = 0, in_seg = 0, f = 0; f < size_t(frames); ++f, ++in_seg) {
             const std::array<float, 16> *pv = &the_view;
             if (use_path) {   // frame f of the path: frame in_seg of segment sg

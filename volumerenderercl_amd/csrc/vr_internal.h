@@ -170,7 +170,11 @@ struct FrameView {
     // Unused: FrameView and CellView are kernel arguments, and these words keep the offsets of the arguments behind
     // them where they were.  The phase-1 kernel at three waves per SIMD, register-bound, is sensitive to them: with
     // the arguments moved it spilled differently and the benchmark took 0.5 % longer.
-    uint32_t arg_pad[4];
+    // (The first two of the four now hold the mark plane of a set of samples, read only by the kernels instantiated
+    // with SAMPLES = true -- vr_pathtrace.hip: one byte per record of `out`, 1 = traced sample, 0 = the ray missed
+    // the box.  Same size, same offsets.)
+    uint8_t *sample_mark;
+    uint32_t arg_pad[2];
     // Phase-2 scheduling: `cost` keeps, per pixel, the phase-2 rounds the pixel's ray needed in the
     // previous frame.  Suspended rays are sorted by it, longest first (counting sort into
     // `order`), so that the longest chains start first and the 16 rays of a group are alike.
@@ -286,6 +290,13 @@ struct RaycastLaunch {
     int bind_events;       // 0: record events behind the launches instead (VRHIP_EVENT_BIND=0, A/B)
     uint8_t *hit_out;      // imgEss: this frame's hit image (resolved after the march), or nullptr
     vrhip_launch_info *info;   // optional: the launchers record what they launched (vrhip_last_launch_info)
+    // technique 1, vrhip_render_samples: the set's frames are consecutive samples of one progressive image, sample k
+    // at iteration render.iteration + k.  frame.out / frame.sample_mark are the scratch planes (sample_plane records
+    // each), fold_out the caller's own destination for the accumulated pixels (or nullptr).
+    int samples;
+    uint32_t sample_plane;
+    float4 *fold_out;
+    int keep_stats;            // launch_timed: the counters go on from the set before (chained sets of samples)
 };
 
 // hipLaunchKernelGGL, or -- with an event -- the launch whose completion the event is bound to

@@ -119,7 +119,15 @@ struct PtPixel {   // the pixel a lane is working on
 #else
 #define VR_PT_OCC
 #endif
-template <typename VT, int INSTR>
+// SAMPLES (vrhip_render_samples): the work queue holds every patch once per SAMPLE of a set of consecutive iterations
+// of the progressive image (the sample's index rides in the patch's frame bits, its seed is fr.seeds[index]), so the
+// launch, an idle wave's ray set-up and the tail of lanes finishing one by one are paid once per set.  The running
+// mean is order-dependent fp32 arithmetic and a pixel's samples end in any order, on any wave: this variant never
+// touches fr.fb.  It writes every sample's raw colour to its plane of a scratch buffer (fr.out, which the queue's
+// out_base already addresses plane by plane) and one byte beside it (fr.sample_mark: 1 traced, 0 the ray missed the
+// box and the record is the background) -- a background's alpha may be any float, 1 included, so no alpha value can
+// carry that mark.  vr_pt_fold_kernel below then folds the planes into the frame buffer in sample order.
+template <typename VT, int INSTR, bool SAMPLES = false>
 __global__ __launch_bounds__(kBlockDim) VR_PT_OCC void vr_pathtrace_kernel(
     VolView vv, TfView tf, CellView grid, FrameView fr, vrhip_camera_params cam,
     vrhip_rendering_params rp, vrhip_pathtrace_params pt, DevStats *stats, uint32_t *touched)
@@ -158,6 +166,7 @@ __global__ __launch_bounds__(kBlockDim) VR_PT_OCC void vr_pathtrace_kernel(
     uint32_t sub = (blockIdx.x * (kBlockDim / 64u) + (threadIdx.x >> 6)) % kDrawCounters, sub_tried = 0;   // (stage 1's counters)
 
     WaveTile wt = {0, 0, 0};
+    uint32_t seed = rp.seed;           // of the current patch (wave-uniform): its sample's own with SAMPLES
 
     // Exit condition reached by every wave: the queue head only grows, every walk ends after at
     // most 513 steps, and the refill / transition stages run unconditionally once no lane walks.
@@ -198,6 +207,7 @@ __global__ __launch_bounds__(kBlockDim) VR_PT_OCC void vr_pathtrace_kernel(
                     if (q >= fr.n_wave_tiles) { drained = true; break; }
                     patch_taken = 0;
                     wt = fr.queue[q];
+                    if (SAMPLES) seed = fr.seeds[wt_frame(wt)];
                 }
                 // the i-th idle lane takes pixel patch_taken + i of the patch
                 const uint32_t rank = (uint32_t)__builtin_popcountll(idle & ((1ull << lane) - 1ull));
@@ -212,16 +222,21 @@ __global__ __launch_bounds__(kBlockDim) VR_PT_OCC void vr_pathtrace_kernel(
                     px.out_index = wt.out_base + ly * fr.out_stride + lx;
                     // pixels outside the frame (ragged right / bottom patches) are dropped
                     if (px.gx < fr.W && px.gy < fr.H) {
-                        const Ray ray = make_ray(px.gx, px.gy, fr, cam, rp, rp.seed);
+                        const Ray ray = make_ray(px.gx, px.gy, fr, cam, rp, seed);
                         px.env0 = ray.env[0]; px.env1 = ray.env[1];
                         px.env2 = ray.env[2]; px.env3 = ray.env[3];
                         if (!ray.hit) {   // :677-683
                             const float4 o = make_float4(px.env0, px.env1, px.env2, px.env3);
-                            fr.fb[(size_t)px.gy * fr.W + px.gx] = o;
-                            if (fr.out) fr.out[px.out_index] = o;
+                            if (SAMPLES) {
+                                fr.out[px.out_index] = o;
+                                fr.sample_mark[px.out_index] = 0;
+                            } else {
+                                fr.fb[(size_t)px.gy * fr.W + px.gx] = o;
+                                if (fr.out) fr.out[px.out_index] = o;
+                            }
                         } else {
                             if (INSTR) c_hit++;
-                            px.rnd = parallel_rng3(px.gx, px.gy, rp.seed);   // :688
+                            px.rnd = parallel_rng3(px.gx, px.gy, seed);   // :688
                             const uint32_t rand2 = parallel_rng(px.rnd);     // :423
                             px.dt = vr_logf(1.f - map_uint_float(rand2)) / pt.max_extinction;
                             px.thr = map_uint_float(px.rnd);
@@ -537,6 +552,11 @@ __global__ __launch_bounds__(kBlockDim) VR_PT_OCC void vr_pathtrace_kernel(
                 px.cnt = 0;
                 state = P_SHADOW;
             }
+            if (SAMPLES && state == P_WRITE) {   // the sample as it is: the fold accumulates
+                fr.out[px.out_index] = make_float4(px.c0, px.c1, px.c2, 1.f);
+                fr.sample_mark[px.out_index] = 1;
+                state = P_FETCH;
+            }
             if (state == P_WRITE) {    // :689-704 accumulate + write
                 const size_t fi = (size_t)px.gy * fr.W + px.gx;
                 float r0 = px.c0, r1 = px.c1, r2 = px.c2;
@@ -587,10 +607,48 @@ __global__ __launch_bounds__(kBlockDim) VR_PT_OCC void vr_pathtrace_kernel(
     }
 }
 
-template <typename VT, int INSTR>
+// The fold of a set of samples (vr_pathtrace_kernel with SAMPLES): one thread per pixel of the set's patches -- the
+// patches of sample 0, every n-th queue entry -- walks the pixel's n records in sample order and applies what the
+// one-sample kernel applies per launch (:689-704 and :677-683): a traced sample enters the running mean with
+// iteration first + k (the sample of iteration 0 is written, never averaged: what the frame buffer held does not
+// leak in), a missed one replaces the pixel, alpha included.  A patch row is 128 contiguous bytes of a plane.
+__global__ __launch_bounds__(kBlockDim) void vr_pt_fold_kernel(FrameView fr, const float4 *planes, const uint8_t *mark,
+                                                               uint32_t n, uint32_t plane, uint32_t first, float4 *out)
+{
+    const uint32_t p = blockIdx.x * (kBlockDim / 64u) + (threadIdx.x >> 6);
+    if (p >= fr.n_wave_tiles / n) return;
+    const WaveTile wt = fr.queue[(size_t)p * n];
+    const uint32_t lx = threadIdx.x & 7u, ly = (threadIdx.x >> 3) & 7u;
+    const uint32_t gx = wt_col(wt) * 8u + lx, gy = wt_row(wt) * 8u + ly;
+    if (gx >= fr.W || gy >= fr.H) return;
+    const size_t oi = (size_t)wt.out_base + ly * fr.out_stride + lx, fi = (size_t)gy * fr.W + gx;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (first != 0) acc = fr.fb[fi];
+#pragma unroll 4
+    for (uint32_t k = 0; k < n; ++k) {
+        const float4 s = planes[(size_t)k * plane + oi];
+        const uint32_t iteration = first + k;
+        if (!mark[(size_t)k * plane + oi]) {
+            acc = s;
+        } else {
+            float r0 = s.x, r1 = s.y, r2 = s.z;
+            if (iteration != 0) {
+                const float it1 = (float)(iteration + 1u);
+                r0 = acc.x + (r0 - acc.x) / it1;
+                r1 = acc.y + (r1 - acc.y) / it1;
+                r2 = acc.z + (r2 - acc.z) / it1;
+            }
+            acc = make_float4(r0, r1, r2, 1.f);
+        }
+    }
+    fr.fb[fi] = acc;
+    if (out) out[oi] = acc;
+}
+
+template <typename VT, int INSTR, bool SAMPLES = false>
 hipError_t launch_pt(const RaycastLaunch &a, hipStream_t stream)
 {
-    auto k = vr_pathtrace_kernel<VT, INSTR>;
+    auto k = vr_pathtrace_kernel<VT, INSTR, SAMPLES>;
     const size_t lds = (size_t)a.tf.tff_n * sizeof(float4);
     int nb = 0;
     {
@@ -604,12 +662,21 @@ hipError_t launch_pt(const RaycastLaunch &a, hipStream_t stream)
     if (grid.x == 0) return hipSuccess;
     const bool bind_stop = a.bind_events && a.stop_event && a.stop_bound;   // (one launch: it carries the frame's end)
     const bool bind_start = a.bind_events && a.start_event && a.start_bound;
-    vr_launch_kernel(k, grid, block, lds, stream, bind_start ? a.start_event : nullptr, bind_stop ? a.stop_event : nullptr, a.vol, a.tf, a.cells, a.frame, a.cam,
+    // (a set of samples ends with its fold: that launch carries the set's end, the event between the two is the phases')
+    vr_launch_kernel(k, grid, block, lds, stream, bind_start ? a.start_event : nullptr,
+                     bind_stop && !SAMPLES ? a.stop_event : nullptr, a.vol, a.tf, a.cells, a.frame, a.cam,
                      a.render, a.pathtrace, a.stats, a.touched);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess && bind_stop) *a.stop_bound = true;
     if (e == hipSuccess && bind_start) *a.start_bound = true;
     if (e == hipSuccess && a.mid_event) e = hipEventRecord(a.mid_event, stream);
+    if (SAMPLES && e == hipSuccess) {
+        const uint32_t n = a.frame.set_frames, n_patches = a.frame.n_wave_tiles / n;
+        vr_launch_kernel(vr_pt_fold_kernel, dim3((n_patches + kBlockDim / 64u - 1u) / (kBlockDim / 64u)), block, 0, stream, nullptr,
+                         bind_stop ? a.stop_event : nullptr, a.frame, (const float4 *)a.frame.out,
+                         (const uint8_t *)a.frame.sample_mark, n, a.sample_plane, a.render.iteration, a.fold_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && bind_stop) *a.stop_bound = true;
     return e;
 }
 
@@ -637,6 +704,18 @@ hipError_t launch_pt_typed(const RaycastLaunch &a, hipStream_t stream)
     return launch_pt<VT, 2>(a, stream);
 }
 
+// a set of samples: production and stats builds (the touched-bitmap variants count one frame's traffic)
+template <typename VT>
+hipError_t launch_pt_samples(const RaycastLaunch &a, hipStream_t stream)
+{
+    if (!a.frame.out || !a.frame.sample_mark || !a.frame.seeds || !a.frame.set_frames || !a.sample_plane ||
+        a.frame.n_wave_tiles % a.frame.set_frames)
+        return hipErrorInvalidValue;
+    if (a.instr == 0) return launch_pt<VT, 0, true>(a, stream);
+    if (a.instr == 1) return launch_pt<VT, 1, true>(a, stream);
+    return hipErrorInvalidValue;
+}
+
 } // namespace
 
 hipError_t vr_launch_pathtrace(const RaycastLaunch &a, hipStream_t stream)
@@ -645,6 +724,15 @@ hipError_t vr_launch_pathtrace(const RaycastLaunch &a, hipStream_t stream)
         a.info->technique = 1;
         a.info->work_items = a.frame.n_wave_tiles;
         a.info->instrumented = (uint32_t)a.instr;
+        a.info->samples = a.samples ? 1u : 0u;
+    }
+    if (a.samples) {
+        switch (a.format) {
+        case VRHIP_UCHAR: return launch_pt_samples<uint8_t>(a, stream);
+        case VRHIP_USHORT: return launch_pt_samples<uint16_t>(a, stream);
+        case VRHIP_FLOAT: return launch_pt_samples<float>(a, stream);
+        default: return hipErrorInvalidValue;
+        }
     }
     switch (a.format) {
     case VRHIP_UCHAR: return launch_pt_typed<uint8_t>(a, stream);

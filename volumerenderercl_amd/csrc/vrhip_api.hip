@@ -30,6 +30,11 @@ struct VolumeSlot {
 std::string g_create_error;
 
 constexpr uint32_t kSkipLdsMaxBytes = 64 * 1024;   // bitmap staged in LDS up to this size
+// vrhip_render_samples: samples per launch set when the caller leaves it open -- the best of the sweep in DESIGN.md
+// section 5.4 (4 ... 64 per set at 1024^2: the more the faster), as long as a set's scratch stays at what that sweep
+// ran with (64 samples of 1024^2 pixels, 17 bytes each: 1.06 GiB); a caller that names a set size gets it
+constexpr uint32_t kDefaultSamplesPerLaunch = 64;
+constexpr unsigned long long kDefaultSampleRecords = 64ull << 20;
 
 } // namespace
 
@@ -123,6 +128,8 @@ struct vrhip_renderer {
     bool ray_list = true;             // VRHIP_NO_RAYLIST=1: phase 1 walks the live patches instead
     uint32_t *seeds_dev = nullptr;    // kMaxBatchFrames jitter seeds of a batch of frames
     vrhip_camera_params *cams_dev = nullptr;   // kMaxBatchFrames cameras of a batch of per-frame views
+    void *samples_dev = nullptr;      // vrhip_render_samples: the records and marks of a set of samples (lazily, reused)
+    size_t samples_cap = 0;           // bytes
     bool sort_cont = true;            // VRHIP_NO_SORT=1 disables
     LiveTile *live = nullptr;         // DDA pre-pass output: patches with rays that sample
     bool prepass = true;              // VRHIP_NO_PREPASS=1 disables
@@ -960,7 +967,7 @@ int ensure_patch_classes(vrhip_renderer *r, RaycastLaunch *a)
 
 int launch_timed(vrhip_renderer *r, const RaycastLaunch &a)
 {
-    if (a.instr) VR_HIP(r, hipMemsetAsync(r->stats_dev, 0, sizeof(DevStats), r->stream));
+    if (a.instr && !a.keep_stats) VR_HIP(r, hipMemsetAsync(r->stats_dev, 0, sizeof(DevStats), r->stream));
     // control words: the block of this set was zeroed by the first kernel of the previous set (memset
     // only for the first set, or after something else has used the block)
     if (!r->ctrl_clean[r->ctrl_sel])
@@ -1387,6 +1394,7 @@ void vrhip_destroy(vrhip_renderer *r)
     if (r->env) (void)hipFree(r->env);
     if (r->seeds_dev) (void)hipFree(r->seeds_dev);
     if (r->cams_dev) (void)hipFree(r->cams_dev);
+    if (r->samples_dev) (void)hipFree(r->samples_dev);
     if (r->fp) (void)hipFree(r->fp);
     if (r->live) (void)hipFree(r->live);
     if (r->order) (void)hipFree(r->order);
@@ -2001,6 +2009,69 @@ int vrhip_render_batch_views(vrhip_renderer *r, uint32_t width, uint32_t height,
     a.frame.seeds = r->seeds_dev;
     a.frame.cams = cams ? r->cams_dev : nullptr;
     return launch_timed(r, a);
+}
+
+int vrhip_render_samples(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h,
+                         const uint32_t *tile_ids, uint32_t n_tiles, const uint32_t *seeds, uint32_t n_samples,
+                         uint32_t samples_per_launch, float *out_rgba, int out_is_device)
+{
+    if (!r) return VRHIP_ERR_INVALID;
+    if (set_device(r)) return VRHIP_ERR_HIP;
+    VR_REQUIRE(r, seeds && n_samples >= 1, VRHIP_ERR_INVALID, "vrhip_render_samples: no seeds");
+    VR_REQUIRE(r, r->render.technique == 1, VRHIP_ERR_UNSUPPORTED,
+               "vrhip_render_samples: path tracer only (technique 1); the ray caster's frames do not accumulate here");
+    VR_REQUIRE(r, height <= (8u << kFrameShift) && width <= (8u << kFrameShift), VRHIP_ERR_INVALID,
+               "Invalid output image size.");
+    VR_REQUIRE(r, !tile_ids || n_tiles > 0, VRHIP_ERR_INVALID, "vrhip_render_samples: empty tile list");
+    const unsigned long long plane = tile_ids ? (unsigned long long)n_tiles * tile_w * tile_h
+                                              : (unsigned long long)width * height;
+    VR_REQUIRE(r, plane >= 1 && plane <= 0xffffffffull, VRHIP_ERR_INVALID, "vrhip_render_samples: too many pixels");
+    // samples per set: what was asked for (0: kDefaultSamplesPerLaunch), within the queue's frame bits and 2^32 records
+    unsigned long long per = samples_per_launch ? samples_per_launch : kDefaultSamplesPerLaunch;
+    if (!samples_per_launch && per * plane > kDefaultSampleRecords) per = kDefaultSampleRecords / plane ? kDefaultSampleRecords / plane : 1;
+    if (per > kMaxBatchFrames) per = kMaxBatchFrames;
+    if (per > n_samples) per = n_samples;
+    if (per * plane > 0xffffffffull) per = 0xffffffffull / plane;
+    // a tile subset for the host has no place of its own to land in: one more plane of the scratch
+    const bool stage = tile_ids && out_rgba && !out_is_device;
+    const uint32_t first = r->render.iteration;
+    for (uint32_t done = 0; done < n_samples;) {
+        const uint32_t m = (uint32_t)(per < n_samples - done ? per : n_samples - done);
+        int rc = prepare_render(r, width, height, tile_w, tile_h, tile_ids, n_tiles, m, 0);
+        if (rc) return rc;
+        const size_t rec_bytes = ((size_t)per + (stage ? 1u : 0u)) * (size_t)plane * sizeof(float4);
+        const size_t need = rec_bytes + (size_t)per * (size_t)plane;
+        if (need > r->samples_cap) {
+            VR_HIP(r, hipStreamSynchronize(r->stream));
+            if (r->samples_dev) VR_HIP(r, hipFree(r->samples_dev));
+            r->samples_dev = nullptr;
+            r->samples_cap = 0;
+            VR_HIP(r, hipMalloc(&r->samples_dev, need));
+            r->samples_cap = need;
+        }
+        if (!r->seeds_dev) VR_HIP(r, hipMalloc((void **)&r->seeds_dev, kMaxBatchFrames * sizeof(uint32_t)));
+        VR_HIP(r, hipMemcpyAsync(r->seeds_dev, seeds + done, m * sizeof(uint32_t), hipMemcpyHostToDevice, r->stream));
+        RaycastLaunch a;
+        fill_launch(r, width, height, tile_ids ? tile_w : width, &a);
+        float4 *const planes = (float4 *)r->samples_dev;
+        a.frame.out = planes;
+        a.frame.sample_mark = (uint8_t *)r->samples_dev + rec_bytes;
+        a.frame.seeds = r->seeds_dev;
+        a.render.iteration = first + done;
+        a.samples = 1;
+        a.sample_plane = (uint32_t)plane;
+        a.fold_out = stage ? planes + (size_t)per * (size_t)plane : out_is_device ? (float4 *)out_rgba : nullptr;
+        a.keep_stats = done != 0;
+        rc = launch_timed(r, a);
+        if (rc) return rc;
+        done += m;
+    }
+    if (out_rgba && !out_is_device) {
+        const float4 *src = stage ? (const float4 *)r->samples_dev + (size_t)per * (size_t)plane : r->fb;
+        VR_HIP(r, hipMemcpyAsync(out_rgba, src, (size_t)plane * sizeof(float4), hipMemcpyDeviceToHost, r->stream));
+        VR_HIP(r, hipStreamSynchronize(r->stream));
+    }
+    return VRHIP_OK;
 }
 
 double vrhip_last_kernel_seconds(const vrhip_renderer *r)

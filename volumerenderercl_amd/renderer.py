@@ -283,6 +283,33 @@ class VolumeRenderCL:
             sd.ctypes.data_as(C.c_void_p), None if cams is None else C.cast(cams, C.c_void_p), int(sd.size),
             C.c_void_p(out_dev_ptr), int(frame_stride)))
 
+    def render_samples(self, width, height, seeds, out_dev_ptr=None, tile_w=0, tile_h=0, tile_ids=None,
+                       samples_per_launch=0):
+        """Progressive path tracer (technique 1): len(seeds) consecutive iterations of the accumulated
+        image -- sample k jittered by seeds[k] at iteration (current iteration + k) -- in as few launch
+        sets as possible (vrhip_render_samples), bit for bit what len(seeds) runRaycastNoGL calls with
+        those seeds leave in the frame buffer.  samples_per_launch: samples per set (0 = the library's
+        default).  With tile_ids the tile subset, compact [n_tiles][tile_h][tile_w][4].  Returns the
+        accumulated image as numpy when no device pointer is given, else writes it there and returns
+        None.  Advances the iteration by len(seeds)."""
+        if not self._vol_loaded:
+            return None
+        sd = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+        self._push_params()
+        ids = None if tile_ids is None else np.ascontiguousarray(tile_ids, dtype=np.uint32).reshape(-1)
+        out = None
+        if out_dev_ptr is None:
+            shape = (int(height), int(width), 4) if ids is None else (int(ids.size), int(tile_h), int(tile_w), 4)
+            out = np.zeros(shape, dtype=np.float32)
+        self._check(self._lib.vrhip_render_samples(
+            self._h, int(width), int(height), int(tile_w), int(tile_h),
+            None if ids is None else ids.ctypes.data_as(C.c_void_p), 0 if ids is None else int(ids.size),
+            sd.ctypes.data_as(C.c_void_p) if sd.size else None, int(sd.size), int(samples_per_launch),
+            out.ctypes.data_as(C.c_void_p) if out is not None else C.c_void_p(out_dev_ptr),
+            0 if out is not None else 1))
+        self._rendering.iteration += int(sd.size)
+        return out
+
     # ---- volume
     def loadVolumeData(self, props):
         """volumerendercl.cpp:765-805. `props` is a datraw.Properties (dat_file_name or
