@@ -37,11 +37,16 @@ public:
 
     // Reads the .dat description (unless raw_file_names is preset) and every time step.
     // Throws std::invalid_argument for empty names, std::runtime_error for I/O problems.
-    void read_files(Properties volume_properties);
+    // convert = false (no reference counterpart): every time step holds the raw file's bytes unchanged --
+    // no stretch, no division, no byte swap -- and an all-zero histogram; the .dat is parsed and the
+    // resolution inferred as usual.  For the device-side ingest (vrhip_ingest_raw).
+    void read_files(Properties volume_properties, bool convert = true);
     bool has_data() const;
     const std::vector<std::vector<char>> &data() const;   // throws when empty
     const Properties &properties() const;                 // throws when empty
     void clearData();
+    // the value range of data read with convert = false, once whoever converts it knows it
+    void set_value_range(float min_value, float max_value);
     const std::array<double, 256> &getHistogram(size_t timestep = 0);
 
 private:
@@ -52,4 +57,5 @@ private:
     Properties _prop;
     std::vector<std::vector<char>> _raw_data;
     std::vector<std::array<double, 256>> _histograms;
+    bool _converted = true;
 };

@@ -95,6 +95,10 @@ public:
     void renderTiles(size_t width, size_t height, size_t tile_w, size_t tile_h,
                      const std::vector<unsigned int> &tile_ids, float *out_tiles_dev,
                      bool advanceIteration = false);   // true: the frame counts for the running mean (:540)
+    // Device-side ingest (default off): loadVolumeData only reads the raw files; the maximum, the USHORT stretch /
+    // FLOAT normalisation and the histogram are computed in HBM (vrhip_ingest_raw), bit for bit what the host
+    // loader computes.  Set before loadVolumeData.  getHistogram answers for synthetic volumes either way.
+    void setDeviceIngest(bool on);
     void setSeed(unsigned int seed);   // pin the per-frame jitter seed
     void clearSeed();                  // back to the std::mt19937 sequence
     vrhip_renderer *handle() { return _r; }
@@ -151,6 +155,7 @@ public:
 
 private:
     void generateBricks();
+    void ingestTimestep(size_t t);
     void calcScaling();
     void pushParams();
     void beginFrame();
@@ -171,6 +176,8 @@ private:
     pathtrace_params _pathtrace_params;
     DatRawReader _dr;
     bool _synthetic = false;
+    bool _deviceIngest = false;
+    std::vector<std::array<double, 256>> _deviceHistograms;   // of ingested or synthetic time steps
     int _channels = 1;          // 1 = R, 2 = RG, 4 = RGBA (volDataToCLmem, :697-705)
     std::vector<unsigned char> _tff;          // what setTransferFunction / setTffPrefixSum were last given
     std::vector<unsigned int> _tffPrefixSum;  // (shareVolumes hands them to the twin)

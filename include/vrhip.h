@@ -122,6 +122,30 @@ int vrhip_upload_volume_device(vrhip_renderer *r, const void *dev_voxels, const 
 /* Synthetic inputs of SURVEY 8(d), generated on the GPU: kind 0 sphere, 1 shells. */
 int vrhip_synth_volume(vrhip_renderer *r, int kind, const uint32_t res[3], int format,
                        uint32_t timestep);
+/* Device-side ingest: the bytes of a .raw file as they are (`raw`, host memory) become time step `timestep`
+ * with everything the host loader does per voxel (DatRawReader::read_raw) done in HBM, bit for bit
+ * the loader's: the maximum over every whole word of the file (FLOAT words byte-swapped first when
+ * big_endian, USHORT words compared unswapped whatever the endianness, as the reference does), USHORT
+ * stretched by 65535.f / max and stored byte-swapped for big-endian files, FLOAT divided by the maximum, and
+ * the 256-bin histogram.  `raw` is uploaded slab by slab through a bounded staging buffer (environment
+ * variable VRHIP_INGEST_SLAB_BYTES, read by vrhip_create: rounded down to whole multiples of 4 slices, at
+ * least 4; default 256 MiB; no effect on any stored byte), de-interleaved on the device for `channels` = 2
+ * or 4, re-tiled raw, then converted in place.  hist: the loader's counts, over every scalar of every channel;
+ * *max_value: the loader's Properties::max_value (255 for UCHAR).  Bytes beyond res[0] * res[1] * res[2] *
+ * bytes per value * channels are not stored but do enter the maximum and the histogram (the loader's loops
+ * run over the whole file); fewer bytes: VRHIP_ERR_INVALID ("Volume size does not match size specified in
+ * dat file.").  A USHORT step of zeros only: the loader multiplies 0 by 65535 / FLT_MIN = inf and converts
+ * the NaN to an integer, which C++ leaves undefined; here the zeros stay zeros and are counted in bin 0. */
+int vrhip_ingest_raw(vrhip_renderer *r, const void *raw, size_t bytes, const uint32_t res[3], int format,
+                     int channels, int big_endian, uint32_t timestep, double hist[256], float *max_value);
+/* The loader's binning applied to the STORED values of time step `timestep`, however it got there (synthetic,
+ * device or host upload, ingest), every channel; nothing is converted: UCHAR bin = the byte, USHORT
+ * bin = value / 256, FLOAT bin = round(value * 255) if that lies in [0, 255], else 255.  For a step ingested
+ * from little-endian data this is the histogram vrhip_ingest_raw returned. */
+int vrhip_volume_histogram(vrhip_renderer *r, uint32_t timestep, double hist[256]);
+/* HIP-event seconds of the kernels of the last vrhip_ingest_raw (the host-to-device copies between them
+ * excluded), like vrhip_last_bricks_seconds. */
+double vrhip_last_ingest_seconds(const vrhip_renderer *r);
 /* Copy timestep `t` back as a dense x-fastest array (bytes must equal its size). */
 int vrhip_download_volume(vrhip_renderer *r, uint32_t timestep, void *host_dst, size_t bytes);
 /* volumeDownsampling's device part (volumerendercl.cpp:238-300 + kernel `downsampling`,

@@ -29,6 +29,9 @@ typedef struct vrdr_info_t {
  * name, i.e. Properties::raw_file_names = {raw_file}).  Returns 0, 1 (std::invalid_argument)
  * or 2 (std::runtime_error); vrdr_error() gives the exception text. */
 int vrdr_load(const char *dat_file, const char *raw_file, vrdr **out);
+/* The same with read_files(props, convert = false): vrdr_data(t) is the raw file's bytes unchanged (what
+ * vrhip_ingest_raw takes), the histograms are empty, min_value / max_value are not computed. */
+int vrdr_load_raw(const char *dat_file, const char *raw_file, vrdr **out);
 const char *vrdr_error(void);
 void vrdr_free(vrdr *h);
 int vrdr_info(vrdr *h, vrdr_info_t *info);

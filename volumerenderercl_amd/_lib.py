@@ -101,6 +101,10 @@ SYMBOLS = {
     "vrhip_set_round_budget": (C.c_int, [_H, C.c_uint32]),
     "vrhip_upload_volume_device": (C.c_int, [_H, C.c_void_p, _U3, C.c_int, C.c_uint32]),
     "vrhip_synth_volume": (C.c_int, [_H, C.c_int, _U3, C.c_int, C.c_uint32]),
+    "vrhip_ingest_raw": (C.c_int, [_H, C.c_void_p, C.c_size_t, _U3, C.c_int, C.c_int, C.c_int, C.c_uint32,
+                                   C.POINTER(C.c_double), C.POINTER(C.c_float)]),
+    "vrhip_volume_histogram": (C.c_int, [_H, C.c_uint32, C.POINTER(C.c_double)]),
+    "vrhip_last_ingest_seconds": (C.c_double, [_H]),
     "vrhip_download_volume": (C.c_int, [_H, C.c_uint32, C.c_void_p, C.c_size_t]),
     "vrhip_downsample_volume": (C.c_int, [_H, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, _U3]),
     "vrhip_clear_volumes": (C.c_int, [_H]),

@@ -77,10 +77,34 @@ void VolumeRenderCL::initialize(bool useGL, bool useCPU, cl_vendor, const std::s
     if (_dr.has_data()) {
         const auto &p = _dr.properties();
         for (size_t t = 0; t < _dr.data().size(); ++t)
-            check("volDataToCLmem",
-                  vrhip_upload_volume_channels(_r, _dr.data()[t].data(), p.volume_res.data(),
-                                               int(p.format), _channels, uint32_t(t)));
+            if (_deviceIngest)
+                ingestTimestep(t);   // (the reader holds raw file bytes: they are converted on the device again)
+            else
+                check("volDataToCLmem",
+                      vrhip_upload_volume_channels(_r, _dr.data()[t].data(), p.volume_res.data(),
+                                                   int(p.format), _channels, uint32_t(t)));
     }
+}
+
+void VolumeRenderCL::setDeviceIngest(bool on) { _deviceIngest = on; }
+
+// one time step of raw file bytes through vrhip_ingest_raw: histogram and value range as the host loader
+// would have left them in the reader
+void VolumeRenderCL::ingestTimestep(size_t t)
+{
+    const auto &p = _dr.properties();
+    if (_deviceHistograms.size() <= t) _deviceHistograms.resize(t + 1);
+    float maxValue = 0.f;
+    int rc = vrhip_ingest_raw(_r, _dr.data()[t].data(), _dr.data()[t].size(), p.volume_res.data(), int(p.format),
+                              _channels, p.endianness == DatRawReader::BIG ? 1 : 0, uint32_t(t),
+                              _deviceHistograms[t].data(), &maxValue);
+    if (rc == VRHIP_ERR_INVALID) {   // loadVolumeData's size check throws std::runtime_error (:740-742)
+        const std::string text = vrhip_last_error(_r);
+        _dr.clearData();
+        throw std::runtime_error(text);
+    }
+    check("vrhip_ingest_raw", rc);
+    _dr.set_value_range(0.f, maxValue);
 }
 
 void VolumeRenderCL::updateView(const std::array<float, 16> viewMat)   // :379-390
@@ -158,7 +182,8 @@ size_t VolumeRenderCL::loadVolumeData(const DatRawReader::Properties volumeFileP
     else
         std::cout << "Loading volume data defined in " << volumeFileProps.dat_file_name << std::endl;
     try {
-        _dr.read_files(volumeFileProps);
+        _dr.read_files(volumeFileProps, !_deviceIngest);
+        _deviceHistograms.clear();
         const auto &p = _dr.properties();
         std::cout << _dr.data().front().size() * _dr.data().size() << " bytes have been read from "
                   << _dr.data().size() << " file(s)." << std::endl;
@@ -181,6 +206,10 @@ size_t VolumeRenderCL::loadVolumeData(const DatRawReader::Properties volumeFileP
         const size_t bpv = p.format == DatRawReader::UCHAR ? 1 : p.format == DatRawReader::USHORT ? 2 : 4;
         check("clearVolumes", vrhip_clear_volumes(_r));
         for (size_t t = 0; t < _dr.data().size(); ++t) {
+            if (_deviceIngest) {
+                ingestTimestep(t);
+                continue;
+            }
             // (the reference checks one channel's worth, :740-742, and lets the image read beyond)
             if (size_t(p.volume_res[0]) * p.volume_res[1] * p.volume_res[2] * bpv * size_t(channels) >
                 _dr.data()[t].size()) {
@@ -247,7 +276,20 @@ const std::array<unsigned int, 4> VolumeRenderCL::getResolution() const   // :82
 
 const std::array<double, 256> &VolumeRenderCL::getHistogram(unsigned int timestep)   // :853-858
 {
+    if (_synthetic && _volLoaded) {
+        // a volume born in HBM has no loader histogram: the same binning over the stored voxels
+        if (_deviceHistograms.size() <= timestep) _deviceHistograms.resize(timestep + 1);
+        int rc = vrhip_volume_histogram(_r, timestep, _deviceHistograms[timestep].data());
+        if (rc == VRHIP_ERR_NODATA) throw std::invalid_argument("Invalid timestep for histogram data.");
+        check("vrhip_volume_histogram", rc);
+        return _deviceHistograms[timestep];
+    }
     if (!_dr.has_data()) throw std::invalid_argument("Invalid timestep for histogram data.");
+    if (_deviceIngest) {
+        if (timestep >= _deviceHistograms.size())
+            throw std::invalid_argument("No histogram data for selected timestep available.");
+        return _deviceHistograms[timestep];
+    }
     return _dr.getHistogram(timestep);
 }
 

@@ -388,6 +388,9 @@ void write_ppm(const std::string &path, const std::vector<float> &rgba, size_t w
         "                                           the same image bit for bit; 0 = the library's default set size, the\n"
         "                                           default; 1 = one launch per sample, as before; with --bench: one\n"
         "                                           untimed image, then the N samples timed with HIP events, ms per sample)\n"
+        "         [--device-ingest]                (--dat: the loader only reads the raw files; maximum, USHORT stretch /\n"
+        "                                           FLOAT normalisation and histogram are computed on the GPU -- the same\n"
+        "                                           voxels bit for bit)\n"
         "         [--downsample FACTOR]            (volumeDownsampling: writes <dat>_<N>.raw/.dat, no frame)\n"
         "         [--state FILE.json] [--tf-stops FILE.tff]   (files saved by the reference GUI)\n"
         "         [--tf-easing linear|quad|cubic] [--dump-tf FILE]   (interpolation between the stops; --dump-tf\n"
@@ -430,7 +433,7 @@ int main(int argc, char **argv)
     size_t W = 1024, H = 1024;
     double q[4] = {1, 0, 0, 0}, tr[3] = {0, 0, 2};
     bool have_view = false, ess = true, ortho = false, linear = true, gradient_bg = false, pin = false;
-    bool pathtrace = false;
+    bool pathtrace = false, device_ingest = false;
     double extinction = 100.0;
     int downsample = 0;
     std::string state_file, tf_stops, tf_easing = "linear", dump_tf;
@@ -475,6 +478,7 @@ int main(int argc, char **argv)
         else if (a == "--seed") { need(i, 1); seed = unsigned(std::strtoul(argv[++i], nullptr, 10)); pin = true; }
         else if (a == "--frames") { need(i, 1); frames = std::atoi(argv[++i]); }
         else if (a == "--pathtrace") pathtrace = true;
+        else if (a == "--device-ingest") device_ingest = true;
         else if (a == "--downsample") { need(i, 1); downsample = std::atoi(argv[++i]); }
         else if (a == "--state") { need(i, 1); state_file = argv[++i]; }
         else if (a == "--tf-stops") { need(i, 1); tf_stops = argv[++i]; }
@@ -581,6 +585,7 @@ int main(int argc, char **argv)
         if (!dat.empty()) {
             DatRawReader::Properties p;
             p.dat_file_name = dat;
+            vr.setDeviceIngest(device_ingest);
             vr.loadVolumeData(p);
         } else {
             DatRawReader::data_format f = synth_fmt == "USHORT" ? DatRawReader::USHORT

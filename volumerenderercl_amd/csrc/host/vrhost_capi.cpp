@@ -17,9 +17,7 @@ struct vrdr {
 
 static thread_local std::string g_error;
 
-extern "C" {
-
-int vrdr_load(const char *dat_file, const char *raw_file, vrdr **out)
+static int load(const char *dat_file, const char *raw_file, bool convert, vrdr **out)
 {
     if (!out) return 1;
     *out = nullptr;
@@ -28,7 +26,7 @@ int vrdr_load(const char *dat_file, const char *raw_file, vrdr **out)
         DatRawReader::Properties p;
         if (dat_file) p.dat_file_name = dat_file;
         if (raw_file && *raw_file) p.raw_file_names.push_back(raw_file);
-        h->reader.read_files(p);
+        h->reader.read_files(p, convert);
     } catch (const std::invalid_argument &e) {
         g_error = e.what();
         delete h;
@@ -41,6 +39,12 @@ int vrdr_load(const char *dat_file, const char *raw_file, vrdr **out)
     *out = h;
     return 0;
 }
+
+extern "C" {
+
+int vrdr_load(const char *dat_file, const char *raw_file, vrdr **out) { return load(dat_file, raw_file, true, out); }
+
+int vrdr_load_raw(const char *dat_file, const char *raw_file, vrdr **out) { return load(dat_file, raw_file, false, out); }
 
 const char *vrdr_error(void) { return g_error.c_str(); }
 

@@ -33,6 +33,8 @@ def _load():
         lib = C.CDLL(LIB_PATH)
         lib.vrdr_load.restype = C.c_int
         lib.vrdr_load.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
+        lib.vrdr_load_raw.restype = C.c_int
+        lib.vrdr_load_raw.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
         lib.vrdr_error.restype = C.c_char_p
         lib.vrdr_free.argtypes = [C.c_void_p]
         lib.vrdr_info.argtypes = [C.c_void_p, C.POINTER(_Info)]
@@ -69,12 +71,16 @@ class DatRawReader:
         self._data = []
         self._hist = []
 
-    def read_files(self, props):
-        """Raises ValueError (std::invalid_argument) / RuntimeError (std::runtime_error)."""
+    def read_files(self, props, convert=True):
+        """Raises ValueError (std::invalid_argument) / RuntimeError (std::runtime_error).
+        convert=False: data() holds each raw file's bytes unchanged (uint8 arrays; no stretch, division or
+        byte swap), histograms() is empty and min_value / max_value are not computed -- the input of
+        vrhip_ingest_raw."""
         lib = _load()
         h = C.c_void_p()
         raw = props.raw_file_names[0] if props.raw_file_names else None
-        rc = lib.vrdr_load(props.dat_file_name.encode(), raw.encode() if raw else None, C.byref(h))
+        load = lib.vrdr_load if convert else lib.vrdr_load_raw
+        rc = load(props.dat_file_name.encode(), raw.encode() if raw else None, C.byref(h))
         if rc != 0:
             msg = lib.vrdr_error().decode()
             raise ValueError(msg) if rc == 1 else RuntimeError(msg)
@@ -90,13 +96,15 @@ class DatRawReader:
         self._data, self._hist = [], []
         for t in range(info.n_timesteps):
             buf = C.string_at(lib.vrdr_data(h, t), info.bytes_per_timestep)
-            if info.format in _NP:
-                self._data.append(np.frombuffer(buf, dtype=_NP[info.format]).copy())
+            if convert and info.format in _NP:
+                whole = len(buf) - len(buf) % np.dtype(_NP[info.format]).itemsize   # (a file may end inside a word)
+                self._data.append(np.frombuffer(buf[:whole], dtype=_NP[info.format]).copy())
             else:
                 self._data.append(np.frombuffer(buf, dtype=np.uint8).copy())
-            hist = (C.c_double * 256)()
-            lib.vrdr_histogram(h, t, hist)
-            self._hist.append(np.array(hist))
+            if convert:
+                hist = (C.c_double * 256)()
+                lib.vrdr_histogram(h, t, hist)
+                self._hist.append(np.array(hist))
         lib.vrdr_free(h)
         self._prop = p
 

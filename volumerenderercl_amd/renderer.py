@@ -311,14 +311,18 @@ class VolumeRenderCL:
         return out
 
     # ---- volume
-    def loadVolumeData(self, props):
+    def loadVolumeData(self, props, ingest="host"):
         """volumerendercl.cpp:765-805. `props` is a datraw.Properties (dat_file_name or
-        raw_file_names set)."""
+        raw_file_names set).  ingest="device": the loader only reads the files; maximum, USHORT
+        stretch / FLOAT normalisation and histogram are computed in HBM (vrhip_ingest_raw), bit for
+        bit what the host loader (ingest="host", the default) computes."""
         from . import datraw
+        if ingest not in ("host", "device"):
+            raise ValueError("ingest must be 'host' or 'device'")
         self._vol_loaded = False
         try:
             reader = datraw.DatRawReader()
-            reader.read_files(props)
+            reader.read_files(props, convert=(ingest == "host"))
         except ValueError as e:      # std::invalid_argument -> runtime_error (:784-787)
             raise RuntimeError(str(e))
         p = reader.properties()
@@ -336,8 +340,50 @@ class VolumeRenderCL:
             raise RuntimeError("ARGB / BGRA volumes are not supported.")
         else:
             raise RuntimeError("Unknown or invalid volume color format.")   # :711
+        if ingest == "device":
+            return self._ingest_raw(vols, p, channels)
         return self.loadVolumeArrays(vols, p.format, p.slice_thickness, p.volume_res[:3],
                                      channels=channels)
+
+    def _ingest_raw(self, raws, p, channels):
+        """The device-ingest half of loadVolumeData: raw file bytes -> vrhip_ingest_raw per time step;
+        fills the histograms and the properties' min_value / max_value as the host loader does."""
+        if p.format not in NP_DTYPE:
+            raise RuntimeError("Unknown or invalid volume data format.")
+        self._check(self._lib.vrhip_clear_volumes(self._h))
+        self._histograms = []
+        for t, raw in enumerate(raws):
+            raw = np.ascontiguousarray(raw, dtype=np.uint8)
+            hist, vmax = (C.c_double * 256)(), C.c_float()
+            rc = self._lib.vrhip_ingest_raw(self._h, raw.ctypes.data_as(C.c_void_p), raw.nbytes,
+                                            _u3(p.volume_res[:3]), p.format, int(channels),
+                                            int(p.endianness), t, hist, C.byref(vmax))
+            if rc == _lib.ERR_INVALID:   # the size check of loadVolumeData throws std::runtime_error
+                raise RuntimeError(self._lib.vrhip_last_error(self._h).decode())
+            self._check(rc)
+            self._histograms.append(np.array(hist))
+            p.min_value, p.max_value = 0.0, float(vmax.value)
+        self._finish_load(p.volume_res[:3], len(raws), p.format, p.slice_thickness)
+        return len(raws)
+
+    def lastIngestSeconds(self):
+        return float(self._lib.vrhip_last_ingest_seconds(self._h))
+
+    def volumeHistogram(self, t=0):
+        """vrhip_volume_histogram: the loader's binning of the values stored in time step t."""
+        hist = (C.c_double * 256)()
+        self._check(self._lib.vrhip_volume_histogram(self._h, int(t), hist))
+        return np.array(hist)
+
+    def _finish_load(self, r, n_steps, fmt, thickness):
+        self._res = [int(r[0]), int(r[1]), int(r[2]), int(n_steps)]
+        self._format = fmt
+        self._thickness = [float(x) for x in thickness]
+        self._calc_scaling()
+        # default prefix sum of the linear ramp (volumerendercl.cpp:795-801)
+        prefix = np.cumsum(np.arange(1024, dtype=np.uint64) * 4).astype(np.uint32)
+        self._vol_loaded = True
+        self.setTffPrefixSum(prefix)
 
     def loadVolumeArrays(self, volumes, fmt, thickness=(1.0, 1.0, 1.0), res=None, channels=None):
         """Upload already-decoded time steps (ndarray [z, y, x], [z, y, x, c] for CL_RG / CL_RGBA
@@ -353,14 +399,7 @@ class VolumeRenderCL:
                 raise RuntimeError("Volume size does not match size specified in dat file.")
             self._check(self._lib.vrhip_upload_volume_channels(
                 self._h, v.ctypes.data_as(C.c_void_p), _u3(r), fmt, int(nch), t))
-        self._res = [int(r[0]), int(r[1]), int(r[2]), len(volumes)]
-        self._format = fmt
-        self._thickness = [float(x) for x in thickness]
-        self._calc_scaling()
-        # default prefix sum of the linear ramp (volumerendercl.cpp:795-801)
-        prefix = np.cumsum(np.arange(1024, dtype=np.uint64) * 4).astype(np.uint32)
-        self._vol_loaded = True
-        self.setTffPrefixSum(prefix)
+        self._finish_load(r, len(volumes), fmt, thickness)
         return len(volumes)
 
     def synthVolume(self, kind, res, fmt):
@@ -374,6 +413,7 @@ class VolumeRenderCL:
         self._thickness = [1.0, 1.0, 1.0]
         self._calc_scaling()
         self._vol_loaded = True
+        self._histograms = [self.volumeHistogram(0)]   # what the TF editor draws under the curve
 
     def downsampleVolume(self, t, factor):
         """Device part of volumeDownsampling (volumerendercl.cpp:238-300 + kernel
