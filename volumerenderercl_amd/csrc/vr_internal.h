@@ -272,7 +272,7 @@ struct RaycastLaunch {
     int format;            // vrhip_format
     int use_ess;
     int instr;             // 0 none, 1 stats, 2 stats + touched bitmap
-    int occ3;              // phase 1 on the ray list at three waves per SIMD (vr_raycast.hip kWavesWide): a schedule, not a result
+    int occ3;              // phase 1 on the ray list at three waves per SIMD (vr_raycast_kernels.h kWavesWide): a schedule, not a result
     int occ3_split;        // the same for phase 2
     DevStats *stats;
     uint32_t *touched;

@@ -1,5 +1,5 @@
-// vr_sampling.h -- device-side building blocks of the ray-cast kernels (single-TU header,
-// included by vr_raycast.hip only): volume / transfer-function / prefix reads restated from
+// vr_sampling.h -- device-side building blocks of the ray-cast kernels (included through
+// vr_raycast_kernels.h by the ray caster's units only): volume / transfer-function / prefix reads restated from
 // the OpenCL 1.2 image rules, the ESS skip bitmap kernel, ray set-up
 // (/root/reference/src/kernel/volumeraycast.cl:605-683) and the diagnostic phase stamps.
 #pragma once

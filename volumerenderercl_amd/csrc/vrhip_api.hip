@@ -909,7 +909,7 @@ void fill_launch(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t ou
     a->use_ess = r->use_ess ? 1 : 0;
     a->instr = r->stats_enabled ? 1 : 0;
     // Three waves per SIMD -- one workgroup of 12 waves per CU that share one transfer function and one skip bitmap
-    // in LDS, 168 VGPRs per lane (vr_raycast.hip kWavesWide) -- where waves wait more than they issue:
+    // in LDS, 168 VGPRs per lane (vr_raycast_kernels.h kWavesWide) -- where waves wait more than they issue:
     //  * volumes whose ESS bricks are too small for the empty-run lookahead (ray_skip_empty): the march waits for its
     //    fetches instead of stepping over empty cells (256^3: -12 % per frame, -6 % one frame at a time);
     //  * launch sets of several frames (the throughput schedule, a rank's tile share): enough rays for a third wave
