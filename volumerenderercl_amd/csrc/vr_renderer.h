@@ -1,0 +1,444 @@
+// vr_renderer.h -- the host state of one renderer (vrhip_renderer, include/vrhip.h), shared by the units that
+// implement the C ABI: vrhip_api.hip, vrhip_gather.hip, vrhip_ingest_api.hip.  Host only.
+//  * DevBuf / Handle: device memory, events and the stream, freed with the object that holds them;
+//  * grow(): the one place that (re)allocates a renderer's buffer;
+//  * the invalidation functions: one per cause, next to the table of what depends on what.
+#ifndef VR_RENDERER_H
+#define VR_RENDERER_H
+
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "vr_internal.h"
+
+// Device memory that goes away with its holder.  Never an object of static storage duration: a free after the
+// runtime has shut down is an error of its own.
+template <class T = void>
+struct DevBuf {
+    T *p = nullptr;
+    size_t bytes = 0;     // capacity (0 for a borrowed pointer)
+    bool owned = true;    // false: somebody else's memory (borrow()), never freed from here
+
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), bytes(o.bytes), owned(o.owned) { o.forget(); }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            p = o.p; bytes = o.bytes; owned = o.owned;
+            o.forget();
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+
+    void release()   // (errors of the free are ignored)
+    {
+        if (p && owned) (void)hipFree(p);
+        forget();
+    }
+    void borrow(T *other) { release(); p = other; owned = false; }
+    operator T *() const { return p; }
+
+private:
+    void forget() { p = nullptr; bytes = 0; owned = true; }
+};
+
+// An event or a stream, destroyed with its holder.
+template <class H, hipError_t (*Destroy)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(const Handle &) = delete;
+    Handle &operator=(const Handle &) = delete;
+    ~Handle() { if (h) (void)Destroy(h); }
+    operator H() const { return h; }
+};
+using DevEvent = Handle<hipEvent_t, hipEventDestroy>;
+using DevStream = Handle<hipStream_t, hipStreamDestroy>;
+
+struct VolumeSlot {
+    // owned, or -- in a `borrowed` slot -- pointers into the slot of the renderer that owns the voxels
+    DevBuf<> dev;         // micro-bricked voxels (channel 0 of a multi-channel volume)
+    DevBuf<> chan[3];     // channels 1..3 of CL_RG / CL_RGBA volumes
+    DevBuf<> bricks;      // (min,max) grid
+    bool bricks_built = false;
+    DevBuf<float2> pt_minmax;     // path tracer: per-cell (min,max) incl. halo, built on demand
+    bool pt_minmax_valid = false;
+    DevBuf<float2> fine_minmax;   // ray caster: the same on the finer grid of the empty bits
+    bool fine_minmax_valid = false;
+    bool borrowed = false;        // dev / chan / bricks belong to another renderer (vrhip_share_volumes)
+};
+
+struct vrhip_renderer {
+    int device = 0;
+    int num_cus = 256;
+    DevStream own_stream;             // (first: destroyed after everything that may still be freed behind it)
+    hipStream_t stream = nullptr;
+    mutable std::string err;
+    std::string devname;
+
+    uint32_t res[3] = {0, 0, 0};
+    int format = -1;
+    int channels = 1;                 // 1 = CL_R, 2 = CL_RG, 4 = CL_RGBA
+    // HBM layout of a time step: 4x4x4-voxel micro-bricks (vr_internal.h, DESIGN.md "Data
+    // layout"); nb = ceil(res / 4)
+    uint32_t nb[3] = {0, 0, 0};
+    std::vector<VolumeSlot> vols;
+    uint32_t timestep = 0;
+
+    DevBuf<float4> tff;
+    uint32_t tff_n = 0;
+    DevBuf<uint32_t> prefix;
+    uint32_t prefix_n = 0;
+
+    uint32_t brick_tex[3] = {0, 0, 0}, brick_edge[3] = {0, 0, 0};
+    float brick_res[3] = {1, 1, 1};
+    bool bricks_valid = false;
+
+    // ESS skip bitmap of the current timestep
+    DevBuf<uint32_t> skip_bits;
+    uint32_t skip_words = 0;
+    bool skip_dirty = true;
+    // patch culling of the DDA pre-pass: the skip bitmap dilated by cull_radius bricks (SkipView::near_bits)
+    DevBuf<uint32_t> near_bits;
+    DevBuf<uint8_t> near_scratch;
+    uint32_t cull_radius = 4;         // VRHIP_CULL_RADIUS (bricks; 0 = no patch culling)
+
+    // cell grid of the current timestep + TF (CellView, vr_internal.h): opacity bound for the
+    // path tracer, empty bits for the ray caster
+    CellView cells = {nullptr, nullptr, 0, 0, 0, 3, 0, 0, 0, 3};
+    DevBuf<float> cell_bound;
+    DevBuf<uint32_t> cell_empty;
+    DevBuf<float> cell_sparse;     // 13 x 4096 floats of scratch for the TF range-max table
+    bool cells_have_bound = false, cells_have_empty = false;   // r->cells' tables match volume, time step and TF
+    bool pt_cull = true;           // VRHIP_PT_NO_CULL=1 disables the path tracer's culling
+    bool pt_leap = true;           // VRHIP_PT_NO_LEAP=1: no leaps over macro cells (A/B)
+    bool pt_leap_far = true;       // VRHIP_PT_NO_FAR_LEAP=1: leaps stay inside one macro cell (A/B)
+    DevBuf<uint8_t> cell_dist;     // CellView::cdist (two buffers)
+    const uint8_t *cell_dist_table = nullptr;
+    bool skip_empty = true;        // VRHIP_NO_EMPTY_SKIP=1 disables the ray caster's empty runs
+    bool skip_empty_force = false; // VRHIP_EMPTY_SKIP=1: also where it is not expected to pay (see ray_skip_empty)
+
+    vrhip_camera_params cam;
+    vrhip_rendering_params render;
+    vrhip_raycast_params raycast;
+    vrhip_pathtrace_params pathtrace;
+    bool use_ess = true;
+
+    DevBuf<float4> fb;
+    uint32_t fb_w = 0, fb_h = 0;
+
+    DevBuf<DevStats> stats_dev;
+    bool stats_enabled = false;
+
+    // work queue of 8x8 wave tiles (centre first) for the current frame/tile set
+    DevBuf<WaveTile> queue_dev;
+    uint32_t queue_n = 0;
+    DevBuf<uint32_t> queue_head;      // 2 x kControlWords (queue head, cont count, cont head, pad, sort bins + cursors):
+                                      // the sets of launches alternate between the two blocks (FrameView::next_ctrl)
+    DevBuf<uint8_t> patch_class;      // FrameView::patch_class of the current queue, camera, parameters and skip bitmaps
+    std::vector<uint8_t> patch_class_key;   // what the classes were computed for (empty: nothing valid)
+    uint32_t skip_version = 0;        // bumped whenever the skip bitmaps are rebuilt
+    uint32_t queue_version = 0;       // bumped whenever the work queue is rebuilt
+    uint32_t queue_frames = 1;        // frames per set of the current queue
+    bool use_patch_classes = true;    // VRHIP_NO_PATCH_CLASS=1 disables
+    int occ_force = 0;                // VRHIP_OCC=2|3: waves per SIMD of the default marching kernels (0 = by volume)
+    int occ_force_split = 0;          // ... of phase 2 (VRHIP_OCC sets both, VRHIP_OCC_P1 / VRHIP_OCC_P2 one)
+    uint32_t ctrl_sel = 0;            // the block the next set of launches uses
+    bool ctrl_clean[2] = {false, false};   // that block is known to hold zeroes
+    bool phase_timing = false;        // vrhip_set_phase_timing: an event between the phases of a frame
+    int event_bind = 2;               // VRHIP_EVENT_BIND (launch_timed)
+    bool frame_timing = true;         // vrhip_set_frame_timing: events around a frame's launches (vrhip_last_kernel_seconds)
+    DevBuf<uint16_t> cost;            // per pixel: phase-2 rounds of the previous frame (sort key)
+    DevBuf<uint32_t> order;           // sorted permutation of the suspended rays
+    DevBuf<ContRec> live_rays;        // pre-pass output: live rays with their DDA state (phase 1's list)
+    bool ray_list = true;             // VRHIP_NO_RAYLIST=1: phase 1 walks the live patches instead
+    DevBuf<uint32_t> seeds_dev;       // kMaxBatchFrames jitter seeds of a batch of frames
+    DevBuf<vrhip_camera_params> cams_dev;   // kMaxBatchFrames cameras of a batch of per-frame views
+    DevBuf<> samples_dev;             // vrhip_render_samples: the records and marks of a set of samples (lazily, reused)
+    bool sort_cont = true;            // VRHIP_NO_SORT=1 disables
+    DevBuf<LiveTile> live;            // DDA pre-pass output: patches with rays that sample
+    bool prepass = true;              // VRHIP_NO_PREPASS=1 disables
+    DevBuf<ContRec> cont;             // suspended rays of the two-phase march
+    uint32_t round_budget = 10;       // phase-1 sample rounds per patch (0 = single phase)
+    uint32_t refill_min = 16;         // phase 2: idle ray slots per wave before a refill (VRHIP_REFILL_MIN)
+    std::vector<uint32_t> queue_key;   // W, H, tile_w, tile_h, tile ids...
+    // image-order ESS: ping-pong hit images (volumerendercl.cpp:482-488, :524-530) + per-frame scratch
+    DevBuf<uint8_t> hit_in, hit_out, hit_status, hit_any;
+    uint32_t hit_w = 0, hit_h = 0;
+    DevBuf<> fp;                      // footprint volume of the current time step (VolView::fp)
+    bool fp_valid = false;
+    uint32_t fp_timestep = 0;         // the time step `fp` was built for
+    uint32_t fp_candidate = 0xffffffffu, fp_candidate_frames = 0;   // time series: see ensure_footprint
+    bool fp_active = false;           // this frame reads it
+    const void *fp_use = nullptr;     // what this frame reads: the renderer's own `fp` or its owner's
+    vrhip_renderer *vol_owner = nullptr;   // vrhip_share_volumes: whose voxels (and footprint volume) this renderer renders from
+    std::vector<vrhip_renderer *> sharers; // the renderers that render from THIS one's voxels (their vol_owner is this)
+    size_t fp_failed_bytes = 0;       // a footprint allocation of this size failed: not retried until the volume or the cap changes
+    bool use_fp = true;               // VRHIP_NO_FOOTPRINT=1 disables
+    size_t fp_max_bytes = (size_t)96 << 30;   // VRHIP_FOOTPRINT_MAX_GB
+    DevBuf<float4> env;               // environment map (float RGBA), or empty
+    uint32_t env_w = 0, env_h = 0;
+
+    // device-side ingest (vrhip_ingest_raw, vrhip_volume_histogram): the running maximum and the 256 64-bit
+    // histogram counters in device memory, the events around its kernels (all created on first use)
+    size_t ingest_slab_bytes = (size_t)256 << 20;   // VRHIP_INGEST_SLAB_BYTES: staging per slab
+    DevBuf<> ingest_ws;
+    DevEvent evi0, evi1;
+    double ingest_seconds = 0.0;
+
+    DevEvent ev0, ev1, evm, evb0, evb1;
+    bool timed = false, bricks_timed = false, phase_timed = false;
+    vrhip_launch_info last_info;      // what the last render call launched (vrhip_last_launch_info)
+    bool have_info = false;
+
+    vrhip_renderer()
+    {
+        // defaults of volumerendercl.h:43-81
+        std::memset(&cam, 0, sizeof cam);
+        std::memset(&render, 0, sizeof render);
+        std::memset(&raycast, 0, sizeof raycast);
+        const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        std::memcpy(cam.viewMat, ident, sizeof ident);
+        for (int i = 0; i < 3; ++i) { cam.bbox_bl[i] = -1.f; cam.bbox_tr[i] = 1.f; }
+        for (int i = 0; i < 4; ++i) render.backgroundColor[i] = 1.f;
+        for (int i = 0; i < 3; ++i) render.modelScale[i] = 1.f;
+        render.illumType = 1;
+        render.useLinear = 1;
+        render.seed = 42;
+        raycast.samplingRate = 1.5f;
+        for (int i = 0; i < 3; ++i) raycast.brickRes[i] = 1.f;
+        pathtrace.max_extinction = 100.f;
+    }
+};
+
+// ---- errors
+
+inline std::string &create_error()   // what vrhip_last_error(NULL) answers: the last failed vrhip_create
+{
+    static std::string msg;
+    return msg;
+}
+
+inline int fail(const vrhip_renderer *r, int code, const std::string &msg)
+{
+    if (r) r->err = msg;
+    else create_error() = msg;
+    return code;
+}
+
+#define VR_HIP(r, call)                                                                       \
+    do {                                                                                      \
+        hipError_t e_ = (call);                                                               \
+        if (e_ != hipSuccess)                                                                 \
+            return fail(r, VRHIP_ERR_HIP,                                                     \
+                        std::string("ERROR: " #call " (") + hipGetErrorString(e_) + ")");     \
+    } while (0)
+
+#define VR_REQUIRE(r, cond, code, msg)                                                        \
+    do {                                                                                      \
+        if (!(cond)) return fail(r, code, msg);                                               \
+    } while (0)
+
+inline int set_device(const vrhip_renderer *r)
+{
+    VR_HIP(r, hipSetDevice(r->device));
+    return VRHIP_OK;
+}
+
+// ---- the one place that (re)allocates a buffer of a renderer
+
+enum : unsigned {
+    kGrowFresh = 1u,      // allocate anew whatever the capacity (the caller initialises the contents)
+    kGrowTolerate = 2u,   // an allocation failure is not an error: the buffer stays empty, nothing is reported
+};
+
+// `b` holds at least `bytes` afterwards.  Nothing happens when it does already; otherwise the renderer's stream
+// is waited for (it may be using the old allocation), the old one is freed and a new one made.  On failure the
+// buffer is empty.
+template <class T>
+int grow(vrhip_renderer *r, DevBuf<T> &b, size_t bytes, unsigned flags = 0)
+{
+    if (!(flags & kGrowFresh) && b.p && bytes <= b.bytes) return VRHIP_OK;
+    VR_HIP(r, hipStreamSynchronize(r->stream));
+    b.release();
+    const hipError_t e = hipMalloc((void **)&b.p, bytes);
+    if (e != hipSuccess) {
+        b.p = nullptr;
+        if (flags & kGrowTolerate) {
+            (void)hipGetLastError();
+            return VRHIP_OK;
+        }
+        return fail(r, VRHIP_ERR_HIP, std::string("ERROR: hipMalloc of ") + std::to_string(bytes) + " bytes (" +
+                                          hipGetErrorString(e) + ")");
+    }
+    b.bytes = bytes;
+    return VRHIP_OK;
+}
+
+// ---- views of the renderer's state for the launchers (vr_internal.h)
+
+inline size_t fmt_bytes(int format) { return format == VRHIP_UCHAR ? 1 : format == VRHIP_USHORT ? 2 : 4; }
+
+inline float inv_max_of(int format)
+{
+    return format == VRHIP_UCHAR ? 1.0f / 255.0f : format == VRHIP_USHORT ? 1.0f / 65535.0f : 1.0f;
+}
+
+inline VolView make_vol_view(const vrhip_renderer *r, const void *data)
+{
+    VolView v;
+    v.data = data;
+    v.w = (int)r->res[0]; v.h = (int)r->res[1]; v.d = (int)r->res[2];
+    v.fw = (float)v.w; v.fh = (float)v.h; v.fd = (float)v.d;
+    v.inv_max = inv_max_of(r->format);
+    v.nbx = r->nb[0];
+    v.nby = r->nb[1];
+    v.nbz = r->nb[2];
+    v.ystride = r->nb[0] * 64u;
+    v.zstride = (unsigned long long)r->nb[0] * r->nb[1] * 64ull;
+    v.chan[0] = v.chan[1] = v.chan[2] = nullptr;
+    v.channels = 1;
+    v.fp = nullptr;
+    v.fp_nbx = (r->res[0] + 4u) >> 2;
+    v.fp_nby = (r->res[1] + 4u) >> 2;
+    return v;
+}
+
+// the render view of a time step: all channels
+inline VolView make_render_view(const vrhip_renderer *r, const VolumeSlot &s)
+{
+    VolView v = make_vol_view(r, s.dev);
+    for (int i = 0; i < 3; ++i) v.chan[i] = s.chan[i];
+    v.channels = r->channels;
+    v.fp = r->fp_active ? r->fp_use : nullptr;
+    return v;
+}
+
+inline BrickView make_brick_view(const vrhip_renderer *r, const void *data)
+{
+    BrickView b;
+    b.data = data;
+    b.bw = (int)r->brick_tex[0];
+    b.bh = (int)r->brick_tex[1];
+    b.bd = (int)r->brick_tex[2];
+    return b;
+}
+
+inline TfView make_tf_view(const vrhip_renderer *r)
+{
+    TfView t;
+    t.tff = r->tff;
+    t.tff_n = r->tff_n;
+    t.prefix = r->prefix;
+    t.prefix_n = r->prefix_n;
+    return t;
+}
+
+// (re)allocate a slot for `timestep`, checking that res/format agree with other timesteps (vrhip_api.hip)
+int prepare_slot(vrhip_renderer *r, const uint32_t res[3], int format, uint32_t timestep, VolumeSlot **slot,
+                 int channels = 1);
+
+// ---- derived state: what is built lazily from what, and what makes it stale
+//
+//   derived                                          | built by            | depends on
+//   -------------------------------------------------+---------------------+-----------------------------------------
+//   bricks of a slot (bricks_built)                  | vrhip_build_bricks  | that slot's voxels
+//   bricks_valid, brick geometry                     | vrhip_build_bricks  | resolution; a build since the last voxel
+//                                                    |                     | change of ANY slot (a sharer: its owner's)
+//   skip bitmap + near bits (skip_dirty,             | ensure_skipmap      | bricks of the current step, TF, prefix
+//     skip_version)                                  |                     | sum, current step
+//   cell (min,max) of a slot, coarse and fine        | ensure_cells        | that slot's voxels
+//     (pt_minmax_valid, fine_minmax_valid)           |                     |
+//   opacity bounds / macro bounds / leap radii,      | ensure_cells        | cell (min,max) of the current step, TF,
+//     empty bits (cells_have_bound / _empty)         |                     | current step
+//   footprint volume (fp_valid, fp_timestep;         | ensure_footprint    | voxels of the current step, current step
+//     fp_failed_bytes: a size not to try again)      |                     | (fp_failed_bytes: any new voxels)
+//   patch classes                                    | ensure_patch_classes| their byte key (patch_class_key), which
+//                                                    |                     | holds skip_version and queue_version
+//
+// A voxel write into ANY slot makes the renderer-wide tables stale, not only one into the current step (the code
+// never looked at which).  fp_candidate / fp_candidate_frames count frames, and survive everything but a change
+// of the step shown.  Mutation sites call one of the functions below and assign none of these members themselves;
+// the ensure_* functions record what they built with the *_built functions.
+
+inline void cells_tables_stale(vrhip_renderer *r) { r->cells_have_bound = r->cells_have_empty = false; }
+
+// the voxels of time step `t` were (or are about to be) written: `r` and the renderers that share its volumes
+inline void voxels_written(vrhip_renderer *r, uint32_t t)
+{
+    auto one = [t](vrhip_renderer *x) {
+        if (t < x->vols.size()) {
+            VolumeSlot &s = x->vols[t];
+            s.bricks_built = s.pt_minmax_valid = s.fine_minmax_valid = false;
+        }
+        x->bricks_valid = false;
+        x->skip_dirty = true;
+        cells_tables_stale(x);
+        x->fp_valid = false;
+        x->fp_failed_bytes = 0;
+    };
+    one(r);
+    for (vrhip_renderer *sh : r->sharers) one(sh);
+}
+
+// every slot is gone (their own flags with them)
+inline void volumes_cleared(vrhip_renderer *r)
+{
+    r->bricks_valid = false;
+    r->skip_dirty = true;
+    cells_tables_stale(r);
+    r->fp_valid = false;
+    r->fp_failed_bytes = 0;
+}
+
+// the slots now point into `owner`'s, bricks included (after volumes_cleared)
+inline void volumes_shared(vrhip_renderer *r, const vrhip_renderer *owner)
+{
+    r->bricks_valid = owner->bricks_valid;
+    r->skip_dirty = true;
+    cells_tables_stale(r);
+    r->fp_valid = false;   // (its own footprint volume is not used while it shares: ensure_footprint)
+}
+
+inline void timestep_changed(vrhip_renderer *r)
+{
+    r->skip_dirty = true;
+    cells_tables_stale(r);
+    r->fp_valid = false;
+}
+
+// transfer function or its prefix sum
+inline void tf_changed(vrhip_renderer *r)
+{
+    r->skip_dirty = true;
+    cells_tables_stale(r);
+}
+
+// vrhip_build_bricks has run: every slot's bricks match its voxels
+inline void bricks_built(vrhip_renderer *r)
+{
+    r->bricks_valid = true;
+    r->skip_dirty = true;
+    cells_tables_stale(r);
+}
+
+inline void slot_bricks_built(VolumeSlot &s) { s.bricks_built = true; }
+inline void cell_minmax_built(VolumeSlot &s, bool fine) { (fine ? s.fine_minmax_valid : s.pt_minmax_valid) = true; }
+inline void cells_tables_built(vrhip_renderer *r, bool bound, bool empty)
+{
+    r->cells_have_bound = r->cells_have_bound || bound;
+    r->cells_have_empty = r->cells_have_empty || empty;
+}
+inline void skipmap_built(vrhip_renderer *r) { r->skip_dirty = false; ++r->skip_version; }
+inline void footprint_stale(vrhip_renderer *r) { r->fp_valid = false; }   // about to be overwritten
+inline void footprint_alloc_failed(vrhip_renderer *r, size_t bytes) { r->fp_failed_bytes = bytes; }
+inline void footprint_built(vrhip_renderer *r) { r->fp_valid = true; r->fp_timestep = r->timestep; }
+
+#endif

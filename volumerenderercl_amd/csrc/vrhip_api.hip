@@ -11,24 +11,9 @@
 #include <string>
 #include <vector>
 
-#include "vr_internal.h"
-#include "vr_ingest.h"
+#include "vr_renderer.h"
 
 namespace {
-
-struct VolumeSlot {
-    void *dev = nullptr;      // micro-bricked voxels (channel 0 of a multi-channel volume)
-    void *chan[3] = {nullptr, nullptr, nullptr};   // channels 1..3 of CL_RG / CL_RGBA volumes
-    void *bricks = nullptr;   // (min,max) grid
-    bool bricks_built = false;   // `bricks` holds the (min,max) of the voxels now in `dev`
-    float2 *pt_minmax = nullptr;   // path tracer: per-cell (min,max) incl. halo, built on demand
-    bool pt_minmax_valid = false;
-    float2 *fine_minmax = nullptr; // ray caster: the same on the finer grid of the empty bits
-    bool fine_minmax_valid = false;
-    bool borrowed = false;    // dev / chan / bricks belong to another renderer (vrhip_share_volumes)
-};
-
-std::string g_create_error;
 
 constexpr uint32_t kSkipLdsMaxBytes = 64 * 1024;   // bitmap staged in LDS up to this size
 // vrhip_render_samples: samples per launch set when the caller leaves it open -- the best of the sweep in DESIGN.md
@@ -36,182 +21,6 @@ constexpr uint32_t kSkipLdsMaxBytes = 64 * 1024;   // bitmap staged in LDS up to
 // ran with (64 samples of 1024^2 pixels, 17 bytes each: 1.06 GiB); a caller that names a set size gets it
 constexpr uint32_t kDefaultSamplesPerLaunch = 64;
 constexpr unsigned long long kDefaultSampleRecords = 64ull << 20;
-
-} // namespace
-
-struct vrhip_renderer {
-    int device = 0;
-    int num_cus = 256;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    mutable std::string err;
-    std::string devname;
-
-    uint32_t res[3] = {0, 0, 0};
-    int format = -1;
-    int channels = 1;                 // 1 = CL_R, 2 = CL_RG, 4 = CL_RGBA
-    // HBM layout of a time step: 4x4x4-voxel micro-bricks (vr_internal.h, DESIGN.md "Data
-    // layout"); nb = ceil(res / 4)
-    uint32_t nb[3] = {0, 0, 0};
-    std::vector<VolumeSlot> vols;
-    uint32_t timestep = 0;
-
-    float4 *tff = nullptr;
-    uint32_t tff_n = 0;
-    uint32_t *prefix = nullptr;
-    uint32_t prefix_n = 0;
-
-    uint32_t brick_tex[3] = {0, 0, 0}, brick_edge[3] = {0, 0, 0};
-    float brick_res[3] = {1, 1, 1};
-    bool bricks_valid = false;
-
-    // ESS skip bitmap of the current timestep (derived from bricks + TF + prefix)
-    uint32_t *skip_bits = nullptr;
-    uint32_t skip_words = 0, skip_cap = 0;
-    bool skip_dirty = true;
-    // patch culling of the DDA pre-pass: the skip bitmap dilated by cull_radius bricks (SkipView::near_bits)
-    uint32_t *near_bits = nullptr;
-    uint8_t *near_scratch = nullptr;
-    uint32_t cull_radius = 4;         // VRHIP_CULL_RADIUS (bricks; 0 = no patch culling)
-
-    // cell grid of the current timestep + TF (CellView, vr_internal.h): opacity bound for the
-    // path tracer, empty bits for the ray caster
-    CellView cells = {nullptr, nullptr, 0, 0, 0, 3, 0, 0, 0, 3};
-    float *cell_bound = nullptr;
-    uint32_t *cell_empty = nullptr;
-    float *cell_sparse = nullptr;  // 13 x 4096 floats of scratch for the TF range-max table
-    size_t cell_cap = 0, empty_cap = 0;
-    bool cells_have_bound = false, cells_have_empty = false;   // r->cells' tables match volume, time step and TF
-    bool pt_dirty = true;          // cells out of date (volume, timestep or TF changed)
-    bool pt_cull = true;           // VRHIP_PT_NO_CULL=1 disables the path tracer's culling
-    bool pt_leap = true;           // VRHIP_PT_NO_LEAP=1: no leaps over macro cells (A/B)
-    bool pt_leap_far = true;       // VRHIP_PT_NO_FAR_LEAP=1: leaps stay inside one macro cell (A/B)
-    uint8_t *cell_dist = nullptr;  // CellView::cdist (two buffers)
-    const uint8_t *cell_dist_table = nullptr;
-    size_t cell_dist_cap = 0;
-    bool skip_empty = true;        // VRHIP_NO_EMPTY_SKIP=1 disables the ray caster's empty runs
-    bool skip_empty_force = false; // VRHIP_EMPTY_SKIP=1: also where it is not expected to pay (see ray_skip_empty)
-
-    vrhip_camera_params cam;
-    vrhip_rendering_params render;
-    vrhip_raycast_params raycast;
-    vrhip_pathtrace_params pathtrace;
-    bool use_ess = true;
-
-    float4 *fb = nullptr;
-    uint32_t fb_w = 0, fb_h = 0;
-
-    DevStats *stats_dev = nullptr;
-    bool stats_enabled = false;
-
-    // work queue of 8x8 wave tiles (centre first) for the current frame/tile set
-    WaveTile *queue_dev = nullptr;
-    uint32_t queue_n = 0, queue_cap = 0;
-    uint32_t *queue_head = nullptr;   // 2 x kControlWords (queue head, cont count, cont head, pad, sort bins + cursors):
-                                      // the sets of launches alternate between the two blocks (FrameView::next_ctrl)
-    uint8_t *patch_class = nullptr;   // FrameView::patch_class of the current queue, camera, parameters and skip bitmaps
-    size_t patch_class_cap = 0;
-    std::vector<uint8_t> patch_class_key;   // what the classes were computed for (empty: nothing valid)
-    uint32_t skip_version = 0;        // bumped whenever the skip bitmaps are rebuilt
-    uint32_t queue_version = 0;       // bumped whenever the work queue is rebuilt
-    uint32_t queue_frames = 1;        // frames per set of the current queue
-    bool use_patch_classes = true;    // VRHIP_NO_PATCH_CLASS=1 disables
-    int occ_force = 0;                // VRHIP_OCC=2|3: waves per SIMD of the default marching kernels (0 = by volume)
-    int occ_force_split = 0;          // ... of phase 2 (VRHIP_OCC sets both, VRHIP_OCC_P1 / VRHIP_OCC_P2 one)
-    uint32_t ctrl_sel = 0;            // the block the next set of launches uses
-    bool ctrl_clean[2] = {false, false};   // that block is known to hold zeroes
-    bool phase_timing = false;        // vrhip_set_phase_timing: an event between the phases of a frame
-    int event_bind = 2;               // VRHIP_EVENT_BIND (launch_timed)
-    bool frame_timing = true;         // vrhip_set_frame_timing: events around a frame's launches (vrhip_last_kernel_seconds)
-    uint16_t *cost = nullptr;         // per pixel: phase-2 rounds of the previous frame (sort key)
-    uint32_t *order = nullptr;        // sorted permutation of the suspended rays
-    ContRec *live_rays = nullptr;     // pre-pass output: live rays with their DDA state (phase 1's list)
-    bool ray_list = true;             // VRHIP_NO_RAYLIST=1: phase 1 walks the live patches instead
-    uint32_t *seeds_dev = nullptr;    // kMaxBatchFrames jitter seeds of a batch of frames
-    vrhip_camera_params *cams_dev = nullptr;   // kMaxBatchFrames cameras of a batch of per-frame views
-    void *samples_dev = nullptr;      // vrhip_render_samples: the records and marks of a set of samples (lazily, reused)
-    size_t samples_cap = 0;           // bytes
-    bool sort_cont = true;            // VRHIP_NO_SORT=1 disables
-    LiveTile *live = nullptr;         // DDA pre-pass output: patches with rays that sample
-    bool prepass = true;              // VRHIP_NO_PREPASS=1 disables
-    ContRec *cont = nullptr;          // suspended rays of the two-phase march
-    size_t cont_cap = 0;
-    uint32_t round_budget = 10;       // phase-1 sample rounds per patch (0 = single phase)
-    uint32_t refill_min = 16;         // phase 2: idle ray slots per wave before a refill (VRHIP_REFILL_MIN)
-    std::vector<uint32_t> queue_key;   // W, H, tile_w, tile_h, tile ids...
-    // image-order ESS: ping-pong hit images (volumerendercl.cpp:482-488, :524-530) + per-frame scratch
-    uint8_t *hit_in = nullptr, *hit_out = nullptr, *hit_status = nullptr, *hit_any = nullptr;
-    uint32_t hit_w = 0, hit_h = 0;
-    void *fp = nullptr;               // footprint volume of the current time step (VolView::fp)
-    size_t fp_cap = 0;                // bytes allocated
-    bool fp_valid = false;
-    uint32_t fp_timestep = 0;         // the time step `fp` was built for
-    uint32_t fp_candidate = 0xffffffffu, fp_candidate_frames = 0;   // time series: see ensure_footprint
-    bool fp_active = false;           // this frame reads it
-    const void *fp_use = nullptr;     // what this frame reads: the renderer's own `fp` or its owner's
-    vrhip_renderer *vol_owner = nullptr;   // vrhip_share_volumes: whose voxels (and footprint volume) this renderer renders from
-    std::vector<vrhip_renderer *> sharers; // the renderers that render from THIS one's voxels (their vol_owner is this)
-    size_t fp_failed_bytes = 0;       // a footprint allocation of this size failed: not retried until the volume or the cap changes
-    bool use_fp = true;               // VRHIP_NO_FOOTPRINT=1 disables
-    size_t fp_max_bytes = (size_t)96 << 30;   // VRHIP_FOOTPRINT_MAX_GB
-    float4 *env = nullptr;            // environment map (float RGBA), or nullptr
-    uint32_t env_w = 0, env_h = 0;
-
-    // device-side ingest (vrhip_ingest_raw, vrhip_volume_histogram): the running maximum and the 256 64-bit
-    // histogram counters in device memory, the events around its kernels (all created on first use)
-    size_t ingest_slab_bytes = (size_t)256 << 20;   // VRHIP_INGEST_SLAB_BYTES: staging per slab
-    void *ingest_ws = nullptr;
-    hipEvent_t evi0 = nullptr, evi1 = nullptr;
-    double ingest_seconds = 0.0;
-
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, evm = nullptr, evb0 = nullptr, evb1 = nullptr;
-    bool timed = false, bricks_timed = false, phase_timed = false;
-    vrhip_launch_info last_info;      // what the last render call launched (vrhip_last_launch_info)
-    bool have_info = false;
-
-    vrhip_renderer()
-    {
-        // defaults of volumerendercl.h:43-81
-        std::memset(&cam, 0, sizeof cam);
-        std::memset(&render, 0, sizeof render);
-        std::memset(&raycast, 0, sizeof raycast);
-        const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-        std::memcpy(cam.viewMat, ident, sizeof ident);
-        for (int i = 0; i < 3; ++i) { cam.bbox_bl[i] = -1.f; cam.bbox_tr[i] = 1.f; }
-        for (int i = 0; i < 4; ++i) render.backgroundColor[i] = 1.f;
-        for (int i = 0; i < 3; ++i) render.modelScale[i] = 1.f;
-        render.illumType = 1;
-        render.useLinear = 1;
-        render.seed = 42;
-        raycast.samplingRate = 1.5f;
-        for (int i = 0; i < 3; ++i) raycast.brickRes[i] = 1.f;
-        pathtrace.max_extinction = 100.f;
-    }
-};
-
-namespace {
-
-int fail(const vrhip_renderer *r, int code, const std::string &msg)
-{
-    if (r) r->err = msg;
-    else g_create_error = msg;
-    return code;
-}
-
-#define VR_HIP(r, call)                                                                       \
-    do {                                                                                      \
-        hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(r, VRHIP_ERR_HIP,                                                     \
-                        std::string("ERROR: " #call " (") + hipGetErrorString(e_) + ")");     \
-    } while (0)
-
-#define VR_REQUIRE(r, cond, code, msg)                                                        \
-    do {                                                                                      \
-        if (!(cond)) return fail(r, code, msg);                                               \
-    } while (0)
-
-size_t fmt_bytes(int format) { return format == VRHIP_UCHAR ? 1 : format == VRHIP_USHORT ? 2 : 4; }
 
 size_t volume_bytes(const vrhip_renderer *r)   // dense (host-side) size
 {
@@ -227,8 +36,6 @@ void set_layout(vrhip_renderer *r)
 {
     for (int i = 0; i < 3; ++i) r->nb[i] = (r->res[i] + 3) / 4;
 }
-
-VolView make_vol_view(const vrhip_renderer *r, const void *data);
 
 // Dense x-fastest array (host memory, or device memory when dense_is_device) <-> micro-bricks,
 // slab by slab (multiples of 4 slices) through a bounded device staging buffer.
@@ -283,61 +90,6 @@ uint32_t round_pow2(uint32_t n)
     return (val - n) > (n - x) ? x : val;
 }
 
-float inv_max_of(int format)
-{
-    return format == VRHIP_UCHAR ? 1.0f / 255.0f : format == VRHIP_USHORT ? 1.0f / 65535.0f : 1.0f;
-}
-
-VolView make_vol_view(const vrhip_renderer *r, const void *data)
-{
-    VolView v;
-    v.data = data;
-    v.w = (int)r->res[0]; v.h = (int)r->res[1]; v.d = (int)r->res[2];
-    v.fw = (float)v.w; v.fh = (float)v.h; v.fd = (float)v.d;
-    v.inv_max = inv_max_of(r->format);
-    v.nbx = r->nb[0];
-    v.nby = r->nb[1];
-    v.nbz = r->nb[2];
-    v.ystride = r->nb[0] * 64u;
-    v.zstride = (unsigned long long)r->nb[0] * r->nb[1] * 64ull;
-    v.chan[0] = v.chan[1] = v.chan[2] = nullptr;
-    v.channels = 1;
-    v.fp = nullptr;
-    v.fp_nbx = (r->res[0] + 4u) >> 2;
-    v.fp_nby = (r->res[1] + 4u) >> 2;
-    return v;
-}
-
-// the render view of a time step: all channels
-VolView make_render_view(const vrhip_renderer *r, const VolumeSlot &s)
-{
-    VolView v = make_vol_view(r, s.dev);
-    for (int i = 0; i < 3; ++i) v.chan[i] = s.chan[i];
-    v.channels = r->channels;
-    v.fp = r->fp_active ? r->fp_use : nullptr;
-    return v;
-}
-
-BrickView make_brick_view(const vrhip_renderer *r, const void *data)
-{
-    BrickView b;
-    b.data = data;
-    b.bw = (int)r->brick_tex[0];
-    b.bh = (int)r->brick_tex[1];
-    b.bd = (int)r->brick_tex[2];
-    return b;
-}
-
-TfView make_tf_view(const vrhip_renderer *r)
-{
-    TfView t;
-    t.tff = r->tff;
-    t.tff_n = r->tff_n;
-    t.prefix = r->prefix;
-    t.prefix_n = r->prefix_n;
-    return t;
-}
-
 // log2 of the cell edges of the two cell grids (CellView): opacity bounds on at most 256 cells per axis,
 // empty bits on at most 512 (edges 8 and 4 up to 2048^3)
 void cell_shifts(const vrhip_renderer *r, int *shift, int *eshift)
@@ -365,12 +117,6 @@ bool ray_skip_empty(const vrhip_renderer *r)
     return std::max(r->brick_edge[0], std::max(r->brick_edge[1], r->brick_edge[2])) >= (4u << eshift);
 }
 
-int set_device(const vrhip_renderer *r)
-{
-    VR_HIP(r, hipSetDevice(r->device));
-    return VRHIP_OK;
-}
-
 // Sharers of `owner` lose their (borrowed) volumes: nothing of theirs points into the owner any more.
 void detach_sharers(vrhip_renderer *owner)
 {
@@ -382,9 +128,11 @@ void detach_sharers(vrhip_renderer *owner)
     }
 }
 
+} // namespace
+
 // (re)allocate a slot for `timestep`, checking that res/format agree with other timesteps
 int prepare_slot(vrhip_renderer *r, const uint32_t res[3], int format, uint32_t timestep,
-                 VolumeSlot **slot, int channels = 1)
+                 VolumeSlot **slot, int channels)
 {
     VR_REQUIRE(r, res && res[0] && res[1] && res[2], VRHIP_ERR_INVALID,
                "Volume resolution must be non-zero.");
@@ -411,46 +159,29 @@ int prepare_slot(vrhip_renderer *r, const uint32_t res[3], int format, uint32_t 
     // they are detached (they report "No volume data is loaded." until they share again).
     if (!r->sharers.empty()) {
         if (r->vols.size() <= timestep || !r->vols[timestep].dev) detach_sharers(r);
-        for (vrhip_renderer *sh : r->sharers) {
-            VR_HIP(r, hipStreamSynchronize(sh->stream));
-            sh->skip_dirty = true;
-            sh->pt_dirty = true;
-            sh->cells_have_bound = sh->cells_have_empty = false;
-            sh->bricks_valid = false;
-            if (timestep < sh->vols.size()) {
-                sh->vols[timestep].pt_minmax_valid = false;
-                sh->vols[timestep].fine_minmax_valid = false;
-            }
-        }
+        for (vrhip_renderer *sh : r->sharers) VR_HIP(r, hipStreamSynchronize(sh->stream));
     }
     if (r->vols.size() <= timestep) r->vols.resize(timestep + 1);
     VolumeSlot &s = r->vols[timestep];
-    if (!s.dev) VR_HIP(r, hipMalloc(&s.dev, volume_alloc_bytes(r)));
-    for (int c = 1; c < channels; ++c)
-        if (!s.chan[c - 1]) VR_HIP(r, hipMalloc(&s.chan[c - 1], volume_alloc_bytes(r)));
-    r->bricks_valid = false;
-    s.bricks_built = false;
-    r->skip_dirty = true;
-    r->pt_dirty = true;
-    r->fp_valid = false;
-    r->fp_failed_bytes = 0;
-    s.pt_minmax_valid = false;
-    s.fine_minmax_valid = false;
+    int rc = grow(r, s.dev, volume_alloc_bytes(r));
+    for (int c = 1; c < channels && !rc; ++c) rc = grow(r, s.chan[c - 1], volume_alloc_bytes(r));
+    if (rc) return rc;
+    voxels_written(r, timestep);
     *slot = &s;
     return VRHIP_OK;
 }
 
+namespace {
+
 int ensure_fb(vrhip_renderer *r, uint32_t w, uint32_t h)
 {
     if (r->fb && r->fb_w == w && r->fb_h == h) return VRHIP_OK;
-    VR_HIP(r, hipStreamSynchronize(r->stream));
-    if (r->fb) VR_HIP(r, hipFree(r->fb));
-    r->fb = nullptr;
-    VR_HIP(r, hipMalloc((void **)&r->fb, (size_t)w * h * sizeof(float4)));
+    // a frame of another size starts from zeroes: the frame buffer accumulates, the cost map holds sort keys
+    r->fb_w = r->fb_h = 0;
+    int rc = grow(r, r->fb, (size_t)w * h * sizeof(float4), kGrowFresh);
+    if (rc) return rc;
     VR_HIP(r, hipMemsetAsync(r->fb, 0, (size_t)w * h * sizeof(float4), r->stream));
-    if (r->cost) VR_HIP(r, hipFree(r->cost));
-    r->cost = nullptr;
-    VR_HIP(r, hipMalloc((void **)&r->cost, (size_t)w * h * sizeof(uint16_t)));
+    if ((rc = grow(r, r->cost, (size_t)w * h * sizeof(uint16_t), kGrowFresh))) return rc;
     VR_HIP(r, hipMemsetAsync(r->cost, 0, (size_t)w * h * sizeof(uint16_t), r->stream));
     r->fb_w = w;
     r->fb_h = h;
@@ -493,15 +224,11 @@ int ensure_hit_images(vrhip_renderer *r, uint32_t w, uint32_t h)
 {
     const uint32_t hw = w / 8u + 1u, hh = h / 8u + 1u;
     if (r->hit_in && r->hit_w == hw && r->hit_h == hh) return VRHIP_OK;
-    VR_HIP(r, hipStreamSynchronize(r->stream));
-    for (uint8_t **p : {&r->hit_in, &r->hit_out, &r->hit_status, &r->hit_any}) {
-        if (*p) VR_HIP(r, hipFree(*p));
-        *p = nullptr;
-    }
     r->hit_w = r->hit_h = 0;
     const size_t n = (size_t)hw * hh;
-    for (uint8_t **p : {&r->hit_in, &r->hit_out, &r->hit_status, &r->hit_any}) {
-        VR_HIP(r, hipMalloc((void **)p, n));
+    for (DevBuf<uint8_t> *p : {&r->hit_in, &r->hit_out, &r->hit_status, &r->hit_any}) {
+        int rc = grow(r, *p, n, kGrowFresh);
+        if (rc) return rc;
         VR_HIP(r, hipMemset(*p, 0, n));
     }
     std::vector<uint8_t> init(n, 0);
@@ -554,28 +281,18 @@ int ensure_footprint(vrhip_renderer *r)
         // renderers that share this one's volumes may be reading the old one on their own streams
         if (r->fp)
             for (vrhip_renderer *sh : r->sharers) VR_HIP(r, hipStreamSynchronize(sh->stream));
-        r->fp_valid = false;
-        if (bytes > r->fp_cap) {
-            if (r->fp) {
-                VR_HIP(r, hipStreamSynchronize(r->stream));
-                VR_HIP(r, hipFree(r->fp));
-            }
-            r->fp = nullptr;
-            r->fp_cap = 0;
-            if (hipMalloc(&r->fp, bytes) != hipSuccess) {   // not enough HBM left: plain layout
-                (void)hipGetLastError();
-                r->fp = nullptr;
-                r->fp_failed_bytes = bytes;   // (reset by a new volume or a new cap)
-                return VRHIP_OK;
-            }
-            r->fp_cap = bytes;
+        footprint_stale(r);
+        const int rc = grow(r, r->fp, bytes, kGrowTolerate);
+        if (rc) return rc;
+        if (!r->fp) {   // not enough HBM left: plain layout
+            footprint_alloc_failed(r, bytes);
+            return VRHIP_OK;
         }
         VolView fv = v;
         fv.fp = r->fp;
         VR_HIP(r, vr_launch_build_footprint(fv, r->format, r->stream));
         VR_HIP(r, hipStreamSynchronize(r->stream));   // sharers render on other streams
-        r->fp_valid = true;
-        r->fp_timestep = r->timestep;
+        footprint_built(r);
     }
     r->fp_use = r->fp;
     r->fp_active = true;
@@ -588,19 +305,10 @@ int ensure_skipmap(vrhip_renderer *r)
     if (!r->use_ess || !r->skip_dirty) return VRHIP_OK;
     const size_t n = (size_t)r->brick_tex[0] * r->brick_tex[1] * r->brick_tex[2];
     const uint32_t words = (uint32_t)(2 * ((n + 63) / 64));
-    if (words + 1 > r->skip_cap) {
-        VR_HIP(r, hipStreamSynchronize(r->stream));
-        if (r->skip_bits) VR_HIP(r, hipFree(r->skip_bits));
-        r->skip_bits = nullptr;
-        VR_HIP(r, hipMalloc((void **)&r->skip_bits, ((size_t)words + 1) * sizeof(uint32_t)));
-        if (r->near_bits) VR_HIP(r, hipFree(r->near_bits));
-        if (r->near_scratch) VR_HIP(r, hipFree(r->near_scratch));
-        r->near_bits = nullptr;
-        r->near_scratch = nullptr;
-        VR_HIP(r, hipMalloc((void **)&r->near_bits, ((size_t)words + 1) * sizeof(uint32_t)));
-        VR_HIP(r, hipMalloc((void **)&r->near_scratch, 2 * n));
-        r->skip_cap = words + 1;
-    }
+    int rc = grow(r, r->skip_bits, ((size_t)words + 1) * sizeof(uint32_t));
+    if (!rc) rc = grow(r, r->near_bits, ((size_t)words + 1) * sizeof(uint32_t));
+    if (!rc) rc = grow(r, r->near_scratch, 2 * n);
+    if (rc) return rc;
     r->skip_words = words;
     VR_HIP(r, vr_launch_skipmap(make_brick_view(r, r->vols[r->timestep].bricks), r->format,
                                 inv_max_of(r->format), make_tf_view(r), r->skip_bits, words,
@@ -608,8 +316,7 @@ int ensure_skipmap(vrhip_renderer *r)
     if (r->cull_radius)
         VR_HIP(r, vr_launch_skip_near(make_brick_view(r, r->vols[r->timestep].bricks), r->skip_bits, words,
                                       r->cull_radius, r->near_scratch, r->near_bits, r->stream));
-    r->skip_dirty = false;
-    ++r->skip_version;
+    skipmap_built(r);
     return VRHIP_OK;
 }
 
@@ -619,18 +326,15 @@ static int build_cell_minmax(vrhip_renderer *r, VolumeSlot &s, const CellView &g
 {
     // scratch for the separable build (one (min, max) per cell column and voxel slice), held only
     // while it runs
-    void *records = nullptr;
+    DevBuf<> records;   // (without it -- the allocation may fail -- the kernels that need none)
     const size_t n_rec = (size_t)g.cx * g.cy * r->res[2];
     if (g.shift <= 4 && r->nb[0] <= 1600u && !getenv("VRHIP_CELLS_PER_WAVE") &&
-        hipMalloc(&records, n_rec * vr_cell_record_bytes(r->format)) != hipSuccess) {
+        hipMalloc((void **)&records.p, n_rec * vr_cell_record_bytes(r->format)) != hipSuccess) {
         (void)hipGetLastError();
-        records = nullptr;
+        records.p = nullptr;
     }
     hipError_t e = vr_launch_cell_minmax(make_vol_view(r, s.dev), r->format, g, out, r->stream, records);
-    if (records) {
-        if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
-        (void)hipFree(records);
-    }
+    if (records && e == hipSuccess) e = hipStreamSynchronize(r->stream);
     VR_HIP(r, e);
     return VRHIP_OK;
 }
@@ -641,10 +345,6 @@ static int build_cell_minmax(vrhip_renderer *r, VolumeSlot &s, const CellView &g
 // shift 2 up to 2048^3, 16 MiB of bits).
 int ensure_cells(vrhip_renderer *r, bool need_bound, bool need_empty)
 {
-    if (r->pt_dirty) {
-        r->cells_have_bound = r->cells_have_empty = false;
-        r->pt_dirty = false;
-    }
     if ((!need_bound || r->cells_have_bound) && (!need_empty || r->cells_have_empty)) return VRHIP_OK;
     VolumeSlot &s = r->vols[r->timestep];
     int shift, eshift;
@@ -661,7 +361,8 @@ int ensure_cells(vrhip_renderer *r, bool need_bound, bool need_empty)
     const size_t n_cells = (size_t)g.cx * g.cy * g.cz, n_fine = (size_t)g.ecx * g.ecy * g.ecz;
     CellView fine = g;   // the fine grid's geometry for the kernels that take one grid
     fine.shift = eshift; fine.cx = g.ecx; fine.cy = g.ecy; fine.cz = g.ecz;
-    if (!r->cell_sparse) VR_HIP(r, hipMalloc((void **)&r->cell_sparse, 13 * 4096 * sizeof(float)));
+    int rc = grow(r, r->cell_sparse, 13 * 4096 * sizeof(float));
+    if (rc) return rc;
 
     // ---- (min, max) per cell: a property of the voxels, kept per time step.  A renderer that shares
     // another one's voxels (vrhip_share_volumes) reads the owner's tables where the owner has built them.
@@ -678,21 +379,19 @@ int ensure_cells(vrhip_renderer *r, bool need_bound, bool need_empty)
         }
     }
     if (need_empty && !one_grid && !s.fine_minmax_valid && !fine_mm) {
-        if (!s.fine_minmax) VR_HIP(r, hipMalloc((void **)&s.fine_minmax, n_fine * sizeof(float2)));
-        int rc = build_cell_minmax(r, s, fine, s.fine_minmax);
-        if (rc) return rc;
-        s.fine_minmax_valid = true;
+        if ((rc = grow(r, s.fine_minmax, n_fine * sizeof(float2)))) return rc;
+        if ((rc = build_cell_minmax(r, s, fine, s.fine_minmax))) return rc;
+        cell_minmax_built(s, true);
     }
     if (s.fine_minmax_valid) fine_mm = s.fine_minmax;
     if ((need_bound || one_grid) && !s.pt_minmax_valid && !coarse_mm) {
-        if (!s.pt_minmax) VR_HIP(r, hipMalloc((void **)&s.pt_minmax, n_cells * sizeof(float2)));
+        if ((rc = grow(r, s.pt_minmax, n_cells * sizeof(float2)))) return rc;
         if (fine_mm && !one_grid) {
             VR_HIP(r, vr_launch_cell_reduce(fine_mm, g, s.pt_minmax, r->stream));
-        } else {
-            int rc = build_cell_minmax(r, s, g, s.pt_minmax);
-            if (rc) return rc;
+        } else if ((rc = build_cell_minmax(r, s, g, s.pt_minmax))) {
+            return rc;
         }
-        s.pt_minmax_valid = true;
+        cell_minmax_built(s, false);
     }
     if (s.pt_minmax_valid) coarse_mm = s.pt_minmax;
 
@@ -703,45 +402,24 @@ int ensure_cells(vrhip_renderer *r, bool need_bound, bool need_empty)
     g.ccz = (g.cz + (1 << kLeapShift) - 1) >> kLeapShift;
     const size_t n_macro = (size_t)g.ccx * g.ccy * g.ccz;
     if (need_bound && !r->cells_have_bound) {
-        if (n_cells + n_macro > r->cell_cap) {
-            VR_HIP(r, hipStreamSynchronize(r->stream));
-            if (r->cell_bound) VR_HIP(r, hipFree(r->cell_bound));
-            r->cell_bound = nullptr;
-            r->cell_cap = 0;
-            VR_HIP(r, hipMalloc((void **)&r->cell_bound, (n_cells + n_macro) * sizeof(float)));
-            r->cell_cap = n_cells + n_macro;
-        }
+        if ((rc = grow(r, r->cell_bound, (n_cells + n_macro) * sizeof(float)))) return rc;
         VR_HIP(r, vr_launch_cell_bounds(coarse_mm, g, inv_max_of(r->format), make_tf_view(r),
                                         r->cell_sparse, r->cell_bound, nullptr, r->stream));
         g.bound = r->cell_bound;
         VR_HIP(r, vr_launch_cell_coarse_bounds(g, r->cell_bound + n_cells, r->stream));
         // how far the macro cells around one are free too (CellView::cdist)
-        if (2 * (size_t)kLeapLevels * n_macro > r->cell_dist_cap) {
-            VR_HIP(r, hipStreamSynchronize(r->stream));
-            if (r->cell_dist) VR_HIP(r, hipFree(r->cell_dist));
-            r->cell_dist = nullptr;
-            r->cell_dist_cap = 0;
-            VR_HIP(r, hipMalloc((void **)&r->cell_dist, 2 * (size_t)kLeapLevels * n_macro));
-            r->cell_dist_cap = 2 * (size_t)kLeapLevels * n_macro;
-        }
+        if ((rc = grow(r, r->cell_dist, 2 * (size_t)kLeapLevels * n_macro))) return rc;
         VR_HIP(r, vr_launch_cell_leap_radius(g, r->cell_bound + n_cells, r->cell_dist, &r->cell_dist_table, r->stream));
-        r->cells_have_bound = true;
+        cells_tables_built(r, true, false);
     }
     g.bound = r->cells_have_bound ? r->cell_bound : nullptr;
     g.cbound = (r->cells_have_bound && r->pt_leap) ? r->cell_bound + n_cells : nullptr;
     g.cdist = (g.cbound && r->pt_leap_far) ? r->cell_dist_table : nullptr;
     if (need_empty && !r->cells_have_empty) {
-        if (n_fine > r->empty_cap) {
-            VR_HIP(r, hipStreamSynchronize(r->stream));
-            if (r->cell_empty) VR_HIP(r, hipFree(r->cell_empty));
-            r->cell_empty = nullptr;
-            r->empty_cap = 0;
-            VR_HIP(r, hipMalloc((void **)&r->cell_empty, ((n_fine + 63) / 64) * 2 * sizeof(uint32_t)));
-            r->empty_cap = n_fine;
-        }
+        if ((rc = grow(r, r->cell_empty, ((n_fine + 63) / 64) * 2 * sizeof(uint32_t)))) return rc;
         VR_HIP(r, vr_launch_cell_bounds(one_grid ? coarse_mm : fine_mm, fine, inv_max_of(r->format),
                                         make_tf_view(r), r->cell_sparse, nullptr, r->cell_empty, r->stream));
-        r->cells_have_empty = true;
+        cells_tables_built(r, false, true);
         g.empty = r->cell_empty;
     }
     if (!r->cells_have_empty) g.empty = nullptr;
@@ -799,15 +477,9 @@ int ensure_queue(vrhip_renderer *r, uint32_t W, uint32_t H, uint32_t tile_w, uin
         }
 
     VR_HIP(r, hipStreamSynchronize(r->stream));
-    if (q.size() > r->queue_cap) {
-        if (r->queue_dev) VR_HIP(r, hipFree(r->queue_dev));
-        r->queue_dev = nullptr;
-        if (r->live) VR_HIP(r, hipFree(r->live));
-        r->live = nullptr;
-        VR_HIP(r, hipMalloc((void **)&r->live, q.size() * sizeof(LiveTile)));
-        VR_HIP(r, hipMalloc((void **)&r->queue_dev, q.size() * sizeof(WaveTile)));
-        r->queue_cap = (uint32_t)q.size();
-    }
+    int rc = grow(r, r->live, q.size() * sizeof(LiveTile));
+    if (!rc) rc = grow(r, r->queue_dev, q.size() * sizeof(WaveTile));
+    if (rc) return rc;
     if (!q.empty())
         VR_HIP(r, hipMemcpy(r->queue_dev, q.data(), q.size() * sizeof(WaveTile),
                             hipMemcpyHostToDevice));
@@ -817,20 +489,10 @@ int ensure_queue(vrhip_renderer *r, uint32_t W, uint32_t H, uint32_t tile_w, uin
     ++r->queue_version;
     // continuation buffer of the two-phase march: worst case every ray is suspended
     const size_t need = q.size() * 64;
-    if (need > r->cont_cap) {
-        if (r->cont) VR_HIP(r, hipFree(r->cont));
-        r->cont = nullptr;
-        r->cont_cap = 0;
-        VR_HIP(r, hipMalloc((void **)&r->cont, need * sizeof(ContRec)));
-        if (r->order) VR_HIP(r, hipFree(r->order));
-        r->order = nullptr;
-        VR_HIP(r, hipMalloc((void **)&r->order, need * sizeof(uint32_t)));
-        if (r->live_rays) VR_HIP(r, hipFree(r->live_rays));
-        r->live_rays = nullptr;
-        VR_HIP(r, hipMalloc((void **)&r->live_rays, (size_t)kLiveLists * live_list_cap((uint32_t)q.size()) * sizeof(ContRec)));
-        r->cont_cap = need;
-    }
-    return VRHIP_OK;
+    rc = grow(r, r->cont, need * sizeof(ContRec));
+    if (!rc) rc = grow(r, r->order, need * sizeof(uint32_t));
+    if (!rc) rc = grow(r, r->live_rays, (size_t)kLiveLists * live_list_cap((uint32_t)q.size()) * sizeof(ContRec));
+    return rc;
 }
 
 void fill_launch(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t out_stride,
@@ -949,14 +611,8 @@ int ensure_patch_classes(vrhip_renderer *r, RaycastLaunch *a)
                                a->skip.near_r, n_patches, r->queue_frames, (uint32_t)a->bricks.bw};
     put(misc, sizeof misc);
     if (key != r->patch_class_key) {
-        if (n_patches > r->patch_class_cap) {
-            VR_HIP(r, hipStreamSynchronize(r->stream));
-            if (r->patch_class) VR_HIP(r, hipFree(r->patch_class));
-            r->patch_class = nullptr;
-            r->patch_class_cap = 0;
-            VR_HIP(r, hipMalloc((void **)&r->patch_class, n_patches));
-            r->patch_class_cap = n_patches;
-        }
+        const int rc = grow(r, r->patch_class, n_patches);
+        if (rc) return rc;
         r->patch_class_key.clear();
         VR_HIP(r, vr_launch_patch_classes(*a, n_patches, r->queue_frames, r->patch_class, r->stream));
         r->patch_class_key.swap(key);
@@ -1113,197 +769,11 @@ int count_touched_impl(vrhip_renderer *r, uint32_t width, uint32_t height, uint3
     return VRHIP_OK;
 }
 
-__global__ __launch_bounds__(256) void vr_assemble_kernel(const float4 *staging, const uint32_t *slot_of_tile,
-                                                          uint32_t W, uint32_t H, uint32_t tw, uint32_t th,
-                                                          uint32_t tiles_x, float4 *frame)
-{
-    const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
-    if (x >= W || y >= H) return;
-    const uint32_t slot = slot_of_tile[(y / th) * tiles_x + x / tw];
-    frame[(size_t)y * W + x] = staging[((size_t)slot * th + (y % th)) * tw + (x % tw)];
-}
-
-// Multi-GPU, rank 0: the frames of a batch straight from the ranks' (sparse) gather messages, one thread per
-// pixel -- tiles of one colour from their single pixel, the others from the message's whole tiles
-// (TileDriver, tiles.py: message = [maxc slot numbers | S pixels | maxc whole tiles], S = frames x cap).
-constexpr uint32_t kMaxGatherRanks = 64;
-struct GatherMsgs { const float *p[kMaxGatherRanks]; };
-
-__global__ __launch_bounds__(256) void vr_assemble_batch_kernel(GatherMsgs msgs, const int32_t *pos, const uint32_t *rank_slot,
-                                                                uint32_t S, uint32_t cap, uint32_t maxc, uint32_t W, uint32_t H,
-                                                                uint32_t tw, uint32_t th, uint32_t tiles_x, float4 *frames)
-{
-    // one workgroup per (tile, frame): the tile's rank, slot and position are looked up once, and a thread's
-    // column inside the tile is fixed where the tile's width divides the workgroup (16 .. 256 pixels)
-    const uint32_t t = blockIdx.x, f = blockIdx.y;
-    const uint32_t rs = rank_slot[t];
-    const uint32_t rank = rs >> 16, row = f * cap + (rs & 0xffffu);
-    const float *m = msgs.p[rank];
-    const int32_t p = pos[(size_t)rank * S + row];
-    const uint32_t x0 = (t % tiles_x) * tw, y0 = (t / tiles_x) * th;
-    float4 *dst = frames + ((size_t)f * H + y0) * W + x0;
-    const uint32_t w = min(tw, W - x0), h = min(th, H - y0);   // (ragged right / bottom tiles)
-    if (p < 0) {
-        const float4 v = reinterpret_cast<const float4 *>(m + maxc)[row];
-        if (256u % tw == 0u) {
-            const uint32_t lx = threadIdx.x % tw;
-            if (lx < w)
-                for (uint32_t ly = threadIdx.x / tw; ly < h; ly += 256u / tw) dst[(size_t)ly * W + lx] = v;
-        } else {
-            for (uint32_t i = threadIdx.x; i < tw * th; i += 256u) {
-                const uint32_t ly = i / tw, lx = i - ly * tw;
-                if (lx < w && ly < h) dst[(size_t)ly * W + lx] = v;
-            }
-        }
-        return;
-    }
-    const float4 *src = reinterpret_cast<const float4 *>(m + maxc + 4u * (size_t)S) + (size_t)p * th * tw;
-    if (256u % tw == 0u) {
-        const uint32_t lx = threadIdx.x % tw;
-        if (lx < w)
-            for (uint32_t ly = threadIdx.x / tw; ly < h; ly += 256u / tw) dst[(size_t)ly * W + lx] = src[ly * tw + lx];
-    } else {
-        for (uint32_t i = threadIdx.x; i < tw * th; i += 256u) {
-            const uint32_t ly = i / tw, lx = i - ly * tw;
-            if (lx < w && ly < h) dst[(size_t)ly * W + lx] = src[i];
-        }
-    }
-}
-
-// ---- the sparse gather message of a batch, packed on the GPU (vrhip_pack_tiles; the C++ host's TileGather):
-// [spad slot numbers | one pixel per slot | the whole tiles], spad = n_slots rounded up to 4 -- the format
-// vr_assemble_batch_kernel reads with maxc = spad (tiles.py packs the same with torch ops and maxc = the ranks'
-// largest count).
-
-// one workgroup per slot: is any pixel of the tile different (bit for bit) from its first?  Also the slot's pixel.
-__global__ __launch_bounds__(256) void vr_pack_flags_kernel(const uint4 *tiles, uint32_t P, int32_t *flags, uint4 *uni)
-{
-    const uint32_t s = blockIdx.x;
-    const uint4 *t = tiles + (size_t)s * P;
-    const uint4 first = t[0];
-    bool diff = false;
-    for (uint32_t i = threadIdx.x; i < P; i += 256u) {
-        const uint4 v = t[i];
-        diff = diff || v.x != first.x || v.y != first.y || v.z != first.z || v.w != first.w;
-    }
-    __shared__ uint32_t any;
-    if (threadIdx.x == 0) any = 0u;
-    __syncthreads();
-    if (__ballot(diff) && (threadIdx.x & 63u) == 0u) atomicOr(&any, 1u);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        flags[s] = any ? 1 : 0;
-        uni[s] = first;
-    }
-}
-
-// one workgroup: flags -> position among the whole tiles (or -1), the slot list and the count
-__global__ __launch_bounds__(1024) void vr_pack_scan_kernel(int32_t *flags_pos, uint32_t S, int32_t *slots, uint32_t *count)
-{
-    __shared__ uint32_t wave_sums[16];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0u;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint32_t base = 0; base < S; base += 1024u) {
-        const uint32_t s = base + threadIdx.x;
-        const bool f = s < S && flags_pos[s] != 0;
-        const unsigned long long m = __ballot(f);
-        const uint32_t below = (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_sums[wave] = (uint32_t)__builtin_popcountll(m);
-        __syncthreads();
-        uint32_t off = carry;
-        for (uint32_t w = 0; w < wave; ++w) off += wave_sums[w];
-        if (s < S) {
-            flags_pos[s] = f ? (int32_t)(off + below) : -1;
-            if (f) slots[off + below] = (int32_t)s;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t t = 0;
-            for (uint32_t w = 0; w < 16u; ++w) t += wave_sums[w];
-            carry += t;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *count = carry;
-}
-
-// one workgroup per slot: a whole tile to its place in the message
-__global__ __launch_bounds__(256) void vr_pack_copy_kernel(const uint4 *tiles, uint32_t P, const int32_t *pos, uint4 *out)
-{
-    const int32_t p = pos[blockIdx.x];
-    if (p < 0) return;
-    const uint4 *t = tiles + (size_t)blockIdx.x * P;
-    uint4 *o = out + (size_t)p * P;
-    for (uint32_t i = threadIdx.x; i < P; i += 256u) o[i] = t[i];
-}
-
-// root: pos[rank][row] = -1, then the position of every listed slot
-__global__ __launch_bounds__(256) void vr_msg_pos_fill_kernel(int32_t *pos, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < n) pos[i] = -1;
-}
-struct GatherCounts { uint32_t c[kMaxGatherRanks]; };
-__global__ __launch_bounds__(256) void vr_msg_pos_scatter_kernel(GatherMsgs msgs, GatherCounts counts, uint32_t S, int32_t *pos)
-{
-    const uint32_t rank = blockIdx.y, i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= counts.c[rank]) return;
-    const uint32_t slot = (uint32_t)reinterpret_cast<const int32_t *>(msgs.p[rank])[i];
-    if (slot < S) pos[(size_t)rank * S + slot] = (int32_t)i;
-}
-
 } // namespace
 
 extern "C" {
 
 int vrhip_abi_version(void) { return VRHIP_ABI_VERSION; }
-
-int vrhip_pack_tiles(vrhip_renderer *r, void *hip_stream, const float *tiles_dev, uint32_t n_slots, uint32_t tile_pixels,
-                     int32_t *scratch_dev, float *msg_dev, uint32_t *count_dev)
-{
-    if (!r) return VRHIP_ERR_INVALID;
-    VR_REQUIRE(r, tiles_dev && scratch_dev && msg_dev && count_dev && n_slots && tile_pixels &&
-                      ((uintptr_t)tiles_dev & 15u) == 0 && ((uintptr_t)msg_dev & 15u) == 0,
-               VRHIP_ERR_INVALID, "vrhip_pack_tiles: invalid argument (buffers must be 16-byte aligned)");
-    if (set_device(r)) return VRHIP_ERR_HIP;
-    hipStream_t st = (hipStream_t)hip_stream;
-    const uint32_t spad = (n_slots + 3u) / 4u * 4u;
-    hipLaunchKernelGGL(vr_pack_flags_kernel, dim3(n_slots), dim3(256), 0, st, (const uint4 *)tiles_dev, tile_pixels,
-                       scratch_dev, (uint4 *)(msg_dev + spad));
-    hipLaunchKernelGGL(vr_pack_scan_kernel, dim3(1), dim3(1024), 0, st, scratch_dev, n_slots, (int32_t *)msg_dev, count_dev);
-    hipLaunchKernelGGL(vr_pack_copy_kernel, dim3(n_slots), dim3(256), 0, st, (const uint4 *)tiles_dev, tile_pixels,
-                       (const int32_t *)scratch_dev, (uint4 *)(msg_dev + spad + 4u * (size_t)n_slots));
-    VR_HIP(r, hipGetLastError());
-    return VRHIP_OK;
-}
-
-int vrhip_message_positions(vrhip_renderer *r, void *hip_stream, const float *const *msgs_dev, const uint32_t *counts_host,
-                            uint32_t world, uint32_t n_slots, int32_t *pos_dev)
-{
-    if (!r) return VRHIP_ERR_INVALID;
-    VR_REQUIRE(r, msgs_dev && counts_host && pos_dev && world >= 1 && world <= kMaxGatherRanks && n_slots,
-               VRHIP_ERR_INVALID, "vrhip_message_positions: invalid argument");
-    if (set_device(r)) return VRHIP_ERR_HIP;
-    hipStream_t st = (hipStream_t)hip_stream;
-    GatherMsgs g;
-    GatherCounts c;
-    uint32_t maxc = 0;
-    for (uint32_t i = 0; i < kMaxGatherRanks; ++i) {
-        g.p[i] = i < world ? msgs_dev[i] : nullptr;
-        c.c[i] = i < world ? counts_host[i] : 0u;
-        VR_REQUIRE(r, c.c[i] <= n_slots && (i >= world || g.p[i]), VRHIP_ERR_INVALID,
-                   "vrhip_message_positions: a count exceeds the number of slots, or a message is NULL");
-        maxc = std::max(maxc, c.c[i]);
-    }
-    const uint32_t n = world * n_slots;
-    hipLaunchKernelGGL(vr_msg_pos_fill_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, pos_dev, n);
-    if (maxc)
-        hipLaunchKernelGGL(vr_msg_pos_scatter_kernel, dim3((maxc + 255u) / 256u, world), dim3(256), 0, st, g, c, n_slots, pos_dev);
-    VR_HIP(r, hipGetLastError());
-    return VRHIP_OK;
-}
 
 int vrhip_create(int device_id, vrhip_renderer **out)
 {
@@ -1325,16 +795,16 @@ int vrhip_create(int device_id, vrhip_renderer **out)
                                                                                                  : hipEventDisableSystemFence;
     if ((e = hipSetDevice(device_id)) != hipSuccess ||
         (e = hipGetDeviceProperties(&prop, device_id)) != hipSuccess ||
-        (e = hipStreamCreateWithFlags(&r->own_stream, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&r->ev0, ev_flags)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&r->ev1, ev_flags)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&r->evm, ev_flags)) != hipSuccess ||
-        (e = hipEventCreate(&r->evb0)) != hipSuccess ||
-        (e = hipEventCreate(&r->evb1)) != hipSuccess ||
-        (e = hipMalloc((void **)&r->stats_dev, sizeof(DevStats))) != hipSuccess ||
-        (e = hipMalloc((void **)&r->queue_head, 2 * kControlWords * sizeof(uint32_t))) != hipSuccess) {
+        (e = hipStreamCreateWithFlags(&r->own_stream.h, hipStreamNonBlocking)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&r->ev0.h, ev_flags)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&r->ev1.h, ev_flags)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&r->evm.h, ev_flags)) != hipSuccess ||
+        (e = hipEventCreate(&r->evb0.h)) != hipSuccess ||
+        (e = hipEventCreate(&r->evb1.h)) != hipSuccess ||
+        (e = hipMalloc((void **)&r->stats_dev.p, sizeof(DevStats))) != hipSuccess ||
+        (e = hipMalloc((void **)&r->queue_head.p, 2 * kControlWords * sizeof(uint32_t))) != hipSuccess) {
         std::string msg = std::string("ERROR: vrhip_create (") + hipGetErrorString(e) + ")";
-        delete r;
+        delete r;   // (with whatever it holds by now)
         return fail(nullptr, VRHIP_ERR_HIP, msg);
     }
     r->stream = r->own_stream;
@@ -1392,48 +862,13 @@ void vrhip_destroy(vrhip_renderer *r)
     if (!r) return;
     (void)hipSetDevice(r->device);
     (void)hipStreamSynchronize(r->stream);
-    vrhip_clear_volumes(r);
-    if (r->tff) (void)hipFree(r->tff);
-    if (r->prefix) (void)hipFree(r->prefix);
-    if (r->fb) (void)hipFree(r->fb);
-    if (r->stats_dev) (void)hipFree(r->stats_dev);
-    if (r->queue_dev) (void)hipFree(r->queue_dev);
-    if (r->queue_head) (void)hipFree(r->queue_head);
-    if (r->cont) (void)hipFree(r->cont);
-    if (r->cost) (void)hipFree(r->cost);
-    for (uint8_t *p : {r->hit_in, r->hit_out, r->hit_status, r->hit_any})
-        if (p) (void)hipFree(p);
-    if (r->env) (void)hipFree(r->env);
-    if (r->seeds_dev) (void)hipFree(r->seeds_dev);
-    if (r->cams_dev) (void)hipFree(r->cams_dev);
-    if (r->samples_dev) (void)hipFree(r->samples_dev);
-    if (r->fp) (void)hipFree(r->fp);
-    if (r->live) (void)hipFree(r->live);
-    if (r->order) (void)hipFree(r->order);
-    if (r->live_rays) (void)hipFree(r->live_rays);
-    if (r->skip_bits) (void)hipFree(r->skip_bits);
-    if (r->near_bits) (void)hipFree(r->near_bits);
-    if (r->near_scratch) (void)hipFree(r->near_scratch);
-    if (r->patch_class) (void)hipFree(r->patch_class);
-    if (r->cell_bound) (void)hipFree(r->cell_bound);
-    if (r->cell_dist) (void)hipFree(r->cell_dist);
-    if (r->cell_empty) (void)hipFree(r->cell_empty);
-    if (r->cell_sparse) (void)hipFree(r->cell_sparse);
-    if (r->ingest_ws) (void)hipFree(r->ingest_ws);
-    if (r->evi0) (void)hipEventDestroy(r->evi0);
-    if (r->evi1) (void)hipEventDestroy(r->evi1);
-    if (r->ev0) (void)hipEventDestroy(r->ev0);
-    if (r->ev1) (void)hipEventDestroy(r->ev1);
-    if (r->evm) (void)hipEventDestroy(r->evm);
-    if (r->evb0) (void)hipEventDestroy(r->evb0);
-    if (r->evb1) (void)hipEventDestroy(r->evb1);
-    if (r->own_stream) (void)hipStreamDestroy(r->own_stream);
+    vrhip_clear_volumes(r);   // detaches the sharers, leaves the owner's list
     delete r;
 }
 
 const char *vrhip_last_error(const vrhip_renderer *r)
 {
-    return r ? r->err.c_str() : g_create_error.c_str();
+    return r ? r->err.c_str() : create_error().c_str();
 }
 
 int vrhip_device_name(const vrhip_renderer *r, char *buf, size_t buf_len)
@@ -1460,7 +895,7 @@ static int download_cells_impl(vrhip_renderer *r, bool fine, float *out_minmax, 
                VRHIP_ERR_NODATA, "No volume data is loaded.");
     VR_REQUIRE(r, r->tff && r->tff_n, VRHIP_ERR_NODATA, "No transfer function set.");
     if (set_device(r)) return VRHIP_ERR_HIP;
-    r->pt_dirty = true;
+    cells_tables_stale(r);   // (this call always rebuilds the table it asks for)
     // (only the grid asked for: the coarse one is then built directly unless the fine one exists already,
     // in which case it is reduced from it -- the tests take both routes)
     int rc = ensure_cells(r, !fine, fine);
@@ -1495,46 +930,6 @@ int vrhip_download_empty_cells(vrhip_renderer *r, float *out_minmax, size_t n_fl
                                uint32_t *shift)
 {
     return download_cells_impl(r, true, out_minmax, n_floats, dims, shift);
-}
-
-int vrhip_assemble_frame(vrhip_renderer *r, const float *staging_dev, const uint32_t *slot_of_tile_dev,
-                         uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h,
-                         float *frame_dev)
-{
-    if (!r) return VRHIP_ERR_INVALID;
-    VR_REQUIRE(r, staging_dev && slot_of_tile_dev && frame_dev && width && height && tile_w && tile_h,
-               VRHIP_ERR_INVALID, "vrhip_assemble_frame: invalid argument");
-    if (set_device(r)) return VRHIP_ERR_HIP;
-    const uint32_t tiles_x = (width + tile_w - 1) / tile_w;
-    hipLaunchKernelGGL(vr_assemble_kernel, dim3((width + 63) / 64, (height + 3) / 4), dim3(256), 0, r->stream,
-                       (const float4 *)staging_dev, slot_of_tile_dev, width, height, tile_w, tile_h, tiles_x,
-                       (float4 *)frame_dev);
-    VR_HIP(r, hipGetLastError());
-    return VRHIP_OK;
-}
-
-int vrhip_assemble_batch(vrhip_renderer *r, void *hip_stream, const float *const *msgs_dev, uint32_t world,
-                         uint32_t n_frames, uint32_t cap, uint32_t maxc, const int32_t *pos_dev,
-                         const uint32_t *rank_slot_of_tile_dev, uint32_t width, uint32_t height, uint32_t tile_w,
-                         uint32_t tile_h, float *frames_dev)
-{
-    if (!r) return VRHIP_ERR_INVALID;
-    VR_REQUIRE(r, msgs_dev && pos_dev && rank_slot_of_tile_dev && frames_dev && world >= 1 && world <= kMaxGatherRanks &&
-                      n_frames && cap && cap <= 65536u && width && height && tile_w && tile_h && n_frames <= 65535u,
-               VRHIP_ERR_INVALID, "vrhip_assemble_batch: invalid argument");
-    if (set_device(r)) return VRHIP_ERR_HIP;
-    GatherMsgs g;
-    for (uint32_t i = 0; i < kMaxGatherRanks; ++i) g.p[i] = i < world ? msgs_dev[i] : nullptr;
-    for (uint32_t i = 0; i < world; ++i)
-        VR_REQUIRE(r, g.p[i] && ((uintptr_t)g.p[i] & 15u) == 0 && maxc % 4u == 0, VRHIP_ERR_INVALID,
-                   "vrhip_assemble_batch: messages must be 16-byte aligned, maxc a multiple of 4");
-    const uint32_t tiles_x = (width + tile_w - 1) / tile_w;
-    const uint32_t tiles_y = (height + tile_h - 1) / tile_h;
-    hipLaunchKernelGGL(vr_assemble_batch_kernel, dim3(tiles_x * tiles_y, n_frames), dim3(256), 0,
-                       (hipStream_t)hip_stream, g, pos_dev, rank_slot_of_tile_dev, n_frames * cap, cap, maxc, width,
-                       height, tile_w, tile_h, tiles_x, (float4 *)frames_dev);
-    VR_HIP(r, hipGetLastError());
-    return VRHIP_OK;
 }
 
 int vrhip_get_stream(const vrhip_renderer *r, void **hip_stream)
@@ -1661,28 +1056,14 @@ int vrhip_clear_volumes(vrhip_renderer *r)
     (void)hipStreamSynchronize(r->stream);
     // renderers that render from these voxels (vrhip_share_volumes) stop doing so before they are freed
     detach_sharers(r);
-    for (VolumeSlot &s : r->vols) {
-        if (!s.borrowed) {
-            if (s.dev) (void)hipFree(s.dev);
-            for (void *c : s.chan)
-                if (c) (void)hipFree(c);
-            if (s.bricks) (void)hipFree(s.bricks);
-        }
-        if (s.pt_minmax) (void)hipFree(s.pt_minmax);
-        if (s.fine_minmax) (void)hipFree(s.fine_minmax);
-    }
-    r->vols.clear();
-    r->fp_valid = false;
-    r->fp_failed_bytes = 0;
+    r->vols.clear();   // (frees what the slots own: not the voxels and bricks of a borrowed slot)
     if (r->vol_owner) {   // a sharer leaves its owner's list
         std::vector<vrhip_renderer *> &v = r->vol_owner->sharers;
         v.erase(std::remove(v.begin(), v.end(), r), v.end());
         r->vol_owner = nullptr;
     }
 
-    r->bricks_valid = false;
-    r->skip_dirty = true;
-    r->pt_dirty = true;
+    volumes_cleared(r);
     r->format = -1;
     r->channels = 1;
     r->res[0] = r->res[1] = r->res[2] = 0;
@@ -1726,18 +1107,15 @@ int vrhip_share_volumes(vrhip_renderer *r, vrhip_renderer *owner)
     for (size_t t = 0; t < owner->vols.size(); ++t) {
         VolumeSlot &d = r->vols[t];
         const VolumeSlot &s = owner->vols[t];
-        d.dev = s.dev;
-        for (int c = 0; c < 3; ++c) d.chan[c] = s.chan[c];
-        d.bricks = s.bricks;
+        d.dev.borrow(s.dev);
+        for (int c = 0; c < 3; ++c) d.chan[c].borrow(s.chan[c]);
+        d.bricks.borrow(s.bricks);
         d.borrowed = true;
     }
-    r->bricks_valid = owner->bricks_valid;
     r->timestep = owner->timestep < r->vols.size() ? owner->timestep : 0;
-    r->fp_valid = false;   // (its own footprint volume is not used while it shares: ensure_footprint)
     r->vol_owner = owner;
     owner->sharers.push_back(r);
-    r->skip_dirty = true;
-    r->pt_dirty = true;
+    volumes_shared(r, owner);
     return VRHIP_OK;
 }
 
@@ -1746,10 +1124,7 @@ int vrhip_set_timestep(vrhip_renderer *r, uint32_t timestep)
     if (!r) return VRHIP_ERR_INVALID;
     // volumerendercl.cpp:1169-1170: silently ignored when out of range
     if (!r->vols.empty() && timestep >= r->vols.size()) return VRHIP_OK;
-    if (r->timestep != timestep) {
-        r->skip_dirty = r->pt_dirty = true;
-        r->fp_valid = false;
-    }
+    if (r->timestep != timestep) timestep_changed(r);
     r->timestep = timestep;
     return VRHIP_OK;
 }
@@ -1780,16 +1155,12 @@ int vrhip_set_transfer_function(vrhip_renderer *r, const uint8_t *rgba8, uint32_
         table[i].w = (float)rgba8[4 * i + 3] / 255.0f;
     }
     VR_HIP(r, hipStreamSynchronize(r->stream));
-    if (r->tff_n != n_entries) {
-        if (r->tff) VR_HIP(r, hipFree(r->tff));
-        r->tff = nullptr;
-        r->tff_n = 0;
-        VR_HIP(r, hipMalloc((void **)&r->tff, n_entries * sizeof(float4)));
-        r->tff_n = n_entries;
-    }
+    r->tff_n = 0;
+    const int rc = grow(r, r->tff, n_entries * sizeof(float4));
+    if (rc) return rc;
     VR_HIP(r, hipMemcpy(r->tff, table.data(), n_entries * sizeof(float4), hipMemcpyHostToDevice));
-    r->skip_dirty = true;
-    r->pt_dirty = true;
+    r->tff_n = n_entries;
+    tf_changed(r);
     return VRHIP_OK;
 }
 
@@ -1799,16 +1170,12 @@ int vrhip_set_tff_prefix_sum(vrhip_renderer *r, const uint32_t *prefix, uint32_t
     VR_REQUIRE(r, prefix && n > 0, VRHIP_ERR_INVALID, "Empty prefix sum.");
     if (set_device(r)) return VRHIP_ERR_HIP;
     VR_HIP(r, hipStreamSynchronize(r->stream));
-    if (r->prefix_n != n) {
-        if (r->prefix) VR_HIP(r, hipFree(r->prefix));
-        r->prefix = nullptr;
-        r->prefix_n = 0;
-        VR_HIP(r, hipMalloc((void **)&r->prefix, n * sizeof(uint32_t)));
-        r->prefix_n = n;
-    }
+    r->prefix_n = 0;
+    const int rc = grow(r, r->prefix, n * sizeof(uint32_t));
+    if (rc) return rc;
     VR_HIP(r, hipMemcpy(r->prefix, prefix, n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    r->skip_dirty = true;
-    r->pt_dirty = true;
+    r->prefix_n = n;
+    tf_changed(r);
     return VRHIP_OK;
 }
 
@@ -1837,13 +1204,11 @@ int vrhip_build_bricks(vrhip_renderer *r)
             const vrhip_renderer *o = r->vol_owner;
             VR_REQUIRE(r, o && t < o->vols.size() && o->vols[t].bricks && o->vols[t].bricks_built, VRHIP_ERR_NODATA,
                        "vrhip_build_bricks: the owner of the shared volumes has to build its bricks first.");
-            s.bricks = o->vols[t].bricks;
+            s.bricks.borrow(o->vols[t].bricks);
             continue;
         }
-        if (!s.bricks) {
-            VR_HIP(r, hipMalloc(&s.bricks, bricks_bytes(r)));
-            s.bricks_built = false;
-        }
+        const int rc = grow(r, s.bricks, bricks_bytes(r));   // (a slot without bricks is one with bricks_built unset)
+        if (rc) return rc;
     }
     bool any = false;
     for (const VolumeSlot &s : r->vols) any = any || (!s.borrowed && !s.bricks_built);
@@ -1853,15 +1218,13 @@ int vrhip_build_bricks(vrhip_renderer *r)
             if (s.borrowed || s.bricks_built) continue;
             VolView v = make_vol_view(r, s.dev);
             VR_HIP(r, vr_launch_build_bricks(v, r->format, r->brick_tex, s.bricks, r->stream));
-            s.bricks_built = true;
+            slot_bricks_built(s);
         }
         VR_HIP(r, hipEventRecord(r->evb1, r->stream));
         r->bricks_timed = true;
     }
     VR_HIP(r, hipStreamSynchronize(r->stream));   // reference: _queueCL.finish() (:670)
-    r->bricks_valid = true;
-    r->skip_dirty = true;
-    r->pt_dirty = true;
+    bricks_built(r);
     return VRHIP_OK;
 }
 
@@ -2009,12 +1372,11 @@ int vrhip_render_batch_views(vrhip_renderer *r, uint32_t width, uint32_t height,
     int rc = prepare_render(r, width, height, tile_w, tile_h, tile_ids, n_tiles, n_frames,
                             out_frame_stride);
     if (rc) return rc;
-    if (!r->seeds_dev) VR_HIP(r, hipMalloc((void **)&r->seeds_dev, kMaxBatchFrames * sizeof(uint32_t)));
+    if ((rc = grow(r, r->seeds_dev, kMaxBatchFrames * sizeof(uint32_t)))) return rc;
     VR_HIP(r, hipMemcpyAsync(r->seeds_dev, seeds, n_frames * sizeof(uint32_t), hipMemcpyHostToDevice,
                              r->stream));
     if (cams) {
-        if (!r->cams_dev)
-            VR_HIP(r, hipMalloc((void **)&r->cams_dev, kMaxBatchFrames * sizeof(vrhip_camera_params)));
+        if ((rc = grow(r, r->cams_dev, kMaxBatchFrames * sizeof(vrhip_camera_params)))) return rc;
         VR_HIP(r, hipMemcpyAsync(r->cams_dev, cams, n_frames * sizeof(vrhip_camera_params), hipMemcpyHostToDevice,
                                  r->stream));
     }
@@ -2056,21 +1418,14 @@ int vrhip_render_samples(vrhip_renderer *r, uint32_t width, uint32_t height, uin
         if (rc) return rc;
         const size_t rec_bytes = ((size_t)per + (stage ? 1u : 0u)) * (size_t)plane * sizeof(float4);
         const size_t need = rec_bytes + (size_t)per * (size_t)plane;
-        if (need > r->samples_cap) {
-            VR_HIP(r, hipStreamSynchronize(r->stream));
-            if (r->samples_dev) VR_HIP(r, hipFree(r->samples_dev));
-            r->samples_dev = nullptr;
-            r->samples_cap = 0;
-            VR_HIP(r, hipMalloc(&r->samples_dev, need));
-            r->samples_cap = need;
-        }
-        if (!r->seeds_dev) VR_HIP(r, hipMalloc((void **)&r->seeds_dev, kMaxBatchFrames * sizeof(uint32_t)));
+        if ((rc = grow(r, r->samples_dev, need))) return rc;
+        if ((rc = grow(r, r->seeds_dev, kMaxBatchFrames * sizeof(uint32_t)))) return rc;
         VR_HIP(r, hipMemcpyAsync(r->seeds_dev, seeds + done, m * sizeof(uint32_t), hipMemcpyHostToDevice, r->stream));
         RaycastLaunch a;
         fill_launch(r, width, height, tile_ids ? tile_w : width, &a);
-        float4 *const planes = (float4 *)r->samples_dev;
+        float4 *const planes = (float4 *)r->samples_dev.p;
         a.frame.out = planes;
-        a.frame.sample_mark = (uint8_t *)r->samples_dev + rec_bytes;
+        a.frame.sample_mark = (uint8_t *)r->samples_dev.p + rec_bytes;
         a.frame.seeds = r->seeds_dev;
         a.render.iteration = first + done;
         a.samples = 1;
@@ -2082,7 +1437,7 @@ int vrhip_render_samples(vrhip_renderer *r, uint32_t width, uint32_t height, uin
         done += m;
     }
     if (out_rgba && !out_is_device) {
-        const float4 *src = stage ? (const float4 *)r->samples_dev + (size_t)per * (size_t)plane : r->fb;
+        const float4 *src = stage ? (const float4 *)r->samples_dev.p + (size_t)per * (size_t)plane : r->fb;
         VR_HIP(r, hipMemcpyAsync(out_rgba, src, (size_t)plane * sizeof(float4), hipMemcpyDeviceToHost, r->stream));
         VR_HIP(r, hipStreamSynchronize(r->stream));
     }
@@ -2173,8 +1528,7 @@ int vrhip_set_environment_map(vrhip_renderer *r, const float *rgba, uint32_t wid
     if (!r) return VRHIP_ERR_INVALID;
     if (set_device(r)) return VRHIP_ERR_HIP;
     VR_HIP(r, hipStreamSynchronize(r->stream));
-    if (r->env) VR_HIP(r, hipFree(r->env));
-    r->env = nullptr;
+    r->env.release();
     r->env_w = r->env_h = 0;
     // the kernel only samples maps wider than one texel (:655); createEnvironmentMap("")
     // installs a 1x1 white one, i.e. none
@@ -2182,7 +1536,8 @@ int vrhip_set_environment_map(vrhip_renderer *r, const float *rgba, uint32_t wid
     VR_REQUIRE(r, width <= 16384 && height <= 16384, VRHIP_ERR_INVALID,
                "Environment map too large.");
     const size_t bytes = (size_t)width * height * sizeof(float4);
-    VR_HIP(r, hipMalloc((void **)&r->env, bytes));
+    const int rc = grow(r, r->env, bytes);
+    if (rc) return rc;
     VR_HIP(r, hipMemcpy(r->env, rgba, bytes, hipMemcpyHostToDevice));
     r->env_w = width;
     r->env_h = height;
@@ -2251,188 +1606,5 @@ int vrhip_count_touched_tiles(vrhip_renderer *r, uint32_t width, uint32_t height
     return count_touched_impl(r, width, height, tile_w, tile_h, tile_ids, n_tiles,
                               microbricks_touched, nullptr, 0);
 }
-
-} // extern "C"
-
-// ---- device-side ingest (vr_ingest.hip)
-
-namespace {
-
-constexpr size_t kIngestHistOffset = 16;   // bytes: the maximum word sits in front of the counters
-constexpr size_t kIngestWsBytes = kIngestHistOffset + 256 * sizeof(unsigned long long);
-
-int ensure_ingest_ws(vrhip_renderer *r)
-{
-    if (!r->ingest_ws) VR_HIP(r, hipMalloc(&r->ingest_ws, kIngestWsBytes));
-    if (!r->evi0) VR_HIP(r, hipEventCreate(&r->evi0));
-    if (!r->evi1) VR_HIP(r, hipEventCreate(&r->evi1));
-    return VRHIP_OK;
-}
-
-unsigned long long *ingest_hist(const vrhip_renderer *r)
-{
-    return reinterpret_cast<unsigned long long *>(static_cast<char *>(r->ingest_ws) + kIngestHistOffset);
-}
-
-// waits for the stream and adds the time between the two ingest events to *seconds
-hipError_t ingest_elapsed(vrhip_renderer *r, double *seconds)
-{
-    hipError_t e = hipStreamSynchronize(r->stream);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, r->evi0, r->evi1);
-    if (e == hipSuccess) *seconds += (double)ms * 1e-3;
-    return e;
-}
-
-// the counters, as the doubles the loader keeps
-hipError_t ingest_read_hist(vrhip_renderer *r, double hist[256])
-{
-    unsigned long long h[256];
-    hipError_t e = hipMemcpyAsync(h, ingest_hist(r), sizeof h, hipMemcpyDeviceToHost, r->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
-    if (e == hipSuccess)
-        for (int i = 0; i < 256; ++i) hist[i] = (double)h[i];
-    return e;
-}
-
-// The two passes of vrhip_ingest_raw over a prepared slot; `stage` holds stage_bytes of interleaved staging
-// followed (channels > 1) by the planar staging of `channels` planes of plane_stride elements.
-hipError_t ingest_passes(vrhip_renderer *r, VolumeSlot *s, const char *raw, size_t bytes, int format, int channels,
-                         int big_endian, int slab, char *stage, size_t stage_bytes, size_t plane_stride,
-                         double hist[256], float *max_value, double *seconds)
-{
-    const size_t bpv = fmt_bytes(format);
-    const size_t slice_texels = (size_t)r->res[0] * r->res[1], slice_b = slice_texels * bpv * (size_t)channels;
-    const size_t need = slice_b * r->res[2];
-    // what the loader's flat loops run over: every whole word of the file, the ones beyond the volume included
-    const size_t tail_words = bytes / bpv - need / bpv, stage_words = stage_bytes / bpv;
-    uint32_t *max_dev = static_cast<uint32_t *>(r->ingest_ws);
-    hipStream_t st = r->stream;
-    void *planes[4] = {s->dev, s->chan[0], s->chan[1], s->chan[2]};
-    char *planar = stage + stage_bytes;
-    hipError_t e = hipSuccess;
-#define VR_TRY(call)                                  \
-    do {                                              \
-        if ((e = (call)) != hipSuccess) return e;     \
-    } while (0)
-    // the words beyond the volume, stage_words at a time, each piece handed to fn(words in the piece)
-    auto for_tail = [&](auto fn) -> hipError_t {
-        for (size_t w0 = 0; w0 < tail_words; w0 += stage_words) {
-            const size_t nw = std::min(stage_words, tail_words - w0);
-            VR_TRY(hipMemcpyAsync(stage, raw + need + w0 * bpv, nw * bpv, hipMemcpyHostToDevice, st));
-            VR_TRY(hipEventRecord(r->evi0, st));
-            VR_TRY(fn(nw));
-            VR_TRY(hipEventRecord(r->evi1, st));
-            VR_TRY(ingest_elapsed(r, seconds));   // (the staging buffer is reused)
-        }
-        return hipSuccess;
-    };
-
-    // ---- pass 1, slab by slab: copy, maximum, de-interleave, re-tile the raw words
-    const uint32_t max_init = vr_ingest_max_init(format);
-    VR_TRY(hipMemcpyAsync(max_dev, &max_init, sizeof max_init, hipMemcpyHostToDevice, st));
-    VR_TRY(hipStreamSynchronize(st));   // (max_init leaves the stack)
-    for (int z0 = 0; z0 < (int)r->res[2]; z0 += slab) {
-        const int nz = std::min<int>(slab, (int)r->res[2] - z0);
-        const size_t texels = (size_t)nz * slice_texels;
-        VR_TRY(hipMemcpyAsync(stage, raw + (size_t)z0 * slice_b, (size_t)nz * slice_b, hipMemcpyHostToDevice, st));
-        VR_TRY(hipEventRecord(r->evi0, st));
-        VR_TRY(vr_launch_ingest_max(stage, texels * (size_t)channels, format, big_endian, max_dev, r->num_cus, st));
-        if (channels > 1) {
-            VR_TRY(vr_launch_deinterleave(stage, planar, plane_stride, texels, format, channels, st));
-            for (int c = 0; c < channels; ++c)
-                VR_TRY(vr_launch_retile(make_vol_view(r, planes[c]), format, planar + (size_t)c * plane_stride * bpv, z0,
-                                        nz, true, st));
-        } else {
-            VR_TRY(vr_launch_retile(make_vol_view(r, s->dev), format, stage, z0, nz, true, st));
-        }
-        VR_TRY(hipEventRecord(r->evi1, st));
-        VR_TRY(ingest_elapsed(r, seconds));
-    }
-    VR_TRY(for_tail([&](size_t nw) { return vr_launch_ingest_max(stage, nw, format, big_endian, max_dev, r->num_cus, st); }));
-    uint32_t max_word = 0;
-    VR_TRY(hipMemcpyAsync(&max_word, max_dev, sizeof max_word, hipMemcpyDeviceToHost, st));
-    VR_TRY(hipStreamSynchronize(st));
-    IngestParams p;
-    p.max_value = vr_ingest_max_decode(format, max_word);
-    p.stretch = 65535.f / p.max_value;   // datrawreader.cpp: numeric_limits<unsigned short>::max() / float(max)
-    p.big_endian = big_endian;
-
-    // ---- pass 2: convert in place and count
-    VR_TRY(hipMemsetAsync(ingest_hist(r), 0, 256 * sizeof(unsigned long long), st));
-    VR_TRY(hipEventRecord(r->evi0, st));
-    for (int c = 0; c < channels; ++c)
-        VR_TRY(vr_launch_ingest_convert(make_vol_view(r, planes[c]), format, p, 1, ingest_hist(r), r->num_cus, st));
-    VR_TRY(hipEventRecord(r->evi1, st));
-    VR_TRY(ingest_elapsed(r, seconds));
-    VR_TRY(for_tail([&](size_t nw) { return vr_launch_ingest_count(stage, nw, format, p, ingest_hist(r), r->num_cus, st); }));
-    VR_TRY(ingest_read_hist(r, hist));
-#undef VR_TRY
-    *max_value = p.max_value;
-    return hipSuccess;
-}
-
-} // namespace
-
-extern "C" {
-
-int vrhip_ingest_raw(vrhip_renderer *r, const void *raw, size_t bytes, const uint32_t res[3], int format, int channels,
-                     int big_endian, uint32_t timestep, double hist[256], float *max_value)
-{
-    if (!r) return VRHIP_ERR_INVALID;
-    VR_REQUIRE(r, raw && hist && max_value, VRHIP_ERR_INVALID, "vrhip_ingest_raw: NULL pointer");
-    VR_REQUIRE(r, channels == 1 || channels == 2 || channels == 4, VRHIP_ERR_INVALID,
-               "Unknown or invalid volume color format.");   // volumerendercl.cpp:711
-    VR_REQUIRE(r, res && res[0] && res[1] && res[2], VRHIP_ERR_INVALID, "Volume resolution must be non-zero.");
-    VR_REQUIRE(r, format >= VRHIP_UCHAR && format <= VRHIP_FLOAT, VRHIP_ERR_INVALID,
-               "Unknown or invalid volume data format.");
-    const size_t bpv = fmt_bytes(format);
-    const size_t slice_texels = (size_t)res[0] * res[1], slice_b = slice_texels * bpv * (size_t)channels;
-    VR_REQUIRE(r, bytes / slice_b >= res[2], VRHIP_ERR_INVALID,
-               "Volume size does not match size specified in dat file.");   // volumerendercl.cpp:740-742
-    if (set_device(r)) return VRHIP_ERR_HIP;
-    VolumeSlot *s;
-    int rc = prepare_slot(r, res, format, timestep, &s, channels);
-    if (rc) return rc;
-    if ((rc = ensure_ingest_ws(r))) return rc;
-    // slabs of whole multiples of 4 slices (micro-brick rows are written whole), at least 4
-    int slab = (int)std::max<size_t>(4, r->ingest_slab_bytes / slice_b / 4 * 4);
-    slab = std::min<int>(slab, (int)((res[2] + 3) / 4 * 4));
-    const size_t stage_bytes = ((size_t)slab * slice_b + 15) / 16 * 16;
-    const size_t per16 = 16 / bpv;
-    const size_t plane_stride = channels > 1 ? ((size_t)slab * slice_texels + per16 - 1) / per16 * per16 : 0;
-    void *stage = nullptr;
-    VR_HIP(r, hipMalloc(&stage, stage_bytes + (size_t)channels * plane_stride * bpv));
-    double seconds = 0.0;
-    const hipError_t e = ingest_passes(r, s, static_cast<const char *>(raw), bytes, format, channels, big_endian ? 1 : 0,
-                                       slab, static_cast<char *>(stage), stage_bytes, plane_stride, hist, max_value,
-                                       &seconds);
-    (void)hipFree(stage);
-    if (e != hipSuccess)
-        return fail(r, VRHIP_ERR_HIP, std::string("ERROR: vrhip_ingest_raw (") + hipGetErrorString(e) + ")");
-    r->ingest_seconds = seconds;
-    return VRHIP_OK;
-}
-
-int vrhip_volume_histogram(vrhip_renderer *r, uint32_t timestep, double hist[256])
-{
-    if (!r) return VRHIP_ERR_INVALID;
-    VR_REQUIRE(r, timestep < r->vols.size() && r->vols[timestep].dev, VRHIP_ERR_NODATA, "No volume data is loaded.");
-    VR_REQUIRE(r, hist, VRHIP_ERR_INVALID, "vrhip_volume_histogram: NULL pointer");
-    if (set_device(r)) return VRHIP_ERR_HIP;
-    int rc = ensure_ingest_ws(r);
-    if (rc) return rc;
-    const VolumeSlot &s = r->vols[timestep];
-    const void *planes[4] = {s.dev, s.chan[0], s.chan[1], s.chan[2]};
-    const IngestParams p = {1.f, 1.f, 0};
-    VR_HIP(r, hipMemsetAsync(ingest_hist(r), 0, 256 * sizeof(unsigned long long), r->stream));
-    for (int c = 0; c < r->channels; ++c)
-        VR_HIP(r, vr_launch_ingest_convert(make_vol_view(r, planes[c]), r->format, p, 0, ingest_hist(r), r->num_cus,
-                                           r->stream));
-    VR_HIP(r, ingest_read_hist(r, hist));
-    return VRHIP_OK;
-}
-
-double vrhip_last_ingest_seconds(const vrhip_renderer *r) { return r ? r->ingest_seconds : 0.0; }
 
 } // extern "C"
