@@ -33,6 +33,8 @@
 //  carry a frame index (vrhip_render_batch).
 //  The per-ray sequence of t values and of fp32 operations is exactly the reference's in every
 //  kernel, so the image is bit-identical whatever the schedule (budget, refill, batch, lists).
+//  Where that is enforced: the kernels share one batch ladder (VR_BATCH_PARAMS, VR_BATCH_PARAMS_SPLIT), one ray record
+//  (VR_PACK_RAY, VR_UNPACK_RAY) and one compositing step (composite, VR_COMPOSITE_QUAD), defined once below.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -107,9 +109,56 @@ struct RayDyn {   // marching state
 };
 #ifdef VR_RAYLEN
 #define VR_RAYLEN_INC(d) ((d).nsmp++)
+#define VR_RAYLEN_PACK(r, d) (r).pad = (d).nsmp     // (the diagnostic build carries the sample count in the key's place)
+#define VR_RAYLEN_UNPACK(rec, d) (d).nsmp = (rec).pad
 #else
 #define VR_RAYLEN_INC(d)
+#define VR_RAYLEN_PACK(r, d)
+#define VR_RAYLEN_UNPACK(rec, d)
 #endif
+
+// ---- The blocks the four kernels share, one definition each -- as MACROS, expanded in the kernel bodies.  As inlined
+// functions each of them, tried alone, changed the device code of some kernels (other registers, another order of
+// independent instructions: this compiler follows the order in which a kernel's locals come into being); expanded in
+// place the kernels compile to what they were (DESIGN.md "Build").  They name the kernels' locals (d, c, fr, vv, ...)
+// where the blocks did.
+
+// The ray record: ContRec `r` from the ray's RayDyn d, its pixel, its frame of the batch (state >> 8: states fit 8 bits)
+// and the sort key; and back: pixel and frame first, then the caller's setup_ray for that pixel (SETUP..., which leaves
+// c and a fresh d), then the state the record holds.  The only code that names ContRec's fields (the sort reads pad).
+#define VR_PACK_RAY(r, OUT_INDEX, FRAME, KEY)                 \
+    ContRec r;                                                \
+    r.pix = gx | (gy << 16);                                  \
+    r.out_index = OUT_INDEX;                                  \
+    r.state = d.state | (int32_t)(FRAME << 8);                \
+    r.t = d.t; r.t_exit = d.t_exit; r.alpha = d.alpha;        \
+    r.r0 = d.r0; r.r1 = d.r1; r.r2 = d.r2;                    \
+    r.cx = d.c0; r.cy = d.c1; r.cz = d.c2;                    \
+    r.tv0 = d.tv0; r.tv1 = d.tv1; r.tv2 = d.tv2;              \
+    r.pad = KEY;                                              \
+    VR_RAYLEN_PACK(r, d)
+#define VR_UNPACK_RAY(rec, FRAME, ...)                        \
+    gx = rec.pix & 0xffffu;                                   \
+    gy = rec.pix >> 16;                                       \
+    out_index = rec.out_index;                                \
+    FRAME = (uint32_t)rec.state >> 8;                         \
+    __VA_ARGS__                                               \
+    d.state = rec.state & 0xff;                               \
+    d.t = rec.t; d.t_exit = rec.t_exit; d.alpha = rec.alpha;  \
+    d.r0 = rec.r0; d.r1 = rec.r1; d.r2 = rec.r2;              \
+    d.c0 = rec.cx; d.c1 = rec.cy; d.c2 = rec.cz;              \
+    d.tv0 = rec.tv0; d.tv1 = rec.tv1; d.tv2 = rec.tv2;        \
+    VR_RAYLEN_UNPACK(rec, d)
+#define VR_SORT_KEY (fr.cost ? (uint32_t)fr.cost[(size_t)gy * fr.W + gx] : 0u)   // last frame's phase-2 rounds of the pixel
+
+// The wave-wide append: the first lane of MASK (not 0) moves the list's counter for all its lanes; `base` is the first
+// slot, lane's slot is base + VR_LANE_RANK.
+#define VR_WAVE_APPEND(base, COUNTER, MASK)                                    \
+    uint32_t base = 0;                                                         \
+    if (lane == (uint32_t)__builtin_ctzll(MASK))                               \
+        base = atomicAdd(COUNTER, (uint32_t)__builtin_popcountll(MASK));       \
+    base = __shfl(base, __builtin_ctzll(MASK), 64)
+#define VR_LANE_RANK(MASK) ((uint32_t)__builtin_popcountll(MASK & ((1ull << lane) - 1ull)))
 
 struct Grid {     // wave-uniform brick-grid constants
     int bw, bh, bd;
@@ -309,7 +358,23 @@ VR_DEV void after_segment(const RayCtx &c, RayDyn &d)
 // round (64 lanes x kBatch samples), for each of the 4 waves of a workgroup
 constexpr int kSlotFloats = 5;   // in: pos.xyz, opacity, owner|flags   out: ndl, spec, contour, op
 constexpr int kStageFloatsPerWave = 64 * kBatch * kSlotFloats;
-constexpr int kStageF4 = (kBlockDim / 64) * kStageFloatsPerWave / 4;   // float4 units, whole workgroup
+// Dynamic LDS of the marching kernels: [a stage per wave][the transfer function, tff_n float4][the skip bitmap, n_words
+// + 1 words, if it is kept there].  The host sizes a launch with march_lds_bytes; the workgroup (WAVES waves) takes its
+// pointers and fills the two tables together with VR_MARCH_LDS, which ends with the barrier.
+#define VR_MARCH_STAGE_F4(WAVES) ((WAVES) * kStageFloatsPerWave / 4)   // float4 units, whole workgroup
+inline size_t march_lds_bytes(int waves, uint32_t tff_n, uint32_t n_words, bool keep_skip)
+{
+    return ((size_t)VR_MARCH_STAGE_F4(waves) + tff_n) * sizeof(float4) + (keep_skip ? ((size_t)n_words + 1) * sizeof(uint32_t) : 0);
+}
+#define VR_MARCH_LDS(WAVES, KEEP_SKIP)                                                                          \
+    extern __shared__ float4 s_mem[];                                                                           \
+    float *s_stage = reinterpret_cast<float *>(s_mem) + (threadIdx.x >> 6) * kStageFloatsPerWave;               \
+    float4 *s_tff = s_mem + VR_MARCH_STAGE_F4(WAVES);                                                           \
+    uint32_t *s_skip = reinterpret_cast<uint32_t *>(s_tff + tf.tff_n);                                          \
+    for (uint32_t i = threadIdx.x; i < tf.tff_n; i += (WAVES) * 64) s_tff[i] = tf.tff[i];                       \
+    if (KEEP_SKIP)                                                                                              \
+        for (uint32_t i = threadIdx.x; i <= skip.n_words; i += (WAVES) * 64) s_skip[i] = skip.bits[i];          \
+    __syncthreads()
 
 // Up to kBatch consecutive samples of one ray (inner loop, :790-864): for each, the colour
 // already multiplied by the sample's opacity and the opacity.  Neither depends on the running
@@ -770,6 +835,13 @@ VR_DEV bool skip_empty_run_wide(const uint32_t (&masks)[4], const RayCtx &c, Ray
     return run;
 }
 
+// Is the empty-run lookahead on for this launch?  It needs the empty bits and the linear sampler's footprint; the
+// traffic-instrumented variant (INSTR 2) reproduces the reference's fetch set instead, and the XS modes that look at
+// every sample stay out: illumType 4, and showEss, which tracks the last sample.  SHOW_ESS: false in the split kernel,
+// which has no such term -- showEss renders in a single phase.  The three marching kernels and the host's launch info ask here.
+#define VR_LOOKAHEAD_ON(INSTR, XS, SHOW_ESS, EMPTY, RP) \
+    (INSTR != 2 && EMPTY != nullptr && RP.useLinear != 0 && !(XS && (RP.illumType == 4 || (SHOW_ESS && RP.showEss))))
+
 // The lookahead costs a few hundred instructions for the whole wave: it runs when at least half
 // of the sampling lanes expect their next sample to be empty (their last one was).
 VR_DEV bool lookahead_pays(bool sampling, bool guess_empty)
@@ -798,6 +870,34 @@ VR_DEV void composite(const RayCtx &c, RayDyn &d, float q0, float q1, float q2, 
         d.t = ti + c.stepSize;
     }
 }
+
+// The batch ladder, where every kernel gets the reference's t sequence from: ray parameters (t += stepSize, :879) and
+// validity -- the inner loop's condition (:790) and the break after a sample at or past tfar (:868) -- of the ray's next
+// kBatch samples, one lane per ray.  FIRST_VALID: the loop condition for the first one (and what gates the lane);
+// NO_SPECULATION: the traffic-instrumented variant must not touch speculative voxels.
+#define VR_BATCH_PARAMS(FIRST_VALID, NO_SPECULATION)                            \
+    tk[0] = d.t;                                                                \
+    vk[0] = FIRST_VALID;                                                        \
+    _Pragma("unroll")                                                           \
+    for (int k = 1; k < kBatch; ++k) {                                          \
+        tk[k] = tk[k - 1] + c.stepSize;                                         \
+        vk[k] = vk[k - 1] && !(tk[k - 1] >= c.tfar) && (tk[k] < d.t_exit);      \
+        if (NO_SPECULATION) vk[k] = false;                                      \
+    }
+// ... of the ray's next kSplit * kBatch samples, four lanes per ray (phase 2): lane `slot` of the quad keeps numbers
+// kBatch * slot .. kBatch * slot + kBatch - 1
+#define VR_BATCH_PARAMS_SPLIT(FIRST_VALID)                                              \
+    float tk[kBatch] = {0.f, 0.f, 0.f, 0.f};                                            \
+    bool vk[kBatch] = {false, false, false, false};                                     \
+    float tc = d.t;                                                                     \
+    bool v = FIRST_VALID;                                                               \
+    _Pragma("unroll")                                                                   \
+    for (int i = 0; i < kSplit * kBatch; ++i) {                                         \
+        if ((int)slot == i / kBatch) { tk[i % kBatch] = tc; vk[i % kBatch] = v; }       \
+        const float tn = tc + c.stepSize;                                               \
+        v = v && !(tc >= c.tfar) && (tn < d.t_exit);                                    \
+        tc = tn;                                                                        \
+    }
 
 // broadcast lane L of every quad (4 consecutive lanes): one DPP move, no LDS
 template <int L> VR_DEV float quad_bcast(float v)
@@ -995,6 +1095,16 @@ VR_DEV Grid make_grid(const BrickView &bricks, const vrhip_raycast_params &rcp, 
     return g;
 }
 
+// What a marching kernel derives once per launch from its arguments, the same in every ray.  (The pre-pass gets grid and
+// voxLen from the host: see there.)  sb: the skip bitmap where this kernel reads it, LDS or global.
+#define VR_MARCH_CONSTS(INSTR, ESS, TOUCHED)                                        \
+    const Vol<VT, INSTR, FP> vol = make_vol<VT, INSTR, FP>(vv, TOUCHED);            \
+    const f3 resf = mk3(vol.fw, vol.fh, vol.fd);                                    \
+    const f3 voxLen = mk3(1.f / vol.fw, 1.f / vol.fh, 1.f / vol.fd);                \
+    const float refInterval = 1.f / rc.samplingRate;                                \
+    const Grid grid = make_grid(bricks, rc, skip.n_words, ESS);                     \
+    const uint32_t *sb = SKIP_LDS ? s_skip : skip.bits
+
 VR_DEV void flush_counters(DevStats *stats, uint32_t lane, const unsigned long long (&c)[6])
 {
     for (int i = 0; i < 6; ++i) {
@@ -1156,22 +1266,11 @@ __global__ __launch_bounds__(kBlockDim) void vr_dda_prepass_kernel(
         if (m) {
             // (list q % kLiveLists: vr_internal.h)
             const uint32_t list = q % kLiveLists;
-            uint32_t base = 0;
-            if (lane == (uint32_t)__builtin_ctzll(m))
-                base = atomicAdd(fr.live_list_count + list * kLiveStride, (uint32_t)__builtin_popcountll(m));
-            base = __shfl(base, __builtin_ctzll(m), 64);
+            VR_WAVE_APPEND(base, fr.live_list_count + list * kLiveStride, m);
             base += list * live_list_cap(fr.n_wave_tiles);
             if (live) {
-                ContRec r;
-                r.pix = gx | (gy << 16);
-                r.out_index = (uint32_t)out_index;
-                r.state = d.state | (int32_t)(wt_frame(wt) << 8);
-                r.t = d.t; r.t_exit = d.t_exit; r.alpha = d.alpha;
-                r.r0 = d.r0; r.r1 = d.r1; r.r2 = d.r2;
-                r.cx = d.c0; r.cy = d.c1; r.cz = d.c2;
-                r.tv0 = d.tv0; r.tv1 = d.tv1; r.tv2 = d.tv2;
-                r.pad = 0;
-                fr.live_rays[base + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull))] = r;
+                VR_PACK_RAY(r, (uint32_t)out_index, wt_frame(wt), 0);
+                fr.live_rays[base + VR_LANE_RANK(m)] = r;
             }
         }
         return;
@@ -1221,24 +1320,12 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_rays_kernel(
     const uint32_t n_rays = ((longest + 63u) >> 6) * kLiveLists * 64u;
     if (n_rays == 0) return;
     const uint32_t list_cap = live_list_cap(fr.n_wave_tiles);
-    extern __shared__ float4 s_mem[];
-    float *s_stage = reinterpret_cast<float *>(s_mem) + (threadIdx.x >> 6) * kStageFloatsPerWave;
-    float4 *s_tff = s_mem + WAVES * kStageFloatsPerWave / 4;
-    uint32_t *s_skip = reinterpret_cast<uint32_t *>(s_tff + tf.tff_n);
-    for (uint32_t i = threadIdx.x; i < tf.tff_n; i += WAVES * 64) s_tff[i] = tf.tff[i];
-    if (SKIP_LDS)
-        for (uint32_t i = threadIdx.x; i <= skip.n_words; i += WAVES * 64) s_skip[i] = skip.bits[i];
-    __syncthreads();
+    VR_MARCH_LDS(WAVES, SKIP_LDS);
 
     const uint32_t lane = threadIdx.x & 63u;
     const int tffn = (int)tf.tff_n;
-    const Vol<VT, 0, FP> vol = make_vol<VT, 0, FP>(vv, nullptr);
-    const f3 resf = mk3(vol.fw, vol.fh, vol.fd);
-    const f3 voxLen = mk3(1.f / vol.fw, 1.f / vol.fh, 1.f / vol.fd);
-    const float refInterval = 1.f / rc.samplingRate;
-    const Grid grid = make_grid(bricks, rc, skip.n_words, true);
-    const uint32_t *sb = SKIP_LDS ? s_skip : skip.bits;
-    const bool skip_empty = cells.empty != nullptr && rp.useLinear != 0;
+    VR_MARCH_CONSTS(0, true, nullptr);
+    const bool skip_empty = VR_LOOKAHEAD_ON(0, false, true, cells.empty, rp);   // (this kernel has no INSTR or XS variants)
     const uint32_t budget = fr.round_budget ? fr.round_budget : 0xffffffffu;
     const uint32_t kRefillLanes = (fr.refill_min ? fr.refill_min : 16u) * 4u;   // idle lanes before a refill
 
@@ -1287,23 +1374,14 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_rays_kernel(
                         have = v < n_rays && pos < s_live_n[list];
                         if (have) {
                             const ContRec rec = fr.live_rays[list * list_cap + pos];
-                            gx = rec.pix & 0xffffu;
-                            gy = rec.pix >> 16;
-                            out_index = rec.out_index;
-                            frame_idx = (uint32_t)rec.state >> 8;
-                            if constexpr (VIEWS) {   // (the lanes of a wave may hold rays of different frames)
-                                const vrhip_camera_params fc = load_frame_cam<false>(fr.cams, frame_idx);
-                                setup_ray<true>(gx, gy, true, fr, fc, rp, rc, resf, voxLen, grid, c, d,
-                                                fr.seeds ? fr.seeds[frame_idx] : rp.seed);
-                            } else {
-                                setup_ray<true>(gx, gy, true, fr, cam, rp, rc, resf, voxLen, grid, c, d,
-                                                fr.seeds ? fr.seeds[frame_idx] : rp.seed);
-                            }
-                            d.state = rec.state & 0xff;
-                            d.t = rec.t; d.t_exit = rec.t_exit; d.alpha = rec.alpha;
-                            d.r0 = rec.r0; d.r1 = rec.r1; d.r2 = rec.r2;
-                            d.c0 = rec.cx; d.c1 = rec.cy; d.c2 = rec.cz;
-                            d.tv0 = rec.tv0; d.tv1 = rec.tv1; d.tv2 = rec.tv2;
+                            // (per lane: the lanes of a wave may hold rays of different frames)
+                            VR_UNPACK_RAY(rec, frame_idx,
+                                if constexpr (VIEWS) {
+                                    const vrhip_camera_params fc = load_frame_cam<false>(fr.cams, frame_idx);
+                                    setup_ray<true>(gx, gy, true, fr, fc, rp, rc, resf, voxLen, grid, c, d, fr.seeds ? fr.seeds[frame_idx] : rp.seed);
+                                } else {
+                                    setup_ray<true>(gx, gy, true, fr, cam, rp, rc, resf, voxLen, grid, c, d, fr.seeds ? fr.seeds[frame_idx] : rp.seed);
+                                });
                             fetch_skip_word(sb, grid, d);
                             my_rounds = 0;
                             guess_empty = true;
@@ -1335,21 +1413,10 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_rays_kernel(
             const bool susp = d.state != S_DONE && my_rounds >= budget;
             const unsigned long long cm = __ballot(susp);
             if (cm) {
-                uint32_t base = 0;
-                if (lane == (uint32_t)__builtin_ctzll(cm))
-                    base = atomicAdd(fr.cont_count, (uint32_t)__builtin_popcountll(cm));
-                base = __shfl(base, __builtin_ctzll(cm), 64);
+                VR_WAVE_APPEND(base, fr.cont_count, cm);
                 if (susp) {
-                    ContRec r;
-                    r.pix = gx | (gy << 16);
-                    r.out_index = out_index;
-                    r.state = d.state | (int32_t)(frame_idx << 8);
-                    r.t = d.t; r.t_exit = d.t_exit; r.alpha = d.alpha;
-                    r.r0 = d.r0; r.r1 = d.r1; r.r2 = d.r2;
-                    r.cx = d.c0; r.cy = d.c1; r.cz = d.c2;
-                    r.tv0 = d.tv0; r.tv1 = d.tv1; r.tv2 = d.tv2;
-                    r.pad = fr.cost ? (uint32_t)fr.cost[(size_t)gy * fr.W + gx] : 0u;   // sort key
-                    fr.cont[base + (uint32_t)__builtin_popcountll(cm & ((1ull << lane) - 1ull))] = r;
+                    VR_PACK_RAY(r, out_index, frame_idx, VR_SORT_KEY);
+                    fr.cont[base + VR_LANE_RANK(cm)] = r;
                     d.state = S_DONE;
                     have = false;
                 }
@@ -1384,13 +1451,7 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_rays_kernel(
         if (__ballot(ev)) {
             float tk[kBatch];
             bool vk[kBatch];
-            tk[0] = d.t;
-            vk[0] = ev && d.t < d.t_exit;   // inner loop condition (:790)
-#pragma unroll
-            for (int k = 1; k < kBatch; ++k) {
-                tk[k] = tk[k - 1] + c.stepSize;                                     // :879
-                vk[k] = vk[k - 1] && !(tk[k - 1] >= c.tfar) && (tk[k] < d.t_exit);  // :868, :790
-            }
+            VR_BATCH_PARAMS(ev && d.t < d.t_exit, false);
 #ifdef VR_MARCH_STATS
             for (int k = 0; k < kBatch; ++k) ms_acc[9] += vk[k] ? 1 : 0;      // valid samples evaluated (per lane: summed below)
 #endif
@@ -1429,32 +1490,16 @@ __global__ __launch_bounds__(kBlockDim) VR_OCC void vr_raycast_kernel(
     uint32_t *touched)
 {
     VR_ZERO_NEXT_CTRL(fr);   // (also when the pre-pass has done it: the block stays unused until the next set)
-    // LDS: [gradient staging, 4 waves][tff_n float4][skip words + 1]
-    extern __shared__ float4 s_mem[];
     VR_STAMP_DECL;
-    float *s_stage = reinterpret_cast<float *>(s_mem) + (threadIdx.x >> 6) * kStageFloatsPerWave;
-    float4 *s_tff = s_mem + kStageF4;
-    uint32_t *s_skip = reinterpret_cast<uint32_t *>(s_tff + tf.tff_n);
-    for (uint32_t i = threadIdx.x; i < tf.tff_n; i += kBlockDim) s_tff[i] = tf.tff[i];
-    if (ESS && SKIP_LDS)
-        for (uint32_t i = threadIdx.x; i <= skip.n_words; i += kBlockDim) s_skip[i] = skip.bits[i];
-    __syncthreads();
+    VR_MARCH_LDS(kBlockDim / 64, ESS && SKIP_LDS);
     VR_STAMP(8);
 
     const uint32_t lane = threadIdx.x & 63u;
     const int tffn = (int)tf.tff_n;
     unsigned long long c_taken = 0, c_nominal = 0, c_shaded = 0, c_bricks = 0, c_skipped = 0,
                        c_hit = 0;
-    const Vol<VT, INSTR, FP> vol = make_vol<VT, INSTR, FP>(vv, touched);
-    const f3 resf = mk3(vol.fw, vol.fh, vol.fd);
-    const f3 voxLen = mk3(1.f / vol.fw, 1.f / vol.fh, 1.f / vol.fd);
-    const float refInterval = 1.f / rc.samplingRate;
-    const Grid grid = make_grid(bricks, rc, skip.n_words, ESS);
-    const uint32_t *sb = SKIP_LDS ? s_skip : skip.bits;
-    // empty-run skipping needs the linear sampler's footprint; the traffic-instrumented variant
-    // reproduces the reference's fetch set instead
-    const bool skip_empty = INSTR != 2 && cells.empty != nullptr && rp.useLinear != 0 &&
-                            !(XS && (rp.illumType == 4 || rp.showEss));   // showEss tracks every sample
+    VR_MARCH_CONSTS(INSTR, ESS, touched);
+    const bool skip_empty = VR_LOOKAHEAD_ON(INSTR, XS, true, cells.empty, rp);
 
     // every wave pulls 8x8 patches until the queue is drained (exit condition reached by every
     // wave: the head only grows).  The next ticket is drawn while the current patch is marched,
@@ -1536,15 +1581,7 @@ __global__ __launch_bounds__(kBlockDim) VR_OCC void vr_raycast_kernel(
                 // ---- up to kBatch consecutive samples of this ray per round
                 float tk[kBatch];
                 bool vk[kBatch], litk[kBatch];
-                tk[0] = d.t;
-                vk[0] = d.t < d.t_exit;   // inner loop condition (:790)
-#pragma unroll
-                for (int k = 1; k < kBatch; ++k) {
-                    tk[k] = tk[k - 1] + c.stepSize;                                     // :879
-                    vk[k] = vk[k - 1] && !(tk[k - 1] >= c.tfar) && (tk[k] < d.t_exit);  // :868, :790
-                    // the traffic-instrumented variant must not touch speculative voxels
-                    if (INSTR == 2) vk[k] = false;
-                }
+                VR_BATCH_PARAMS(d.t < d.t_exit, INSTR == 2);
                 float p0[kBatch], p1[kBatch], p2[kBatch], opk[kBatch];
                 eval_batch<VT, INSTR, XS, FP>(vol, s_tff, tffn, s_stage, c, rp, rc, refInterval, tk, vk, p0, p1, p2,
                                       opk, litk);
@@ -1568,24 +1605,10 @@ __global__ __launch_bounds__(kBlockDim) VR_OCC void vr_raycast_kernel(
         const bool cont = suspended && d.state != S_DONE;
         const unsigned long long cm = __ballot(cont);
         if (cm) {
-            uint32_t base = 0;
-            if (lane == (uint32_t)__builtin_ctzll(cm))
-                base = atomicAdd(fr.cont_count, (uint32_t)__builtin_popcountll(cm));
-            base = __shfl(base, __builtin_ctzll(cm), 64);
+            VR_WAVE_APPEND(base, fr.cont_count, cm);
             if (cont) {
-                ContRec r;
-                r.pix = gx | (gy << 16);
-                r.out_index = wt.out_base + ly * fr.out_stride + lx;
-                r.state = d.state | (int32_t)(frame_idx << 8);   // (states fit 8 bits)
-                r.t = d.t; r.t_exit = d.t_exit; r.alpha = d.alpha;
-                r.r0 = d.r0; r.r1 = d.r1; r.r2 = d.r2;
-                r.cx = d.c0; r.cy = d.c1; r.cz = d.c2;
-                r.tv0 = d.tv0; r.tv1 = d.tv1; r.tv2 = d.tv2;
-                r.pad = fr.cost ? (uint32_t)fr.cost[(size_t)gy * fr.W + gx] : 0u;   // sort key
-#ifdef VR_RAYLEN
-                r.pad = d.nsmp;
-#endif
-                const uint32_t rank = (uint32_t)__builtin_popcountll(cm & ((1ull << lane) - 1ull));
+                VR_PACK_RAY(r, wt.out_base + ly * fr.out_stride + lx, frame_idx, VR_SORT_KEY);
+                const uint32_t rank = VR_LANE_RANK(cm);
                 fr.cont[base + rank] = r;
             }
         }
@@ -1626,6 +1649,16 @@ VR_DEV void composite_from(const RayCtx &c, RayDyn &d, const float (&p0)[kBatch]
     }
 }
 
+// ... of the whole quad: the ray's kSplit * kBatch samples of this round in ray order; F_LAST, O_LAST: flag and opacity
+// of the 16th of them (lane 3 of the quad, slot kBatch - 1), for the next round's guess
+#define VR_COMPOSITE_QUAD(COUNT, F_LAST, O_LAST)                                    \
+    composite_from<0>(c, d, p0, p1, p2, opk, tk, fl, COUNT, c_taken, c_shaded);     \
+    composite_from<1>(c, d, p0, p1, p2, opk, tk, fl, COUNT, c_taken, c_shaded);     \
+    composite_from<2>(c, d, p0, p1, p2, opk, tk, fl, COUNT, c_taken, c_shaded);     \
+    composite_from<3>(c, d, p0, p1, p2, opk, tk, fl, COUNT, c_taken, c_shaded);     \
+    const int F_LAST = quad_bcast<3>(fl[kBatch - 1]);                               \
+    const float O_LAST = quad_bcast<3>(opk[kBatch - 1])
+
 // Resumes suspended rays with kSplit = 4 lanes per ray (16 rays per wave).  The 4 lanes of a ray
 // hold the same state and take the same decisions; lane `slot` evaluates samples
 // 4*slot .. 4*slot+3 of the next 16 consecutive samples (same batch code as phase 1), then every
@@ -1641,29 +1674,16 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_split_kernel(
     static_assert(kSplit == 4 && (kBatch == 4 || kBatch == 8), "phase 2 is written for 4 lanes x 4 (8: A/B build) samples");
     const uint32_t n_rays = *fr.cont_count;   // written by phase 1 (previous kernel on the stream)
     if (n_rays == 0) return;
-    extern __shared__ float4 s_mem[];
     VR_STAMP_DECL;
-    float *s_stage = reinterpret_cast<float *>(s_mem) + (threadIdx.x >> 6) * kStageFloatsPerWave;
-    float4 *s_tff = s_mem + WAVES * kStageFloatsPerWave / 4;
-    uint32_t *s_skip = reinterpret_cast<uint32_t *>(s_tff + tf.tff_n);
-    for (uint32_t i = threadIdx.x; i < tf.tff_n; i += WAVES * 64) s_tff[i] = tf.tff[i];
-    if (ESS && SKIP_LDS)
-        for (uint32_t i = threadIdx.x; i <= skip.n_words; i += WAVES * 64) s_skip[i] = skip.bits[i];
-    __syncthreads();
+    VR_MARCH_LDS(WAVES, ESS && SKIP_LDS);
 
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t slot = lane & (kSplit - 1);   // 16 rays per wave, 4 lanes each
     constexpr uint32_t kRaysPerWave = 64 / kSplit;
     const int tffn = (int)tf.tff_n;
     unsigned long long c_taken = 0, c_shaded = 0, c_bricks = 0, c_skipped = 0;
-    const Vol<VT, INSTR, FP> vol = make_vol<VT, INSTR, FP>(vv, touched);
-    const f3 resf = mk3(vol.fw, vol.fh, vol.fd);
-    const f3 voxLen = mk3(1.f / vol.fw, 1.f / vol.fh, 1.f / vol.fd);
-    const float refInterval = 1.f / rc.samplingRate;
-    const Grid grid = make_grid(bricks, rc, skip.n_words, ESS);
-    const uint32_t *sb = SKIP_LDS ? s_skip : skip.bits;
-    const bool skip_empty = INSTR != 2 && cells.empty != nullptr && rp.useLinear != 0 &&
-                            !(XS && rp.illumType == 4);
+    VR_MARCH_CONSTS(INSTR, ESS, touched);
+    const bool skip_empty = VR_LOOKAHEAD_ON(INSTR, XS, false, cells.empty, rp);
     // Rays are handed out one by one from the sorted list: when `refill_min` ray slots (quads) of
     // the wave are idle they retire their rays and take the next ones (their set-up runs
     // together).  With the default, 16, a wave refills when all its rays are done, but draws as
@@ -1723,26 +1743,14 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_split_kernel(
                         if (have) {
                             const uint32_t rix = fr.order ? fr.order[ri] : ri;
                             const ContRec rec = fr.cont[rix];
-                            gx = rec.pix & 0xffffu;
-                            gy = rec.pix >> 16;
-                            out_index = rec.out_index;
-                            const uint32_t f = (uint32_t)rec.state >> 8;
-                            if constexpr (VIEWS) {   // (per lane: the quads of a wave may hold rays of different frames)
-                                const vrhip_camera_params fc = load_frame_cam<false>(fr.cams, f);
-                                setup_ray<ESS>(gx, gy, true, fr, fc, rp, rc, resf, voxLen, grid, c, d,
-                                               fr.seeds ? fr.seeds[f] : rp.seed);
-                            } else {
-                                setup_ray<ESS>(gx, gy, true, fr, cam, rp, rc, resf, voxLen, grid, c, d,
-                                               fr.seeds ? fr.seeds[f] : rp.seed);
-                            }
-                            d.state = rec.state & 0xff;
-                            d.t = rec.t; d.t_exit = rec.t_exit; d.alpha = rec.alpha;
-                            d.r0 = rec.r0; d.r1 = rec.r1; d.r2 = rec.r2;
-                            d.c0 = rec.cx; d.c1 = rec.cy; d.c2 = rec.cz;
-                            d.tv0 = rec.tv0; d.tv1 = rec.tv1; d.tv2 = rec.tv2;
-#ifdef VR_RAYLEN
-                            d.nsmp = rec.pad;
-#endif
+                            // (per lane: the quads of a wave may hold rays of different frames)
+                            VR_UNPACK_RAY(rec, const uint32_t f,
+                                if constexpr (VIEWS) {
+                                    const vrhip_camera_params fc = load_frame_cam<false>(fr.cams, f);
+                                    setup_ray<ESS>(gx, gy, true, fr, fc, rp, rc, resf, voxLen, grid, c, d, fr.seeds ? fr.seeds[f] : rp.seed);
+                                } else {
+                                    setup_ray<ESS>(gx, gy, true, fr, cam, rp, rc, resf, voxLen, grid, c, d, fr.seeds ? fr.seeds[f] : rp.seed);
+                                });
                             if (ESS) fetch_skip_word(sb, grid, d);
                             my_rounds = 0;
                             guess_empty = true;
@@ -1798,17 +1806,7 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_split_kernel(
                 // eval_back): the dense pass over the gathered samples is run by all 64 lanes, also those
                 // of rays that step over empty runs or have ended
                 if (__ballot(ev2)) {
-                    float tk[kBatch] = {0.f, 0.f, 0.f, 0.f};
-                    bool vk[kBatch] = {false, false, false, false};
-                    float tc = d.t;
-                    bool v = ev2 && d.t < d.t_exit;
-#pragma unroll
-                    for (int i = 0; i < kSplit * kBatch; ++i) {
-                        if ((int)slot == i / kBatch) { tk[i % kBatch] = tc; vk[i % kBatch] = v; }
-                        const float tn = tc + c.stepSize;
-                        v = v && !(tc >= c.tfar) && (tn < d.t_exit);
-                        tc = tn;
-                    }
+                    VR_BATCH_PARAMS_SPLIT(ev2 && d.t < d.t_exit);
                     EvalFront ef;
                     const uint32_t ns = eval_front<VT, FP>(vol, s_tff, tffn, s_stage, c, rp, tk, vk, ev2, ef);
                     if (ns) eval_dense<VT, FP>(vol, s_stage, c, refInterval, ns);
@@ -1818,13 +1816,8 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_split_kernel(
                     int fl[kBatch];
 #pragma unroll
                     for (int k = 0; k < kBatch; ++k) fl[k] = (vk[k] ? 1 : 0) | ((ef.lit[k] && rp.illumType == 1) ? 2 : 0);
-                    composite_from<0>(c, d, p0, p1, p2, opk, tk, fl, false, c_taken, c_shaded);
-                    composite_from<1>(c, d, p0, p1, p2, opk, tk, fl, false, c_taken, c_shaded);
-                    composite_from<2>(c, d, p0, p1, p2, opk, tk, fl, false, c_taken, c_shaded);
-                    composite_from<3>(c, d, p0, p1, p2, opk, tk, fl, false, c_taken, c_shaded);
-                    {   // the ray's 16th sample of this round: lane 3 of the quad, slot kBatch - 1
-                        const int f3v = quad_bcast<3>(fl[kBatch - 1]);
-                        const float o3 = quad_bcast<3>(opk[kBatch - 1]);
+                    {
+                        VR_COMPOSITE_QUAD(false, f3v, o3);
                         if (ev2) {
                             if (f3v & 1) guess_empty = o3 == 0.f && cool == 0u;
                             if (cool) --cool;
@@ -1835,19 +1828,7 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_split_kernel(
                 }
             } else
             if (d.state == S_SAMPLE && !more_empty) {
-                // parameters (t += stepSize, :879) and validity (:790, :868) of the ray's next 16
-                // samples; this lane keeps numbers 4*slot .. 4*slot+3
-                float tk[kBatch] = {0.f, 0.f, 0.f, 0.f};
-                bool vk[kBatch] = {false, false, false, false};
-                float tc = d.t;
-                bool v = d.t < d.t_exit;
-#pragma unroll
-                for (int i = 0; i < kSplit * kBatch; ++i) {
-                    if ((int)slot == i / kBatch) { tk[i % kBatch] = tc; vk[i % kBatch] = v; }
-                    const float tn = tc + c.stepSize;
-                    v = v && !(tc >= c.tfar) && (tn < d.t_exit);
-                    tc = tn;
-                }
+                VR_BATCH_PARAMS_SPLIT(d.t < d.t_exit);
                 if (INSTR == 2) {   // no speculative voxel touches: one sample per round
 #pragma unroll
                     for (int k = 0; k < kBatch; ++k) vk[k] = vk[k] && slot == 0 && k == 0;
@@ -1860,13 +1841,8 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_split_kernel(
                 int fl[kBatch];
 #pragma unroll
                 for (int k = 0; k < kBatch; ++k) fl[k] = (vk[k] ? 1 : 0) | (litk[k] ? 2 : 0);
-                composite_from<0>(c, d, p0, p1, p2, opk, tk, fl, count, c_taken, c_shaded);
-                composite_from<1>(c, d, p0, p1, p2, opk, tk, fl, count, c_taken, c_shaded);
-                composite_from<2>(c, d, p0, p1, p2, opk, tk, fl, count, c_taken, c_shaded);
-                composite_from<3>(c, d, p0, p1, p2, opk, tk, fl, count, c_taken, c_shaded);
-                {   // the ray's 16th sample of this round: lane 3 of the quad, slot kBatch - 1
-                    const int f3v = quad_bcast<3>(fl[kBatch - 1]);
-                    const float o3 = quad_bcast<3>(opk[kBatch - 1]);
+                {
+                    VR_COMPOSITE_QUAD(count, f3v, o3);
                     if (f3v & 1) guess_empty = o3 == 0.f && cool == 0u;
                     if (cool) --cool;
                 }
@@ -1890,11 +1866,7 @@ hipError_t prepare_variant(K kernel, size_t lds, int *nb_out, const char *what, 
 }
 
 // dynamic LDS of the marching kernels: a stage per wave, the transfer function, the skip bitmap if it is kept there
-inline size_t march_lds(int waves, const RaycastLaunch &a, bool skip_lds)
-{
-    return (size_t)waves * kStageFloatsPerWave * sizeof(float) + (size_t)a.tf.tff_n * sizeof(float4) +
-           (skip_lds ? ((size_t)a.skip.n_words + 1) * sizeof(uint32_t) : 0);
-}
+inline size_t march_lds(int waves, const RaycastLaunch &a, bool skip_lds) { return march_lds_bytes(waves, a.tf.tff_n, a.skip.n_words, skip_lds); }
 // does a workgroup of kWavesWide waves with the skip bitmap fit a CU's LDS?
 inline bool wide_fits_lds(const RaycastLaunch &a) { return march_lds(kWavesWide, a, true) <= (size_t)160 * 1024; }
 
@@ -1938,9 +1910,7 @@ hipError_t launch_variant(const RaycastLaunch &a, hipStream_t stream)
         li.phase1_waves = 4;
         li.phase2_waves = a.frame.round_budget ? (uint32_t)waves2 : 0u;
         li.sorted_phase2 = (a.frame.round_budget && a.frame.order) ? 1u : 0u;
-        // the lookahead's condition in the kernels: cells.empty && useLinear (and INSTR != 2, not the XS modes that track every sample)
-        li.empty_skip = (INSTR != 2 && a.cells.empty != nullptr && a.render.useLinear != 0 &&
-                         !(XS && (a.render.illumType == 4 || a.render.showEss))) ? 1u : 0u;
+        li.empty_skip = VR_LOOKAHEAD_ON(INSTR, XS, true, a.cells.empty, a.render) ? 1u : 0u;
     }
     // the events of the frame's timing ride on the launches themselves (RaycastLaunch::stop_event, start_event)
     hipEvent_t start_ev = (a.bind_events && a.start_bound) ? a.start_event : nullptr;
