@@ -128,6 +128,22 @@ public:
     void renderFramesTiles(size_t width, size_t height, size_t tile_w, size_t tile_h,
                            const std::vector<unsigned int> &tile_ids, const std::vector<unsigned int> &seeds,
                            const std::vector<std::array<float, 16>> &views, float *dev_out, size_t frame_stride = 0);
+    // ---- 8-bit frames: the reference's output image is CL_UNORM_INT8 (volumerendercl.cpp:468-478), which is what its
+    // runRaycastNoGL actually reads back (:568-607) and its GUI shows, saves and records.  Per channel 0 for a NaN, else
+    // rint(clamp(f * 255.0f, 0, 255)), ties to even (vrhip.h "8-bit frames"); quantised on the GPU.
+    // runRaycastNoGL with `output` resized to width*height*4 bytes, R G B A per pixel, row 0 = top.  The frame buffer
+    // keeps the float frame: accumulation and image-order ESS carry on as with runRaycast.
+    void runRaycastRGBA8(size_t width, size_t height, std::vector<unsigned char> &output);
+    // the bytes of the frame the frame buffer holds (vrhip_frame_rgba8): what the last runRaycast / runRaycastNoGL /
+    // runRaycastRGBA8 / whole-frame renderSamples of this size rendered; nothing is rendered, nothing advances
+    void frameRGBA8(size_t width, size_t height, std::vector<unsigned char> &output);
+    // renderFrames with the frames also as 8-bit pixels: the floats into DEVICE memory dev_frames[f][height][width][4]
+    // as renderFrames writes them, their 8-bit twins into DEVICE memory dev_out[f][height][width][4] (bytes) on the
+    // same stream; returns without waiting
+    void renderFramesRGBA8(size_t width, size_t height, const std::vector<unsigned int> &seeds, float *dev_frames,
+                           unsigned char *dev_out);
+    void renderFramesRGBA8(size_t width, size_t height, const std::vector<unsigned int> &seeds,
+                           const std::vector<std::array<float, 16>> &views, float *dev_frames, unsigned char *dev_out);
     // ---- the progressive path tracer (technique 1), many samples per call (vrhip_render_samples): seeds.size()
     // consecutive iterations of the accumulated image -- sample k with jitter seed seeds[k] at iteration
     // (current iteration + k) -- in as few launch sets as possible, bit for bit what seeds.size() runRaycastNoGL calls

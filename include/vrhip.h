@@ -286,6 +286,52 @@ int vrhip_pack_tiles(vrhip_renderer *r, void *hip_stream, const float *tiles_dev
 int vrhip_message_positions(vrhip_renderer *r, void *hip_stream, const float *const *msgs_dev,
                             const uint32_t *counts_host, uint32_t world, uint32_t n_slots, int32_t *pos_dev);
 
+/* ---- 8-bit frames (the reference's output image is CL_UNORM_INT8, volumerendercl.cpp:468-478: what its GUI shows,
+ * saves and records; the float frame above stays the parity surface) -------------------------------------------
+ * One conversion everywhere, per channel of an fp32 pixel: q(f) = 0 for a NaN, else (uint8) rint(clamp(f * 255.0f,
+ * 0, 255)) -- ONE rounded fp32 multiply, a clamp, round-half-to-even: OpenCL's convert_uchar_sat_rte(f * 255.0f),
+ * what write_imagef does on such an image.  +inf gives 255; -inf, negatives and -0.0 give 0.  A pixel is the bytes
+ * R, G, B, A in memory order, i.e. the word r | g << 8 | b << 16 | a << 24.  (numpy: frontend.quantise_rgba8.) */
+/* Quantise `rows` blocks of `row_pixels` RGBA float pixels, `src_stride` (>= row_pixels) pixels apart in src_dev
+ * (device memory, 16-byte aligned) and dense in dst: a frame (rows = 1), the frames of a batch rendered with
+ * out_frame_stride, a tile layout.  One kernel on hip_stream (a hipStream_t; NULL = legacy default stream).
+ * dst_is_device != 0: dst is device memory (4-byte aligned) and the call returns without synchronising; else dst is
+ * host memory: the bytes travel through a pinned staging block the renderer owns (grown on demand, freed with the
+ * renderer) and the call returns after the copy has completed.  A NULL pointer, src_stride < row_pixels or
+ * rows x row_pixels >= 2^32: VRHIP_ERR_INVALID. */
+int vrhip_quantise_rgba8(vrhip_renderer *r, void *hip_stream, const float *src_dev, uint32_t rows,
+                         uint32_t row_pixels, uint32_t src_stride, uint8_t *dst, int dst_is_device);
+/* runRaycastNoGL as the reference reads it back (volumerendercl.cpp:568-607): exactly vrhip_render_frame with
+ * out_rgba == NULL, then the renderer's frame buffer quantised on the same stream into out_rgba8 (width * height * 4
+ * bytes, row 0 = top; host memory, or device memory when out_is_device != 0).  The float frame buffer keeps the
+ * unquantised frame: progressive accumulation and image-order ESS carry on across calls bit for bit as with
+ * vrhip_render_frame. */
+int vrhip_render_frame_rgba8(vrhip_renderer *r, uint32_t width, uint32_t height, uint8_t *out_rgba8,
+                             int out_is_device);
+/* The second half of it alone: the frame the renderer's frame buffer holds -- what the last vrhip_render_frame
+ * (with out_rgba NULL or host memory), vrhip_render_frame_rgba8 or whole-frame vrhip_render_samples of this size
+ * left there -- quantised on the renderer's stream into out_rgba8; nothing is rendered.  For a caller that has the
+ * float frame already and wants its bytes too (a screenshot of what is shown).  No frame of width x height in the
+ * frame buffer: VRHIP_ERR_NODATA. */
+int vrhip_frame_rgba8(vrhip_renderer *r, uint32_t width, uint32_t height, uint8_t *out_rgba8, int out_is_device);
+/* Multi-GPU, every rank: the 8-bit twin of vrhip_pack_tiles.  tiles_dev holds the FLOAT tiles the rank has rendered;
+ * the message is [spad slot numbers of the whole tiles (int32) | n_slots pixels, one word each | the whole tiles,
+ * tile_pixels words each], spad = n_slots rounded up to a multiple of 4: a tile travels as its one pixel when its
+ * QUANTISED pixels are all equal (so also one whose floats differ only below the rounding).  msg_dev holds spad +
+ * n_slots + n_slots tile_pixels words (the worst case); count_dev receives the number c of whole tiles: the first
+ * spad + n_slots + c tile_pixels words are what has to travel.  scratch_dev: n_slots int32.  All device memory,
+ * tiles_dev and msg_dev 16-byte aligned; three small kernels on hip_stream.  The head is the float message's:
+ * vrhip_message_positions reads both formats. */
+int vrhip_pack_tiles_rgba8(vrhip_renderer *r, void *hip_stream, const float *tiles_dev, uint32_t n_slots,
+                           uint32_t tile_pixels, int32_t *scratch_dev, uint32_t *msg_dev, uint32_t *count_dev);
+/* Multi-GPU, rank 0: the 8-bit twin of vrhip_assemble_batch.  Arguments as there, with message r = [maxc slot
+ * numbers | S = n_frames x cap words, one per tile slot | whole tiles of tile_w x tile_h words] (16-byte aligned,
+ * maxc a multiple of 4) and frames_dev[n_frames][height][width] words (4-byte aligned). */
+int vrhip_assemble_batch_rgba8(vrhip_renderer *r, void *hip_stream, const uint32_t *const *msgs_dev, uint32_t world,
+                               uint32_t n_frames, uint32_t cap, uint32_t maxc, const int32_t *pos_dev,
+                               const uint32_t *rank_slot_of_tile_dev, uint32_t width, uint32_t height,
+                               uint32_t tile_w, uint32_t tile_h, uint8_t *frames_dev);
+
 /* A batch of n_frames <= 256 INDEPENDENT frames (n_frames x pixels per frame < 2^32) -- same camera and parameters, frame f with jitter
  * seed seeds[f] (rendering_params.seed is not used) -- in ONE set of launches: the work queue holds
  * every patch once per frame, so a small tile share still fills the GPU and the latency chain of

@@ -83,6 +83,14 @@ SYMBOLS = {
                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                        C.c_uint32, C.c_void_p]),
     "vrhip_pack_tiles": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vrhip_quantise_rgba8": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int]),
+    "vrhip_render_frame_rgba8": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int]),
+    "vrhip_frame_rgba8": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int]),
+    "vrhip_pack_tiles_rgba8": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "vrhip_assemble_batch_rgba8": (C.c_int, [_H, C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32,
+                                             C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                             C.c_uint32, C.c_void_p]),
     "vrhip_message_positions": (C.c_int, [_H, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint32,
                                           C.c_uint32, C.c_void_p]),
     "vrhip_assemble_frame": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,

@@ -527,6 +527,43 @@ void VolumeRenderCL::renderFramesTiles(size_t width, size_t height, size_t tile_
                                                    uint32_t(seeds.size()), dev_out, uint32_t(frame_stride)));
 }
 
+// ---- 8-bit frames (vrhip_render_frame_rgba8, vrhip_quantise_rgba8)
+
+void VolumeRenderCL::runRaycastRGBA8(size_t width, size_t height, std::vector<unsigned char> &output)
+{
+    if (!_volLoaded) return;
+    beginFrame();
+    output.resize(width * height * 4);
+    check("runRaycastRGBA8", vrhip_render_frame_rgba8(_r, uint32_t(width), uint32_t(height), output.data(), 0));
+    _rendering_params.iteration++;
+}
+
+void VolumeRenderCL::frameRGBA8(size_t width, size_t height, std::vector<unsigned char> &output)
+{
+    if (!_volLoaded) return;
+    output.resize(width * height * 4);
+    check("frameRGBA8", vrhip_frame_rgba8(_r, uint32_t(width), uint32_t(height), output.data(), 0));
+}
+
+void VolumeRenderCL::renderFramesRGBA8(size_t width, size_t height, const std::vector<unsigned int> &seeds,
+                                       float *dev_frames, unsigned char *dev_out)
+{
+    if (!_volLoaded) return;
+    renderFrames(width, height, seeds, dev_frames);
+    check("renderFramesRGBA8", vrhip_quantise_rgba8(_r, stream(), dev_frames, uint32_t(seeds.size()), uint32_t(width * height),
+                                                    uint32_t(width * height), dev_out, 1));
+}
+
+void VolumeRenderCL::renderFramesRGBA8(size_t width, size_t height, const std::vector<unsigned int> &seeds,
+                                       const std::vector<std::array<float, 16>> &views, float *dev_frames,
+                                       unsigned char *dev_out)
+{
+    if (!_volLoaded) return;
+    renderFrames(width, height, seeds, views, dev_frames);
+    check("renderFramesRGBA8", vrhip_quantise_rgba8(_r, stream(), dev_frames, uint32_t(seeds.size()), uint32_t(width * height),
+                                                    uint32_t(width * height), dev_out, 1));
+}
+
 // ---- the progressive path tracer, many samples per call (vrhip_render_samples)
 
 void VolumeRenderCL::renderSamples(size_t width, size_t height, const std::vector<unsigned int> &seeds,

@@ -376,6 +376,30 @@ void write_ppm(const std::string &path, const std::vector<float> &rgba, size_t w
     }
 }
 
+// --rgba8: PREFIX.ppm from the 8-bit pixels, their R, G, B bytes as they are
+void write_ppm_rgba8(const std::string &path, const std::vector<unsigned char> &rgba8, size_t w, size_t h)
+{
+    std::ofstream f(path, std::ios::binary);
+    f << "P6\n" << w << " " << h << "\n255\n";
+    std::vector<unsigned char> rgb(w * h * 3);
+    for (size_t i = 0; i < w * h; ++i)
+        for (size_t c = 0; c < 3; ++c) rgb[i * 3 + c] = rgba8[i * 4 + c];
+    f.write(reinterpret_cast<const char *>(rgb.data()), std::streamsize(rgb.size()));
+}
+
+// --rgba8: PREFIX.rgba.u8 (the last frame), PREFIX.frames.rgba.u8 (all frames of a multi-frame run) and PREFIX.ppm
+void write_rgba8(const std::string &out, const std::vector<unsigned char> &frame8, const std::vector<unsigned char> &all8,
+                 size_t w, size_t h)
+{
+    if (!all8.empty()) {
+        std::ofstream af(out + ".frames.rgba.u8", std::ios::binary);
+        af.write(reinterpret_cast<const char *>(all8.data()), std::streamsize(all8.size()));
+    }
+    std::ofstream raw(out + ".rgba.u8", std::ios::binary);
+    raw.write(reinterpret_cast<const char *>(frame8.data()), std::streamsize(frame8.size()));
+    write_ppm_rgba8(out + ".ppm", frame8, w, h);
+}
+
 [[noreturn]] void usage()
 {
     std::cerr <<
@@ -420,6 +444,9 @@ void write_ppm(const std::string &path, const std::vector<float> &rgba, size_t w
         "                                           them -- or of an N-view turntable about the axis from the start\n"
         "                                           camera; --frames is ignored, the frames go to PREFIX.frames.rgba.f32;\n"
         "                                           --dump-views writes the 16-float matrices and exits, no GPU)\n"
+        "         [--rgba8]                        (also the frame as 8-bit RGBA, the reference's display format, quantised\n"
+        "                                           on the GPU: PREFIX.rgba.u8 (W*H*4 bytes), with several frames\n"
+        "                                           PREFIX.frames.rgba.u8, and PREFIX.ppm from those bytes; not with --ranks)\n"
         "writes PREFIX.rgba.f32 (W*H*4 float32, row 0 = top), PREFIX.ppm and prints one JSON line\n";
     std::exit(2);
 }
@@ -443,7 +470,7 @@ int main(int argc, char **argv)
     int frames = 1, device = 0, ranks = 0;
     size_t tile = 64;
     bool loopback = false, force_gather = false;
-    bool independent = false, bench = false;
+    bool independent = false, bench = false, rgba8 = false;
     int frames_per_launch = 0, frames_in_flight = 2, round_budget = 48, samples_per_launch = 0;
     double root_share = 1.0;
     double rate = 1.5;
@@ -498,6 +525,7 @@ int main(int argc, char **argv)
         else if (a == "--force-gather") force_gather = true;
         else if (a == "--independent") independent = true;
         else if (a == "--bench") bench = true;
+        else if (a == "--rgba8") rgba8 = true;
         else if (a == "--frames-per-launch") { need(i, 1); frames_per_launch = std::atoi(argv[++i]); }
         else if (a == "--samples-per-launch") { need(i, 1); samples_per_launch = std::atoi(argv[++i]); if (samples_per_launch < 0) usage(); }
         else if (a == "--frames-in-flight") { need(i, 1); frames_in_flight = std::atoi(argv[++i]); }
@@ -515,6 +543,11 @@ int main(int argc, char **argv)
         else usage();
     }
     if (have_path_arg && (camera_path.empty() || have_orbit)) usage();
+    if (rgba8 && ranks > 0) {
+        std::cerr << "--rgba8 cannot be combined with --ranks: the C++ tile gather carries float pixels "
+                     "(8-bit frames over several GPUs: the Python TileDriver, pixel_format=\"rgba8\")" << std::endl;
+        return 2;
+    }
     if (have_orbit && (orbit_n < 1 || orbit_n > 1 << 20 ||
                        orbit_axis[0] * orbit_axis[0] + orbit_axis[1] * orbit_axis[1] + orbit_axis[2] * orbit_axis[2] == 0.0))
         usage();
@@ -789,6 +822,7 @@ int main(int argc, char **argv)
         VolumeRenderCL vr;
         if (!setup(vr, device)) return 0;
         std::vector<float> frame, all_frames;
+        std::vector<unsigned char> frame8, all_frames8;   // --rgba8
         double kernel_s = 0.0;
         if (frames_per_launch > 0) {
             // ---- the throughput path on one GPU: F renderers over one shared volume take launch sets of <= K
@@ -813,9 +847,11 @@ int main(int argc, char **argv)
             };
             hip_ok(hipSetDevice(device), "hipSetDevice");
             std::vector<float *> blocks(F, nullptr);
+            std::vector<unsigned char *> blocks8(F, nullptr);   // --rgba8: the 8-bit twins of a set's frames
             std::vector<hipStream_t> streams(F);
             for (size_t j = 0; j < F; ++j) {
                 hip_ok(hipMalloc(reinterpret_cast<void **>(&blocks[j]), K * W * H * 4 * sizeof(float)), "hipMalloc frames");
+                if (rgba8) hip_ok(hipMalloc(reinterpret_cast<void **>(&blocks8[j]), K * W * H * 4), "hipMalloc 8-bit frames");
                 streams[j] = static_cast<hipStream_t>(lanes[j]->stream());
                 lanes[j]->setFrameTiming(false);   // nobody reads a set's own time: the next set may start under its tail
             }
@@ -831,7 +867,9 @@ int main(int argc, char **argv)
                     apply_segment(*lanes[j], ls.seg);   // (waits for the renderer's stream: its sets in flight)
                     lane_seg[j] = ls.seg;
                 }
-                if (use_path) lanes[j]->renderFrames(W, H, sd, ls.views, blocks[j]);
+                if (rgba8 && use_path) lanes[j]->renderFramesRGBA8(W, H, sd, ls.views, blocks[j], blocks8[j]);
+                else if (rgba8) lanes[j]->renderFramesRGBA8(W, H, sd, blocks[j], blocks8[j]);
+                else if (use_path) lanes[j]->renderFrames(W, H, sd, ls.views, blocks[j]);
                 else lanes[j]->renderFrames(W, H, sd, blocks[j]);
             };
             if (bench) {   // every renderer once, untimed: buffers, work queue, skip bitmap, cell grid, cost map
@@ -861,6 +899,10 @@ int main(int argc, char **argv)
                         const size_t at = all_frames.size(), nfl = sets[k].seeds.size() * W * H * 4;
                         all_frames.resize(at + nfl);
                         hip_ok(hipMemcpy(all_frames.data() + at, blocks[k % F], nfl * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy");
+                        if (rgba8) {
+                            all_frames8.resize(at + nfl);
+                            hip_ok(hipMemcpy(all_frames8.data() + at, blocks8[k % F], nfl, hipMemcpyDeviceToHost), "hipMemcpy");
+                        }
                     }
                 }
             }
@@ -888,6 +930,12 @@ int main(int argc, char **argv)
             std::ofstream raw(out + ".rgba.f32", std::ios::binary);
             raw.write(reinterpret_cast<const char *>(frame.data()), std::streamsize(frame.size() * sizeof(float)));
             write_ppm(out + ".ppm", frame, W, H);
+            if (rgba8) {
+                frame8.resize(W * H * 4);
+                hip_ok(hipMemcpy(frame8.data(), blocks8[last % F] + (sets[last].seeds.size() - 1) * W * H * 4, frame8.size(),
+                                 hipMemcpyDeviceToHost), "hipMemcpy");
+                write_rgba8(out, frame8, all_frames8, W, H);
+            }
             auto res = vr.getResolution();
             std::printf("{\"device\": \"%s\", \"volume\": [%u, %u, %u], \"width\": %zu, \"height\": %zu, \"frames\": %d, "
                         "\"renderers\": %zu, \"launch_sets\": %zu, \"frames_per_launch_set\": %zu, \"round_budget\": %u, "
@@ -900,6 +948,7 @@ int main(int argc, char **argv)
                         double(ms) / frames, wall / frames * 1e3, bench ? "true" : "false",
                         bench ? "" : " (frames copied to the host inside the region)", out.c_str());
             for (float *b : blocks) (void)hipFree(b);
+            for (unsigned char *b : blocks8) (void)hipFree(b);
             (void)hipEventDestroy(ev0);
             (void)hipEventDestroy(ev1);
             for (auto &e : done) (void)hipEventDestroy(e);
@@ -953,6 +1002,11 @@ int main(int argc, char **argv)
             std::ofstream raw(out + ".rgba.f32", std::ios::binary);
             raw.write(reinterpret_cast<const char *>(frame.data()), std::streamsize(frame.size() * sizeof(float)));
             write_ppm(out + ".ppm", frame, W, H);
+            if (rgba8) {   // the bytes of the image the frame buffer holds
+                std::vector<unsigned char> frame8;
+                vr.frameRGBA8(W, H, frame8);
+                write_rgba8(out, frame8, std::vector<unsigned char>(), W, H);
+            }
             auto res = vr.getResolution();
             std::printf("{\"device\": \"%s\", \"volume\": [%u, %u, %u], \"width\": %zu, \"height\": %zu, "
                         "\"samples\": %d, \"samples_per_launch\": %u, \"sample_kernel\": %s, \"bench\": %s, "
@@ -975,6 +1029,10 @@ int main(int argc, char **argv)
             vr.runRaycastNoGL(W, H, frame);   // frames accumulate (running mean), like the reference
             kernel_s += vr.getLastExecTime();
             if (independent) all_frames.insert(all_frames.end(), frame.begin(), frame.end());
+            if (rgba8) {   // the same frame's bytes, quantised on the GPU from the frame buffer
+                vr.frameRGBA8(W, H, frame8);
+                if (independent) all_frames8.insert(all_frames8.end(), frame8.begin(), frame8.end());
+            }
         }
         if (!all_frames.empty()) {
             std::ofstream af(out + ".frames.rgba.f32", std::ios::binary);
@@ -983,6 +1041,7 @@ int main(int argc, char **argv)
         std::ofstream raw(out + ".rgba.f32", std::ios::binary);
         raw.write(reinterpret_cast<const char *>(frame.data()), std::streamsize(frame.size() * sizeof(float)));
         write_ppm(out + ".ppm", frame, W, H);
+        if (rgba8) write_rgba8(out, frame8, all_frames8, W, H);
         auto res = vr.getResolution();
         std::printf("{\"device\": \"%s\", \"volume\": [%u, %u, %u], \"width\": %zu, \"height\": %zu, "
                     "\"frames\": %d, \"kernel_ms_per_frame\": %.4f, \"out\": \"%s.rgba.f32\"}\n",

@@ -49,6 +49,22 @@ private:
     void forget() { p = nullptr; bytes = 0; owned = true; }
 };
 
+// Pinned host memory that goes away with its holder (the staging block of a download).
+struct PinnedBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { release(); }
+    void release()   // (errors of the free are ignored)
+    {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+};
+
 // An event or a stream, destroyed with its holder.
 template <class H, hipError_t (*Destroy)(H)>
 struct Handle {
@@ -186,6 +202,11 @@ struct vrhip_renderer {
     DevBuf<float4> env;               // environment map (float RGBA), or empty
     uint32_t env_w = 0, env_h = 0;
 
+    // 8-bit frames to host memory (vrhip_quantise_rgba8 with a host destination, vr_rgba8.hip): the quantised words
+    // on the device and the pinned block they are copied through; grown on demand, kept, freed with the renderer
+    DevBuf<uint32_t> rgba8_dev;
+    PinnedBuf rgba8_host;
+
     // device-side ingest (vrhip_ingest_raw, vrhip_volume_histogram): the running maximum and the 256 64-bit
     // histogram counters in device memory, the events around its kernels (all created on first use)
     size_t ingest_slab_bytes = (size_t)256 << 20;   // VRHIP_INGEST_SLAB_BYTES: staging per slab
@@ -281,6 +302,25 @@ int grow(vrhip_renderer *r, DevBuf<T> &b, size_t bytes, unsigned flags = 0)
     b.bytes = bytes;
     return VRHIP_OK;
 }
+
+// The same for the pinned staging block: nothing uses the old one when this is called (its users wait for their
+// copy before they return).
+inline int grow_pinned(vrhip_renderer *r, PinnedBuf &b, size_t bytes)
+{
+    if (b.p && bytes <= b.bytes) return VRHIP_OK;
+    b.release();
+    const hipError_t e = hipHostMalloc(&b.p, bytes, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        b.p = nullptr;
+        return fail(r, VRHIP_ERR_HIP, std::string("ERROR: hipHostMalloc of ") + std::to_string(bytes) + " bytes (" +
+                                          hipGetErrorString(e) + ")");
+    }
+    b.bytes = bytes;
+    return VRHIP_OK;
+}
+
+// the scan of the sparse gather message's head (vrhip_gather.hip), shared by the float and the 8-bit pack
+void launch_pack_scan(hipStream_t st, int32_t *flags_pos, uint32_t n_slots, int32_t *slots, uint32_t *count);
 
 // ---- views of the renderer's state for the launchers (vr_internal.h)
 

@@ -149,6 +149,11 @@ __global__ __launch_bounds__(256) void vr_msg_pos_scatter_kernel(GatherMsgs msgs
 
 } // namespace
 
+void launch_pack_scan(hipStream_t st, int32_t *flags_pos, uint32_t n_slots, int32_t *slots, uint32_t *count)
+{
+    hipLaunchKernelGGL(vr_pack_scan_kernel, dim3(1), dim3(1024), 0, st, flags_pos, n_slots, slots, count);
+}
+
 extern "C" {
 
 int vrhip_pack_tiles(vrhip_renderer *r, void *hip_stream, const float *tiles_dev, uint32_t n_slots, uint32_t tile_pixels,
@@ -163,7 +168,7 @@ int vrhip_pack_tiles(vrhip_renderer *r, void *hip_stream, const float *tiles_dev
     const uint32_t spad = (n_slots + 3u) / 4u * 4u;
     hipLaunchKernelGGL(vr_pack_flags_kernel, dim3(n_slots), dim3(256), 0, st, (const uint4 *)tiles_dev, tile_pixels,
                        scratch_dev, (uint4 *)(msg_dev + spad));
-    hipLaunchKernelGGL(vr_pack_scan_kernel, dim3(1), dim3(1024), 0, st, scratch_dev, n_slots, (int32_t *)msg_dev, count_dev);
+    launch_pack_scan(st, scratch_dev, n_slots, (int32_t *)msg_dev, count_dev);
     hipLaunchKernelGGL(vr_pack_copy_kernel, dim3(n_slots), dim3(256), 0, st, (const uint4 *)tiles_dev, tile_pixels,
                        (const int32_t *)scratch_dev, (uint4 *)(msg_dev + spad + 4u * (size_t)n_slots));
     VR_HIP(r, hipGetLastError());

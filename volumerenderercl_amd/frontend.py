@@ -171,6 +171,17 @@ def prefix_sum(tff):
     return np.cumsum(tff[:, 3].astype(np.uint64)).astype(np.uint32)
 
 
+def quantise_rgba8(frame_f32):
+    """The 8-bit frame of float pixels, per channel: 0 for a NaN, else rint(clip(f * 255.0f, 0, 255)) in float32
+    -- one rounded fp32 multiply, a clamp, round-half-to-even: OpenCL's convert_uchar_sat_rte(f * 255.0f), what
+    write_imagef does on the reference's CL_UNORM_INT8 output image (volumerendercl.cpp:468-478).  The numpy
+    statement of what the library's kernels compute (vr_rgba8.hip); same shape, dtype uint8."""
+    f = np.asarray(frame_f32, dtype=np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        q = np.rint(np.clip(f * np.float32(255.0), np.float32(0.0), np.float32(255.0)))
+    return np.where(np.isnan(f), np.float32(0.0), q).astype(np.uint8)
+
+
 # ---- the reference GUI's saved files (SURVEY 8f1): camera state, transfer functions ----------
 
 def read_tff_stops(path):

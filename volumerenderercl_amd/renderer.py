@@ -135,6 +135,7 @@ class VolumeRenderCL:
         return twin
 
     def close(self):
+        self._batch_f32 = None      # (the float frames behind render_batch(rgba8=True))
         if self._lib is not None and self._h:
             self._lib.vrhip_destroy(self._h)
             self._h = C.c_void_p()
@@ -241,6 +242,55 @@ class VolumeRenderCL:
             output[:] = out.reshape(-1).tolist()
         return out
 
+    # ---- 8-bit frames (the reference's CL_UNORM_INT8 output image; frontend.quantise_rgba8 states the conversion)
+    @staticmethod
+    def _rgba8_out(out, shape):
+        """(array to return, pointer, is_device) of an 8-bit destination: `out` (numpy uint8, or a torch uint8
+        device tensor) or a fresh numpy array of `shape`."""
+        if out is None:
+            out = np.empty(shape, dtype=np.uint8)
+        n = int(np.prod(shape))
+        if isinstance(out, np.ndarray):
+            if out.dtype != np.uint8 or out.size != n or not out.flags.c_contiguous:
+                raise ValueError("out must be a contiguous uint8 array of %d bytes" % n)
+            return out, out.ctypes.data, 0
+        import torch
+        if out.dtype != torch.uint8 or out.numel() != n or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("out must be a numpy array or a contiguous uint8 device tensor of %d bytes" % n)
+        return out, out.data_ptr(), 1
+
+    def render_frame_rgba8(self, width, height, out=None):
+        """runRaycastNoGL as the reference reads it back: the frame as uint8 [height, width, 4]
+        (vrhip_render_frame_rgba8: the frame of runRaycast, then quantised on the same stream; the float
+        frame buffer keeps the unquantised frame, so accumulation carries on as with runRaycast).  out: a
+        numpy uint8 array or a torch uint8 device tensor to fill; returned."""
+        if not self._vol_loaded:
+            return out
+        out, ptr, dev = self._rgba8_out(out, (int(height), int(width), 4))
+        self._begin_frame()
+        self._check(self._lib.vrhip_render_frame_rgba8(self._h, int(width), int(height), C.c_void_p(ptr), dev))
+        self._rendering.iteration += 1
+        return out
+
+    def quantise_rgba8(self, frames, out=None, stream=None):
+        """A contiguous float32 device tensor [..., 4] as uint8 of the same shape (vrhip_quantise_rgba8), on
+        torch's current stream (or the hipStream_t handle `stream`).  out: a numpy uint8 array (the call
+        returns when it is filled) or a torch uint8 device tensor; None: a new device tensor."""
+        import torch
+        if (frames.dtype != torch.float32 or not frames.is_cuda or not frames.is_contiguous() or frames.dim() < 1
+                or frames.shape[-1] != 4):
+            raise ValueError("quantise_rgba8: a contiguous float32 device tensor [..., 4]")
+        if out is None:
+            out = torch.empty(frames.shape, dtype=torch.uint8, device=frames.device)
+        out, ptr, dev = self._rgba8_out(out, tuple(frames.shape))
+        n = frames.numel() // 4
+        if n:
+            if stream is None:
+                stream = torch.cuda.current_stream(frames.device).cuda_stream
+            self._check(self._lib.vrhip_quantise_rgba8(self._h, C.c_void_p(stream), C.c_void_p(frames.data_ptr()), 1, n, n,
+                                                       C.c_void_p(ptr), dev))
+        return out
+
     def render_tiles(self, width, height, tile_w, tile_h, tile_ids, out_dev_ptr):
         """Image-tile decomposition entry; no reference counterpart."""
         if not self._vol_loaded:
@@ -251,17 +301,28 @@ class VolumeRenderCL:
                                                  int(tile_h), ids.ctypes.data_as(C.c_void_p),
                                                  int(ids.size), C.c_void_p(out_dev_ptr)))
 
-    def render_batch(self, width, height, seeds, out_dev_ptr, tile_w=0, tile_h=0, tile_ids=None,
-                     frame_stride=0, views=None):
+    def render_batch(self, width, height, seeds, out_dev_ptr=None, tile_w=0, tile_h=0, tile_ids=None,
+                     frame_stride=0, views=None, rgba8=False, out=None):
         """len(seeds) <= 256 independent frames (frame f jittered by seeds[f]) in one set of
         launches (vrhip_render_batch): whole frames into out[f][height][width][4], or -- with
         tile_ids -- the tile subset into out[f][n_tiles][tile_h][tile_w][4] (device memory);
         frame_stride: pixels between the frames of `out` when they are not packed.
         views: one row-major 16-float view matrix per frame (as updateView takes it): frame f is
         rendered from views[f] with the renderer's bbox and ortho setting (vrhip_render_batch_views);
-        None: every frame from the renderer's view."""
+        None: every frame from the renderer's view.
+        rgba8=True: the frames as 8-bit pixels from the same launch set -- the floats are rendered into a
+        buffer this object keeps until close() and quantised on the renderer's stream (vrhip_quantise_rgba8)
+        -- into `out`, a torch uint8 device tensor [n, height, width, 4] (tiles: [n, n_tiles, tile_h, tile_w, 4]),
+        or None for a new one; returned.  out_dev_ptr and frame_stride belong to the float form and must be
+        left alone then, as `out` must without rgba8."""
         if not self._vol_loaded:
             return
+        if rgba8:
+            if out_dev_ptr is not None or frame_stride:
+                raise ValueError("render_batch: with rgba8 the frames go to `out`, packed")
+            return self._render_batch_rgba8(width, height, seeds, out, tile_w, tile_h, tile_ids, views)
+        if out_dev_ptr is None or out is not None:
+            raise ValueError("render_batch: a device pointer for the float frames")
         self._rendering.iteration = 0
         self._push_params()
         sd = np.ascontiguousarray(seeds, dtype=np.uint32)
@@ -282,6 +343,32 @@ class VolumeRenderCL:
             None if ids is None else ids.ctypes.data_as(C.c_void_p), 0 if ids is None else int(ids.size),
             sd.ctypes.data_as(C.c_void_p), None if cams is None else C.cast(cams, C.c_void_p), int(sd.size),
             C.c_void_p(out_dev_ptr), int(frame_stride)))
+
+    def _render_batch_rgba8(self, width, height, seeds, out, tile_w, tile_h, tile_ids, views):
+        import torch
+        n = len(seeds)
+        shape = ((n, int(height), int(width), 4) if tile_ids is None
+                 else (n, len(tile_ids), int(tile_h), int(tile_w), 4))
+        dev = torch.device("cuda", getattr(self, "_device_id", 0))
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=dev)
+        elif tuple(out.shape) != shape:
+            raise ValueError("render_batch: out must have shape %r" % (shape,))
+        out, ptr, is_dev = self._rgba8_out(out, shape)
+        if not is_dev:
+            raise ValueError("render_batch: out must be a torch uint8 device tensor")
+        f32 = getattr(self, "_batch_f32", None)
+        if f32 is None or f32.numel() < int(np.prod(shape)):
+            f32 = self._batch_f32 = torch.zeros(int(np.prod(shape)), dtype=torch.float32, device=dev)
+        # the renderer's stream follows torch's current one (the float buffer's last reader, `out`'s producer) and
+        # the other way round afterwards, as TileDriver brackets a render
+        rs = torch.cuda.ExternalStream(self.get_stream(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        rs.wait_stream(cur)
+        self.render_batch(width, height, seeds, f32.data_ptr(), tile_w, tile_h, tile_ids, views=views)
+        self.quantise_rgba8(f32[: int(np.prod(shape))].view(shape), out, stream=self.get_stream())
+        cur.wait_stream(rs)
+        return out
 
     def render_samples(self, width, height, seeds, out_dev_ptr=None, tile_w=0, tile_h=0, tile_ids=None,
                        samples_per_launch=0):

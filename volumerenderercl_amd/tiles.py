@@ -54,6 +54,13 @@ def deal_tiles(W, H, tw, th, world, root_share=1.0):
     return owner
 
 
+def quantise_rgba8_torch(torch, x):
+    """frontend.quantise_rgba8 in torch ops, for tensors the library's kernel does not serve (CPU tensors, a
+    stand-in renderer): 0 for a NaN, else round-half-to-even of clamp(x * 255, 0, 255) in float32."""
+    q = torch.clamp(x * 255.0, 0.0, 255.0).round()
+    return torch.where(torch.isnan(x), torch.zeros_like(q), q).to(torch.uint8)
+
+
 class TileSplit:
     def __init__(self, width, height, tile_w, tile_h, world, rank, root_share=1.0):
         if tile_w % 16 or tile_h % 16:
@@ -111,12 +118,25 @@ class TileDriver:
     for the current stream (the gather that last read the tile buffer was waited for there), and
     the current stream then waits for the renderer's stream before the gather is issued.  A
     renderer that already launches on the current stream (vr.set_stream) needs neither wait.
+
+    pixel_format="rgba8" (default "float": everything above): the frames travel as 8-bit pixels, the reference's
+    display format (frontend.quantise_rgba8 states the conversion).  The tiles are rendered as floats and quantised
+    on the rank that rendered them, before the gather; staging buffers, messages and the `frames` tensor handed
+    to collect / collect_batch / render_frame are uint8 [.., 4].  Dense: a quarter of the bytes.  Sparse: the
+    message is [spad slot numbers | S pixels, one word each | the whole tiles, P words each] with spad = S
+    rounded up to 4 on both paths (vrhip_pack_tiles_rgba8 / vrhip_assemble_batch_rgba8 on a GPU, torch ops
+    elsewhere), and a tile travels as one pixel when its QUANTISED pixels are all equal.  Image-order ESS merging
+    is untouched: hit images are bytes already.
     """
 
     def __init__(self, vr, split, device, render_tiles_fn=None, dist=None, image_ess=False,
-                 hit_io=None, batch=1, lanes=None, force_gather=False, sparse=False):
+                 hit_io=None, batch=1, lanes=None, force_gather=False, sparse=False,
+                 pixel_format="float"):
         import torch
         self.torch = torch
+        if pixel_format not in ("float", "rgba8"):
+            raise ValueError("pixel_format must be 'float' or 'rgba8'")
+        self.rgba8 = pixel_format == "rgba8"
         self.vr, self.split, self.device = vr, split, device
         self.render_tiles_fn = render_tiles_fn
         s = split
@@ -157,10 +177,14 @@ class TileDriver:
             # [frame of the batch, slot, th, tw, 4]
             self.local = [torch.zeros((B, s.cap, s.th, s.tw, 4), dtype=torch.float32, device=device)
                           for _ in range(2)]
+            # what travels: the float tiles themselves, or (rgba8) their quantised twins
+            pix = torch.uint8 if self.rgba8 else torch.float32
+            if self.rgba8:
+                self.local8 = [torch.zeros((B, s.cap, s.th, s.tw, 4), dtype=pix, device=device) for _ in range(2)]
             if s.rank == 0:
                 # one block per buffer: [rank, frame, slot, th, tw, 4]; the gather writes rank r's
                 # tiles into staging[b][r]
-                self.staging = [torch.zeros((s.world, B, s.cap, s.th, s.tw, 4), dtype=torch.float32,
+                self.staging = [torch.zeros((s.world, B, s.cap, s.th, s.tw, 4), dtype=pix,
                                             device=device) for _ in range(2)]
                 # (frame f, tile id) -> row of staging.view(world * B * cap, ...)
                 perm = np.zeros((B, s.n_tiles), dtype=np.int64)
@@ -172,7 +196,7 @@ class TileDriver:
                 self.exact = (s.W % s.tw == 0) and (s.H % s.th == 0)
                 if not self.exact:
                     self.padded = torch.zeros((B, s.tiles_y * s.th, s.tiles_x * s.tw, 4),
-                                              dtype=torch.float32, device=device)
+                                              dtype=pix, device=device)
 
     # ---- stream ordering between a renderer and the collective
     def _stream_of(self, r, given=None):
@@ -289,6 +313,8 @@ class TileDriver:
 
     def _start_gather(self, b, n):
         s = self.split
+        if self.rgba8:
+            return self._start_gather_rgba8(b, n)
         if not self.sparse:
             glist = [self.staging[b][r] for r in range(s.world)] if s.rank == 0 else None
             work = self.dist.gather(self.local[b], glist, dst=0, async_op=True)
@@ -328,6 +354,57 @@ class TileDriver:
         self.pending.append({"b": b, "n": n, "work": None, "whole": whole, "uni": uni, "x": x,
                              "counts": counts, "cwork": cwork})
 
+    def _quantise_local(self, b, n):
+        """rgba8: the float tiles of buffer b, frames [0, n), as 8-bit pixels in local8[b] -- the library's kernel on
+        the current stream for a real renderer on a GPU, the same conversion in torch ops elsewhere (CPU tensors, a
+        stand-in renderer)."""
+        torch = self.torch
+        x, y = self.local[b][:n], self.local8[b][:n]
+        if getattr(self.vr, "lib", None) is not None and x.is_cuda:
+            self.vr.quantise_rgba8(x, y)
+            return
+        y.copy_(quantise_rgba8_torch(torch, x))
+
+    def _start_gather_rgba8(self, b, n):
+        s, torch = self.split, self.torch
+        if not self.sparse:
+            self._quantise_local(b, n)
+            glist = [self.staging[b][r] for r in range(s.world)] if s.rank == 0 else None
+            work = self.dist.gather(self.local8[b], glist, dst=0, async_op=True)
+            self.pending.append({"b": b, "n": n, "work": work})
+            return
+        self._issue_payloads()
+        S, P = n * s.cap, s.th * s.tw
+        counts = [torch.zeros(1, dtype=torch.int32, device=self.device) for _ in range(s.world)]
+        if self._gpu_pack():
+            # vrhip_pack_tiles_rgba8 reads the float tiles and quantises as it packs; a pixel is one word
+            import ctypes as C
+            Smax = self.batch * s.cap
+            if not hasattr(self, "_msg"):
+                # (rounded up to 4 words: rank 0 receives the messages as the rows of one block, and every row has to
+                # start 16-byte aligned as the first does)
+                full = ((Smax + 3) // 4 * 4 + Smax + Smax * P + 3) // 4 * 4
+                self._msg = [torch.empty(full, dtype=torch.int32, device=self.device) for _ in range(2)]
+                self._scratch = [torch.empty(Smax, dtype=torch.int32, device=self.device) for _ in range(2)]
+                self._count = [torch.zeros(1, dtype=torch.int32, device=self.device) for _ in range(2)]
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = self.vr.lib.vrhip_pack_tiles_rgba8(self.vr.handle, C.c_void_p(stream), C.c_void_p(self.local[b].data_ptr()),
+                                                    S, P, C.c_void_p(self._scratch[b].data_ptr()),
+                                                    C.c_void_p(self._msg[b].data_ptr()), C.c_void_p(self._count[b].data_ptr()))
+            if rc != 0:
+                raise RuntimeError("vrhip_pack_tiles_rgba8 failed (%d)" % rc)
+            cwork = self.dist.all_gather(counts, self._count[b], async_op=True)
+            self.pending.append({"b": b, "n": n, "work": None, "packed": True, "counts": counts, "cwork": cwork})
+            return
+        self._quantise_local(b, n)
+        xi = self.local8[b].view(torch.int32).view(self.batch * s.cap, P)[:S]     # a pixel is one word
+        whole = (xi != xi[:, :1]).any(dim=1)                          # not all quantised pixels equal
+        uni = xi[:, 0].contiguous()
+        count = whole.sum().to(torch.int32).view(1)
+        cwork = self.dist.all_gather(counts, count, async_op=True)
+        self.pending.append({"b": b, "n": n, "work": None, "whole": whole, "uni": uni, "x": xi,
+                             "counts": counts, "cwork": cwork})
+
     def _issue_payloads(self):
         """Sparse: start the payload gather of every batch that has none yet (ONE host synchronisation per batch:
         the ranks' counts)."""
@@ -342,14 +419,26 @@ class TileDriver:
                 # the library's layout: the slot-number block is spad wide whatever the counts; all ranks send the
                 # same length (a gather wants equal sizes): the prefix that holds the largest count's tiles
                 maxc = (S + 3) // 4 * 4
-                length = maxc + 4 * S + 4 * max(cs) * P
+                length = maxc + S + max(cs) * P if self.rgba8 else maxc + 4 * S + 4 * max(cs) * P
                 msg = self._msg[e["b"]][:length]
                 recv = None
                 if s.rank == 0:
                     if not hasattr(self, "_recv") or self._recv[0].shape[1] < self._msg[0].numel():
-                        self._recv = [torch.empty((s.world, self._msg[0].numel()), dtype=torch.float32, device=self.device)
+                        self._recv = [torch.empty((s.world, self._msg[0].numel()), dtype=self._msg[0].dtype, device=self.device)
                                       for _ in range(2)]
                     recv = [self._recv[e["b"]][r][:length] for r in range(s.world)]
+            elif self.rgba8:
+                # the library's layout, word for word: spad slot numbers whatever the counts, S words, the largest
+                # count's tiles
+                maxc = (S + 3) // 4 * 4
+                slots = torch.nonzero(e["whole"]).view(-1).to(torch.int32)   # cs[rank] entries
+                msg = torch.zeros(maxc + S + max(cs) * P, dtype=torch.int32, device=self.device)
+                k = cs[s.rank]
+                if k:
+                    msg[:k].copy_(slots)
+                    msg[maxc + S: maxc + S + k * P].view(k, P).copy_(e["x"].index_select(0, slots.to(torch.int64)))
+                msg[maxc: maxc + S].copy_(e["uni"])
+                recv = ([torch.empty_like(msg) for _ in range(s.world)] if s.rank == 0 else None)
             else:
                 maxc = (max(1, max(cs)) + 3) // 4 * 4          # (a multiple of 4: the pixels behind it stay 16-byte aligned)
                 slots = torch.nonzero(e["whole"]).view(-1).to(torch.int32)   # cs[rank] entries
@@ -366,8 +455,8 @@ class TileDriver:
                 e.pop(key, None)
             self.gather_stats["batches"] += 1
             peers = max(1, s.world - 1)   # (a world of one, force_gather: its own message counts once)
-            self.gather_stats["dense_bytes"] += 16 * S * P * peers
-            self.gather_stats["sent_bytes"] += 4 * int(msg.numel()) * peers
+            self.gather_stats["dense_bytes"] += (4 if self.rgba8 else 16) * S * P * peers
+            self.gather_stats["sent_bytes"] += int(msg.element_size()) * int(msg.numel()) * peers
 
     def _assemble_fused(self, e, frames):
         """Rank 0, sparse, on the GPU: the frames straight from the received messages with one kernel
@@ -378,7 +467,8 @@ class TileDriver:
         lib = getattr(self.vr, "lib", None)
         if os.environ.get("VRHIP_NO_FUSED_ASSEMBLY"):      # A/B: the torch path
             return False
-        if (lib is None or frames is None or not frames.is_cuda or frames.dtype != torch.float32 or s.world > 64
+        if (lib is None or frames is None or not frames.is_cuda
+                or frames.dtype != (torch.uint8 if self.rgba8 else torch.float32) or s.world > 64
                 or s.cap > 65536 or not frames[:e["n"]].is_contiguous() or tuple(frames.shape[1:]) != (s.H, s.W, 4)):
             return False
         import ctypes as C
@@ -399,11 +489,11 @@ class TileDriver:
         rc = lib.vrhip_message_positions(self.vr.handle, C.c_void_p(stream), ptrs, counts, s.world, S,
                                          C.c_void_p(pos.data_ptr()))
         if rc == 0:
-            rc = lib.vrhip_assemble_batch(self.vr.handle, C.c_void_p(stream), ptrs, s.world, n, s.cap, maxc,
+            rc = (lib.vrhip_assemble_batch_rgba8 if self.rgba8 else lib.vrhip_assemble_batch)(self.vr.handle, C.c_void_p(stream), ptrs, s.world, n, s.cap, maxc,
                                           C.c_void_p(pos.data_ptr()), C.c_void_p(self._rank_slot.data_ptr()), s.W, s.H,
                                           s.tw, s.th, C.c_void_p(frames.data_ptr()))
         if rc != 0:
-            raise RuntimeError("vrhip_message_positions / vrhip_assemble_batch failed (%d)" % rc)
+            raise RuntimeError("vrhip_message_positions / vrhip_assemble_batch%s failed (%d)" % ("_rgba8" if self.rgba8 else "", rc))
         e["keep"] = (pos, ptrs)     # (alive until the kernel has run: the caller synchronises before reuse)
         self._last_assembled = e
         return True
@@ -414,6 +504,13 @@ class TileDriver:
         S, P, maxc = e["n"] * s.cap, s.th * s.tw, e["maxc"]
         for r in range(s.world):
             m = e["recv"][r]
+            if self.rgba8:      # a pixel is one word
+                dense = self.staging[e["b"]][r].view(torch.int32).view(self.batch * s.cap, P)[:S]
+                dense.copy_(m[maxc: maxc + S].view(S, 1).expand(S, P))
+                k = e["cs"][r]
+                if k:
+                    dense.index_copy_(0, m[:k].to(torch.int64), m[maxc + S: maxc + S + k * P].view(k, P))
+                continue
             dense = self.staging[e["b"]][r].view(self.batch * s.cap, P, 4)[:S]
             dense.copy_(m[maxc: maxc + 4 * S].view(S, 1, 4).expand(S, P, 4))
             k = e["cs"][r]
@@ -470,12 +567,17 @@ class TileDriver:
             if self.render_tiles_fn is None:
                 streams = [self._stream_of(self.vr)]
                 cur = self._before_render(streams)
-                self.vr.runRaycast(s.W, s.H, out_dev_ptr=frame.data_ptr())
+                if self.rgba8:
+                    self.vr.render_frame_rgba8(s.W, s.H, out=frame)
+                else:
+                    self.vr.runRaycast(s.W, s.H, out_dev_ptr=frame.data_ptr())
                 self._after_render(streams, cur)     # `frame` is the caller's, on the current stream
                 return frame
             out = self.torch.zeros((s.n_tiles, s.th, s.tw, 4), dtype=self.torch.float32,
                                    device=self.device)
             self.render_tiles_fn(s.my_tiles, out)
+            if self.rgba8:
+                out = quantise_rgba8_torch(self.torch, out)
             for k, t in enumerate(s.my_tiles):
                 x0, y0, w, h = s.tile_rect(t)
                 frame[y0:y0 + h, x0:x0 + w] = out[k, :h, :w]
