@@ -333,11 +333,17 @@ static float vol_nearest(const vol_t *v, float px, float py, float pz)
 /* TF read: read_imagef(tffData, linearSmp, x) on the RGBA8 1-D image
  * (volumeraycast.cl:777,808); UNORM8 -> c / 255.0f.  x is first clamped to [-1, 2]: every x
  * outside reads TF[0] or TF[n-1] exactly, as CLAMP_TO_EDGE does for x <= 0 and x >= 1, and the
- * index stays far inside int range.  NaN reads as -1 (fmaxf): TF[0]. */
+ * index stays far inside int range.  NaN reads as -1 (fmaxf): TF[0] -- every NaN,
+ * signalling ones included, for which libm's fmaxf answers NaN: the clamp is written out. */
+static inline float tff_coord(float x)
+{
+    float c = x > -1.0f ? x : -1.0f; /* fmaxf(x, -1): the other operand for a NaN */
+    return c < 2.0f ? c : 2.0f;
+}
 static void tff_linear(const vro_scene *s, float x, float out[4])
 {
     int n = (int)s->tff_n;
-    float ub = fminf(fmaxf(x, -1.0f), 2.0f) * (float)n - 0.5f;
+    float ub = tff_coord(x) * (float)n - 0.5f;
     float fl = floorf(ub);
     float a = ub - fl;
     int i = (int)fl;
@@ -365,6 +371,15 @@ static uint32_t prefix_nearest(const vro_scene *s, float x)
     float fi = floorf(x * (float)s->prefix_n);
     if (!(fi >= 0.0f && fi <= (float)(s->prefix_n - 1))) return 0u;
     return s->prefix[(int)fi];
+}
+
+/* The per-brick skip test (volumeraycast.cl:777-787) on one (min, max) pair. */
+static int skip_test(const vro_scene *s, float mn, float mx)
+{
+    float tfc[4];
+    tff_linear(s, mx, tfc);
+    if (!(tfc[3] < 1e-6f)) return 0;
+    return prefix_nearest(s, mn) == prefix_nearest(s, mx);
 }
 
 /* read_imagef(volBrickData, (int4)(cell,0)).xy (volumeraycast.cl:765); out-of-range
@@ -740,6 +755,17 @@ static float vro_logf(float x) /* x in (0, 1] here */
     return fmaf(fe, 0.693359375f, lg);
 }
 
+/* (int)q the way the device converts: saturating, 0 for a NaN.  C leaves the conversion of a
+ * value outside int range undefined; |q| >= 2^31 needs |x| >= 3.4e9, which no caller passes, but
+ * both sides then still take the same quadrant. */
+static inline int f2i_sat(float q)
+{
+    if (q != q) return 0;
+    if (q >= 2147483648.0f) return INT32_MAX;
+    if (q <= -2147483648.0f) return INT32_MIN;
+    return (int)q;
+}
+
 /* sin and cos of x in [0, 2*pi]: quadrant reduction + Cephes sinf/cosf kernels */
 static void vro_sincosf(float x, float *s, float *c)
 {
@@ -757,7 +783,7 @@ static void vro_sincosf(float x, float *s, float *c)
     cp = fmaf(cp, z, -1.388731625493765E-003f);
     cp = fmaf(cp, z, 4.166664568298827E-002f);
     float cv = fmaf(cp * z, z, fmaf(z, -0.5f, 1.0f));
-    int qi = ((int)q) & 3;
+    int qi = f2i_sat(q) & 3;
     switch (qi) {
     case 0: *s = sv; *c = cv; break;
     case 1: *s = cv; *c = -sv; break;
@@ -1205,16 +1231,10 @@ static int render_pixel(const vol_t *v, const kargs_t *k, uint32_t gx, uint32_t 
             t_exit = vclamp(t_exit, t + stepSize, t + brickDia);
             for (int i = 0; i < 3; ++i) tv[i] += inc[i] * deltaT[i];
 
-            float tfc[4];
-            tff_linear(v->s, mx, tfc);
-            if (tfc[3] < 1e-6f) {
-                uint32_t pmin = prefix_nearest(v->s, mn);
-                uint32_t pmax = prefix_nearest(v->s, mx);
-                if (pmin == pmax) {
-                    st->bricks_skipped++;
-                    t = t_exit;
-                    continue;
-                }
+            if (skip_test(v->s, mn, mx)) {
+                st->bricks_skipped++;
+                t = t_exit;
+                continue;
             }
         }
         /* :790-880 */
@@ -1472,5 +1492,86 @@ int vro_synth_volume(int kind, const uint32_t res[3], int format, void *out)
                 else if (format == VRO_USHORT) ((uint16_t *)out)[i] = (uint16_t)lround(65535.0 * dv);
                 else ((float *)out)[i] = (float)dv;
             }
+    return 0;
+}
+
+/* ------------------------------------------------------------- batch entry */
+
+/* words per element of an operation's arguments and of its result (vr_oracle.h) */
+int vro_math_arity(int op, int *n_in, int *n_out)
+{
+    static const signed char tab[VRO_OP_COUNT][2] = {
+        [VRO_OP_LOGF] = {1, 1},      [VRO_OP_POWR] = {2, 1},       [VRO_OP_SINCOSF] = {1, 2},
+        [VRO_OP_ATAN2F] = {2, 1},    [VRO_OP_ACOSF] = {1, 1},      [VRO_OP_NORMALIZE3] = {3, 3},
+        [VRO_OP_LEN3] = {3, 1},      [VRO_OP_DOT3] = {6, 1},       [VRO_OP_VMIN] = {2, 1},
+        [VRO_OP_VMAX] = {2, 1},      [VRO_OP_VCLAMP] = {3, 1},     [VRO_OP_LERPF] = {3, 1},
+        [VRO_OP_RNG] = {1, 1},       [VRO_OP_RNG3] = {3, 1},       [VRO_OP_MAP_UINT_FLOAT] = {1, 1},
+        [VRO_OP_TFF_LINEAR] = {1, 4},    [VRO_OP_TFF_LINEAR_RAW] = {1, 4}, [VRO_OP_TFF_ALPHA] = {1, 1},
+        [VRO_OP_TFF_ALPHA_RAW] = {1, 1}, [VRO_OP_PREFIX_NEAREST] = {1, 1}, [VRO_OP_SKIP_TEST] = {2, 1},
+    };
+    if (op < 0 || op >= VRO_OP_COUNT) return -1;
+    if (n_in) *n_in = tab[op][0];
+    if (n_out) *n_out = tab[op][1];
+    return 0;
+}
+
+/* One operation on `count` elements: element i reads its n_in argument words at in[i * n_in] and
+ * writes its n_out result words at out[i * n_out] (floats as their bit patterns).  Always the
+ * parity definitions, whatever vro_set_literal says. */
+int vro_math_batch(int op, size_t count, const uint32_t *in, uint32_t *out, const vro_tables *tables)
+{
+    int ni, no;
+    if (vro_math_arity(op, &ni, &no) || (count && (!in || !out))) return -1;
+    vro_scene sc;
+    memset(&sc, 0, sizeof sc);
+    if (op >= VRO_OP_TFF_LINEAR) {
+        if (!tables || !tables->tff || !tables->tff_n) return -1;
+        if (op >= VRO_OP_PREFIX_NEAREST && (!tables->prefix || !tables->prefix_n)) return -1;
+        sc.tff = tables->tff;
+        sc.tff_n = tables->tff_n;
+        sc.prefix = tables->prefix;
+        sc.prefix_n = tables->prefix_n;
+    }
+    const int literal = g_literal;
+    g_literal = 0;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < (int64_t)count; ++i) {
+        const uint32_t *a = in + (size_t)i * (size_t)ni;
+        uint32_t *o = out + (size_t)i * (size_t)no;
+        float r[4];
+        f3 v;
+        switch (op) {
+        case VRO_OP_LOGF: o[0] = f2u(vro_logf(u2f(a[0]))); break;
+        case VRO_OP_POWR: o[0] = f2u(vro_powr(u2f(a[0]), u2f(a[1]))); break;
+        case VRO_OP_SINCOSF: vro_sincosf(u2f(a[0]), &r[0], &r[1]); o[0] = f2u(r[0]); o[1] = f2u(r[1]); break;
+        case VRO_OP_ATAN2F: o[0] = f2u(vro_atan2f(u2f(a[0]), u2f(a[1]))); break;
+        case VRO_OP_ACOSF: o[0] = f2u(vro_acosf(u2f(a[0]))); break;
+        case VRO_OP_NORMALIZE3:
+            v = normalize3(mk3(u2f(a[0]), u2f(a[1]), u2f(a[2])));
+            o[0] = f2u(v.x); o[1] = f2u(v.y); o[2] = f2u(v.z);
+            break;
+        case VRO_OP_LEN3: o[0] = f2u(len3(mk3(u2f(a[0]), u2f(a[1]), u2f(a[2])))); break;
+        case VRO_OP_DOT3:
+            o[0] = f2u(dot3(mk3(u2f(a[0]), u2f(a[1]), u2f(a[2])), mk3(u2f(a[3]), u2f(a[4]), u2f(a[5]))));
+            break;
+        case VRO_OP_VMIN: o[0] = f2u(vmin(u2f(a[0]), u2f(a[1]))); break;
+        case VRO_OP_VMAX: o[0] = f2u(vmax(u2f(a[0]), u2f(a[1]))); break;
+        case VRO_OP_VCLAMP: o[0] = f2u(vclamp(u2f(a[0]), u2f(a[1]), u2f(a[2]))); break;
+        case VRO_OP_LERPF: o[0] = f2u(lerpf(u2f(a[0]), u2f(a[1]), u2f(a[2]))); break;
+        case VRO_OP_RNG: o[0] = vro_parallel_rng(a[0]); break;
+        case VRO_OP_RNG3: o[0] = vro_parallel_rng3(a[0], a[1], a[2]); break;
+        case VRO_OP_MAP_UINT_FLOAT: o[0] = f2u(vro_map_uint_float(a[0])); break;
+        case VRO_OP_TFF_LINEAR:
+        case VRO_OP_TFF_LINEAR_RAW:
+            tff_linear(&sc, u2f(a[0]), r);
+            o[0] = f2u(r[0]); o[1] = f2u(r[1]); o[2] = f2u(r[2]); o[3] = f2u(r[3]);
+            break;
+        case VRO_OP_TFF_ALPHA:
+        case VRO_OP_TFF_ALPHA_RAW: tff_linear(&sc, u2f(a[0]), r); o[0] = f2u(r[3]); break;
+        case VRO_OP_PREFIX_NEAREST: o[0] = prefix_nearest(&sc, u2f(a[0])); break;
+        default: o[0] = (uint32_t)skip_test(&sc, u2f(a[0]), u2f(a[1])); break;
+        }
+    }
+    g_literal = literal;
     return 0;
 }

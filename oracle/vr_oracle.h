@@ -188,6 +188,30 @@ int vro_num_threads(void);
 void vro_set_literal(int on);
 int vro_get_literal(void);
 
+/*
+ * The fp32 building blocks on arrays: the operations of vr_device_math.h and the transfer-function
+ * reads of vr_sampling.h, one id each (the HIP probe tests/hip/probe_math.hip uses the same ids).
+ * The oracle has one transfer-function read, clamped to [-1, 2]; VRO_OP_TFF_LINEAR /
+ * _ALPHA and their _RAW twins evaluate the same definition and differ only on the device
+ * (tff_linear<false> / <true>).  VRO_OP_DOT3 takes two vectors; SKIP_TEST takes (min, max) and
+ * gives 0 or 1; SINCOSF gives (sin, cos).
+ */
+enum {
+    VRO_OP_LOGF = 0, VRO_OP_POWR, VRO_OP_SINCOSF, VRO_OP_ATAN2F, VRO_OP_ACOSF,
+    VRO_OP_NORMALIZE3, VRO_OP_LEN3, VRO_OP_DOT3, VRO_OP_VMIN, VRO_OP_VMAX, VRO_OP_VCLAMP,
+    VRO_OP_LERPF, VRO_OP_RNG, VRO_OP_RNG3, VRO_OP_MAP_UINT_FLOAT,
+    VRO_OP_TFF_LINEAR, VRO_OP_TFF_LINEAR_RAW, VRO_OP_TFF_ALPHA, VRO_OP_TFF_ALPHA_RAW,
+    VRO_OP_PREFIX_NEAREST, VRO_OP_SKIP_TEST, VRO_OP_COUNT
+};
+typedef struct {
+    const uint8_t *tff;     /* RGBA8 transfer function (ops from VRO_OP_TFF_LINEAR on) */
+    uint32_t tff_n;
+    const uint32_t *prefix; /* VRO_OP_PREFIX_NEAREST, VRO_OP_SKIP_TEST */
+    uint32_t prefix_n;
+} vro_tables;
+int vro_math_arity(int op, int *n_in, int *n_out);
+int vro_math_batch(int op, size_t count, const uint32_t *in, uint32_t *out, const vro_tables *tables);
+
 #ifdef __cplusplus
 }
 #endif

@@ -197,6 +197,56 @@ def synth_volume(kind, res, fmt):
     return out
 
 
+# ids of vro_math_batch's operations (vr_oracle.h VRO_OP_*), in order
+MATH_OPS = ("logf", "powr", "sincosf", "atan2f", "acosf", "normalize3", "len3", "dot3", "vmin", "vmax",
+            "vclamp", "lerpf", "rng", "rng3", "map_uint_float", "tff_linear", "tff_linear_raw",
+            "tff_alpha", "tff_alpha_raw", "prefix_nearest", "skip_test")
+MATH_OP_ID = {name: i for i, name in enumerate(MATH_OPS)}
+
+
+class Tables(C.Structure):
+    _fields_ = [("tff", C.c_void_p), ("tff_n", C.c_uint32), ("prefix", C.c_void_p), ("prefix_n", C.c_uint32)]
+
+
+def math_arity(op):
+    """(argument words, result words) per element of operation `op` (a name of MATH_OPS)."""
+    ni, no = C.c_int(), C.c_int()
+    f = lib().vro_math_arity
+    f.restype = C.c_int
+    f.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    assert f(MATH_OP_ID[op], C.byref(ni), C.byref(no)) == 0
+    return ni.value, no.value
+
+
+def math_batch(op, args, tff=None, prefix=None):
+    """Operation `op` of the parity definitions on every row of args.
+
+    args: [count, n_in] of uint32 bit patterns (float32 arrays are reinterpreted); returns the result
+    bits, uint32 [count, n_out].  tff: RGBA8 table [n, 4], prefix: uint32 [n], for the table reads.
+    """
+    ni, no = math_arity(op)
+    args = np.ascontiguousarray(args)
+    if args.dtype == np.float32:
+        args = args.view(np.uint32)
+    assert args.dtype == np.uint32
+    args = args.reshape(-1, ni)
+    out = np.zeros((args.shape[0], no), dtype=np.uint32)
+    t = Tables()
+    if tff is not None:
+        tff = np.ascontiguousarray(tff, dtype=np.uint8).reshape(-1)
+        t.tff, t.tff_n = tff.ctypes.data, tff.size // 4
+    if prefix is not None:
+        prefix = np.ascontiguousarray(prefix, dtype=np.uint32)
+        t.prefix, t.prefix_n = prefix.ctypes.data, prefix.size
+    f = lib().vro_math_batch
+    f.restype = C.c_int
+    f.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(Tables)]
+    rc = f(MATH_OP_ID[op], args.shape[0], args.ctypes.data, out.ctypes.data, C.byref(t))
+    if rc != 0:
+        raise RuntimeError("vro_math_batch(%s) failed: %d" % (op, rc))
+    return out
+
+
 class FrameExtras(C.Structure):
     _fields_ = [("hit_in", C.c_void_p), ("hit_out", C.c_void_p), ("env_rgba", C.c_void_p),
                 ("env_w", C.c_uint32), ("env_h", C.c_uint32)]
