@@ -42,7 +42,8 @@ public:
         IN_HIT_IMG, OUT_HIT_IMG, ENVIRONMENT, CAMERA, RENDERING, RAYCAST, PATHTRACE
     };
     enum scaling_metric { MIN = 0, MAX, AVG, DENSITY };
-    enum technique { TECH_RAYCAST = 0, TECH_PATHTRACE = 1 };
+    // TECH_MIP: maximum intensity projection (VRHIP_TECHNIQUE_MIP, vrhip.h; no reference counterpart)
+    enum technique { TECH_RAYCAST = 0, TECH_PATHTRACE = 1, TECH_MIP = 2 };
 
     VolumeRenderCL();
     ~VolumeRenderCL();
@@ -175,6 +176,7 @@ private:
     void calcScaling();
     void pushParams();
     void beginFrame();
+    void advanceIteration();
     [[noreturn]] void fail(const char *what, int rc);
     void check(const char *what, int rc);
 

@@ -54,10 +54,26 @@ typedef struct vrhip_rendering_params {
     uint32_t showEss;
     uint32_t useLinear;
     uint32_t useGradient;
-    uint32_t technique;  /* 0 ray cast, 1 path tracing */
+    uint32_t technique;  /* 0 ray cast, 1 path tracing, 2 maximum intensity projection (VRHIP_TECHNIQUE_MIP) */
     uint32_t seed;
     uint32_t iteration;
 } vrhip_rendering_params; /* 64 bytes */
+
+/* rendering_params.technique == 2: maximum intensity projection (no reference counterpart; DESIGN.md "Maximum
+ * intensity projection").
+ *  Ray: exactly technique 0's -- view matrix, ortho switch, bbox_bl / bbox_tr, step length from samplingRate, start
+ *   jitter from the seed -- and technique 0's sample positions with object-order ESS off: t_0 = max(0, tnear),
+ *   t_{k+1} = t_k + stepSize while t_k < tfar (a step that no longer changes t ends the sequence).
+ *  Value: m = the maximum over those samples of the normalised, filtered channel-0 value (useLinear: trilinear or
+ *   nearest); a sample replaces m only when s > m, so a NaN sample never does; m starts at -inf.
+ *  Pixel: c = TF(m), the transfer-function read of the ray caster, no opacity correction, no shading;
+ *   rgb = c.rgb * c.a + bg.rgb * (1 - c.a), a = c.a + bg.a * (1 - c.a), bg = backgroundColor, every product and sum
+ *   one rounded fp32 operation in this order.  A ray that misses the box or takes no sample: bg unchanged.
+ *  Ignored: illumType, useGradient, contours, aerial.  VRHIP_ERR_UNSUPPORTED: imgEss, showEss, useAO, iteration > 0,
+ *   RG / RGBA volumes, a set environment map, vrhip_render_samples, vrhip_count_touched*, vrhip_count_fetched.
+ *  vrhip_set_object_ess: on, samples that provably cannot raise m are not fetched (cell grid, vrhip_download_cells);
+ *   no pixel changes.  Needs neither ESS bricks nor the prefix sum.  vrhip_get_stats: zeros. */
+#define VRHIP_TECHNIQUE_MIP 2u
 
 typedef struct vrhip_raycast_params {
     float samplingRate;
@@ -339,8 +355,9 @@ int vrhip_assemble_batch_rgba8(vrhip_renderer *r, void *hip_stream, const uint32
  * tile_ids == NULL: whole frames, out_dev[n_frames][height][width][4]; else the tile subset like
  * vrhip_render_tiles, out_dev[n_frames][n_tiles][tile_h][tile_w][4]; out_frame_stride != 0 gives the
  * distance between the frames of out_dev in pixels (>= one frame).  DEVICE output only (the
- * renderer's own frame buffer is not meaningful afterwards).  Ray caster, iteration 0, no
- * image-order ESS, no ambient occlusion: anything else is VRHIP_ERR_UNSUPPORTED. */
+ * renderer's own frame buffer is not meaningful afterwards).  Ray caster or maximum intensity
+ * projection (technique 0 or 2), iteration 0, no image-order ESS, no ambient occlusion: anything else is
+ * VRHIP_ERR_UNSUPPORTED. */
 int vrhip_render_batch(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t tile_w,
                        uint32_t tile_h, const uint32_t *tile_ids, uint32_t n_tiles,
                        const uint32_t *seeds, uint32_t n_frames, float *out_dev,
@@ -369,7 +386,7 @@ int vrhip_render_batch_views(vrhip_renderer *r, uint32_t width, uint32_t height,
  * out_rgba[n_tiles][tile_h][tile_w][4].  out_rgba may be NULL (the image stays in the frame buffer), host memory or
  * (out_is_device) device memory.  vrhip_get_stats: the sums over all samples; vrhip_last_kernel_seconds and
  * vrhip_last_launch_info: the last set, its fold included (with phase timing on, phase 2 is the fold).
- * Technique 0: VRHIP_ERR_UNSUPPORTED.  n_samples == 0 or seeds == NULL: VRHIP_ERR_INVALID. */
+ * Technique 0 or 2: VRHIP_ERR_UNSUPPORTED.  n_samples == 0 or seeds == NULL: VRHIP_ERR_INVALID. */
 int vrhip_render_samples(vrhip_renderer *r, uint32_t width, uint32_t height,
                          uint32_t tile_w, uint32_t tile_h, const uint32_t *tile_ids, uint32_t n_tiles,
                          const uint32_t *seeds, uint32_t n_samples, uint32_t samples_per_launch /* 0 = default */,
@@ -395,7 +412,8 @@ int vrhip_set_frame_timing(vrhip_renderer *r, int enabled);
  * are the ones that ran -- e.g. that the timed frames of the benchmark and the frames compared with the
  * oracle came out of the same kernels. */
 typedef struct vrhip_launch_info {
-    uint32_t technique;      /* 0 ray caster, 1 path tracer                                             */
+    uint32_t technique;      /* 0 ray caster, 1 path tracer, 2 maximum intensity projection (then only  */
+                             /* frames, work_items, empty_skip and views are filled, the rest is 0)     */
     uint32_t frames;         /* frames of the launch set (vrhip_render_batch), else 1                   */
     uint32_t work_items;     /* 8x8 patches in the work queue, all frames                               */
     uint32_t prepass;        /* 1: vr_dda_prepass_kernel ran                                            */
@@ -404,7 +422,8 @@ typedef struct vrhip_launch_info {
     uint32_t phase2_waves;   /* the same for vr_raycast_split_kernel; 0: single phase                   */
     uint32_t round_budget;   /* phase-1 sample rounds per ray, 0 = single phase                         */
     uint32_t footprint;      /* 1: the kernels read the footprint volume                                */
-    uint32_t empty_skip;     /* 1: the empty-run lookahead is on (cell grid handed to the kernels)      */
+    uint32_t empty_skip;     /* 1: the empty-run lookahead is on (cell grid handed to the kernels);     */
+                             /* technique 2: samples below the running maximum are skipped by that grid */
     uint32_t skip_in_lds;    /* 1: the ESS skip bitmap is staged in LDS (phase 1)                       */
     uint32_t instrumented;   /* 0 production kernels, 1 work counters, 2 / 3 + touched bitmap           */
     uint32_t extras;         /* 1: the variants with the rarer modes (illumType 2-5, AO, contours, ...) */

@@ -4,8 +4,9 @@ interface.  The product is `libvrhip.so` (csrc/, C ABI in include/vrhip.h); this
 the thin host-side mirror used by tests, bench.py and the multi-GPU tile driver."""
 from . import _lib, frontend
 from ._lib import (CameraParams, PathtraceParams, RaycastParams, RenderingParams, Stats,
-                   UCHAR, USHORT, FLOAT)
+                   UCHAR, USHORT, FLOAT, TECH_RAYCAST, TECH_PATHTRACE, TECH_MIP)
 from .renderer import VolumeRenderCL
 
 __all__ = ["VolumeRenderCL", "frontend", "_lib", "CameraParams", "RenderingParams",
-           "RaycastParams", "PathtraceParams", "Stats", "UCHAR", "USHORT", "FLOAT"]
+           "RaycastParams", "PathtraceParams", "Stats", "UCHAR", "USHORT", "FLOAT",
+           "TECH_RAYCAST", "TECH_PATHTRACE", "TECH_MIP"]

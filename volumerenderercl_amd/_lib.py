@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("VRHIP_LIB_PATH") or os.path.join(_HERE, "libvrhip.so"
 
 OK, ERR_INVALID, ERR_HIP, ERR_NODATA, ERR_UNSUPPORTED = range(5)
 UCHAR, USHORT, FLOAT = 0, 1, 2
+# rendering_params.technique: ray caster, path tracer, maximum intensity projection (VRHIP_TECHNIQUE_MIP)
+TECH_RAYCAST, TECH_PATHTRACE, TECH_MIP = 0, 1, 2
 
 
 class CameraParams(C.Structure):

@@ -146,7 +146,7 @@ void VolumeRenderCL::runRaycast(const size_t width, const size_t height)   // :5
     if (!_volLoaded) return;
     beginFrame();
     check("runRaycast", vrhip_render_frame(_r, uint32_t(width), uint32_t(height), nullptr, 0));
-    _rendering_params.iteration++;   // :540
+    advanceIteration();   // :540
 }
 
 void VolumeRenderCL::runRaycastNoGL(const size_t width, const size_t height,
@@ -157,7 +157,7 @@ void VolumeRenderCL::runRaycastNoGL(const size_t width, const size_t height,
     output.resize(width * height * 4);   // :583
     check("runRaycastNoGL", vrhip_render_frame(_r, uint32_t(width), uint32_t(height),
                                                output.data(), 0));
-    _rendering_params.iteration++;
+    advanceIteration();
 }
 
 void VolumeRenderCL::renderTiles(size_t width, size_t height, size_t tile_w, size_t tile_h,
@@ -169,7 +169,7 @@ void VolumeRenderCL::renderTiles(size_t width, size_t height, size_t tile_w, siz
     check("renderTiles", vrhip_render_tiles(_r, uint32_t(width), uint32_t(height), uint32_t(tile_w),
                                             uint32_t(tile_h), tile_ids.data(),
                                             uint32_t(tile_ids.size()), out_tiles_dev));
-    if (advanceIteration) _rendering_params.iteration++;
+    if (advanceIteration) this->advanceIteration();
 }
 
 size_t VolumeRenderCL::loadVolumeData(const DatRawReader::Properties volumeFileProps)   // :765-805
@@ -346,6 +346,13 @@ void VolumeRenderCL::setBackground(std::array<float, 4> color)   // :1025-1030
     _rendering_params.backgroundColor[1] = color[1];
     _rendering_params.backgroundColor[2] = color[2];
     _rendering_params.backgroundColor[3] = 0.f;
+}
+
+// A frame was rendered: the accumulating techniques move on to the next iteration; a maximum intensity
+// projection does not accumulate, every frame of it is iteration 0 (the library rejects anything else).
+void VolumeRenderCL::advanceIteration()
+{
+    if (_rendering_params.technique != TECH_MIP) _rendering_params.iteration++;
 }
 
 void VolumeRenderCL::setTechnique(technique tech)   // :1042-1047
@@ -535,7 +542,7 @@ void VolumeRenderCL::runRaycastRGBA8(size_t width, size_t height, std::vector<un
     beginFrame();
     output.resize(width * height * 4);
     check("runRaycastRGBA8", vrhip_render_frame_rgba8(_r, uint32_t(width), uint32_t(height), output.data(), 0));
-    _rendering_params.iteration++;
+    advanceIteration();
 }
 
 void VolumeRenderCL::frameRGBA8(size_t width, size_t height, std::vector<unsigned char> &output)

@@ -408,6 +408,10 @@ void write_rgba8(const std::string &out, const std::vector<unsigned char> &frame
         "         [--tf default|FILE] [--illum N] [--no-ess] [--ortho] [--nearest] [--rate R]\n"
         "         [--bg R G B] [--gradient-bg] [--seed S] [--frames N] [--device D] --out PREFIX\n"
         "         [--pathtrace] [--extinction E]   (technique 1; --frames = samples per pixel)\n"
+        "         [--mip]                          (technique 2, maximum intensity projection: independent frames only --\n"
+        "                                           one frame, --independent, --frames-per-launch, --camera-path / --orbit;\n"
+        "                                           combines with --rgba8; not with --pathtrace, --ao, --show-ess, --img-ess,\n"
+        "                                           --env)\n"
         "         [--samples-per-launch K]         (--pathtrace: the N samples in launch sets of K -- vrhip_render_samples,\n"
         "                                           the same image bit for bit; 0 = the library's default set size, the\n"
         "                                           default; 1 = one launch per sample, as before; with --bench: one\n"
@@ -460,7 +464,7 @@ int main(int argc, char **argv)
     size_t W = 1024, H = 1024;
     double q[4] = {1, 0, 0, 0}, tr[3] = {0, 0, 2};
     bool have_view = false, ess = true, ortho = false, linear = true, gradient_bg = false, pin = false;
-    bool pathtrace = false, device_ingest = false;
+    bool pathtrace = false, mip = false, device_ingest = false;
     double extinction = 100.0;
     int downsample = 0;
     std::string state_file, tf_stops, tf_easing = "linear", dump_tf;
@@ -505,6 +509,7 @@ int main(int argc, char **argv)
         else if (a == "--seed") { need(i, 1); seed = unsigned(std::strtoul(argv[++i], nullptr, 10)); pin = true; }
         else if (a == "--frames") { need(i, 1); frames = std::atoi(argv[++i]); }
         else if (a == "--pathtrace") pathtrace = true;
+        else if (a == "--mip") mip = true;
         else if (a == "--device-ingest") device_ingest = true;
         else if (a == "--downsample") { need(i, 1); downsample = std::atoi(argv[++i]); }
         else if (a == "--state") { need(i, 1); state_file = argv[++i]; }
@@ -543,6 +548,7 @@ int main(int argc, char **argv)
         else usage();
     }
     if (have_path_arg && (camera_path.empty() || have_orbit)) usage();
+    if (mip && pathtrace) usage();
     if (rgba8 && ranks > 0) {
         std::cerr << "--rgba8 cannot be combined with --ranks: the C++ tile gather carries float pixels "
                      "(8-bit frames over several GPUs: the Python TileDriver, pixel_format=\"rgba8\")" << std::endl;
@@ -666,6 +672,7 @@ int main(int argc, char **argv)
             vr.setTechnique(VolumeRenderCL::TECH_PATHTRACE);
             vr.setExtinction(extinction);
         }
+        if (mip) vr.setTechnique(VolumeRenderCL::TECH_MIP);
         if (pin) vr.setSeed(seed);
         vr.updateOutputImg(W, H, 0);
         vr.updateView(have_view ? view : view_matrix(q, tr));

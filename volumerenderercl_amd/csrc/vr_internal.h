@@ -297,6 +297,11 @@ struct RaycastLaunch {
     uint32_t sample_plane;
     float4 *fold_out;
     int keep_stats;            // launch_timed: the counters go on from the set before (chained sets of samples)
+    // technique 2 with object-order ESS: the (min, max) pairs of the cell grid of the current time step -- the fine grid
+    // (cells.ecx.., cells.eshift) when cell_minmax_fine is set, else the coarse one (cells.cx.., cells.shift) -- or
+    // nullptr: every sample is fetched
+    const float2 *cell_minmax;
+    int cell_minmax_fine;
 };
 
 // hipLaunchKernelGGL, or -- with an event -- the launch whose completion the event is bound to
@@ -346,10 +351,14 @@ constexpr int kLeapLevels = 7, kLeapRadius = 15;
 // alternate between); returns in *result the buffer that holds the table at the end
 hipError_t vr_launch_cell_leap_radius(const CellView &grid, const float *cbound, uint8_t *dist, const uint8_t **result,
                                       hipStream_t stream);
+// technique 2 (maximum intensity projection): one launch, one wave per 8x8 patch of every frame; vr_mip.hip
+hipError_t vr_launch_mip(const RaycastLaunch &a, hipStream_t stream);
 // the frame launch for a.render.technique
 inline hipError_t vr_launch_frame(const RaycastLaunch &a, hipStream_t stream)
 {
-    return a.render.technique == 1 ? vr_launch_pathtrace(a, stream) : vr_launch_raycast(a, stream);
+    return a.render.technique == VRHIP_TECHNIQUE_MIP ? vr_launch_mip(a, stream)
+           : a.render.technique == 1               ? vr_launch_pathtrace(a, stream)
+                                                   : vr_launch_raycast(a, stream);
 }
 
 // skip bitmap from bricks + TF + prefix

@@ -396,6 +396,8 @@ int prepare_slot(vrhip_renderer *r, const uint32_t res[3], int format, uint32_t 
 //     skip_version)                                  |                     | sum, current step
 //   cell (min,max) of a slot, coarse and fine        | ensure_cells        | that slot's voxels
 //     (pt_minmax_valid, fine_minmax_valid)           |                     |
+//     (read as they are by technique 2, which       |                     |
+//     derives nothing of its own from them)          |                     |
 //   opacity bounds / macro bounds / leap radii,      | ensure_cells        | cell (min,max) of the current step, TF,
 //     empty bits (cells_have_bound / _empty)         |                     | current step
 //   footprint volume (fp_valid, fp_timestep;         | ensure_footprint    | voxels of the current step, current step

@@ -117,6 +117,23 @@ bool ray_skip_empty(const vrhip_renderer *r)
     return std::max(r->brick_edge[0], std::max(r->brick_edge[1], r->brick_edge[2])) >= (4u << eshift);
 }
 
+// Technique 2 steps over samples that cannot raise the running maximum when object-order ESS is on
+// (VRHIP_NO_EMPTY_SKIP=1 disables this like the ray caster's empty runs).
+bool mip_skips(const vrhip_renderer *r) { return r->use_ess && r->skip_empty; }
+
+// The (min, max) pairs of a cell grid of the current time step as ensure_cells left them: the renderer's own, or
+// -- for a renderer that shares another one's voxels -- the owner's.  nullptr: not built.
+const float2 *cell_minmax_of(const vrhip_renderer *r, bool fine)
+{
+    const VolumeSlot &s = r->vols[r->timestep];
+    const float2 *src = fine ? (s.fine_minmax_valid ? s.fine_minmax.p : nullptr) : (s.pt_minmax_valid ? s.pt_minmax.p : nullptr);
+    if (!src && r->vol_owner && r->timestep < r->vol_owner->vols.size()) {
+        const VolumeSlot &os = r->vol_owner->vols[r->timestep];
+        src = fine ? (os.fine_minmax_valid ? os.fine_minmax.p : nullptr) : (os.pt_minmax_valid ? os.pt_minmax.p : nullptr);
+    }
+    return src;
+}
+
 // Sharers of `owner` lose their (borrowed) volumes: nothing of theirs points into the owner any more.
 void detach_sharers(vrhip_renderer *owner)
 {
@@ -201,12 +218,25 @@ int check_renderable(vrhip_renderer *r, uint32_t width, uint32_t height)
         VR_REQUIRE(r, r->prefix && r->prefix_n, VRHIP_ERR_NODATA,
                    "No transfer function prefix sum set.");
     }
-    VR_REQUIRE(r, r->render.technique <= 1, VRHIP_ERR_INVALID, "Unknown rendering technique.");
-    // the path-tracing branch of the kernel returns before illumType is looked at (:686-706)
-    VR_REQUIRE(r, r->render.illumType <= 5 || r->render.technique == 1, VRHIP_ERR_INVALID,
+    VR_REQUIRE(r, r->render.technique <= VRHIP_TECHNIQUE_MIP, VRHIP_ERR_INVALID, "Unknown rendering technique.");
+    // the path-tracing branch of the kernel returns before illumType is looked at (:686-706); technique 2 ignores it
+    VR_REQUIRE(r, r->render.illumType <= 5 || r->render.technique != 0, VRHIP_ERR_INVALID,
                "Unknown illumination type.");
-    VR_REQUIRE(r, r->render.technique == 0 || r->pathtrace.max_extinction > 0.f, VRHIP_ERR_INVALID,
+    VR_REQUIRE(r, r->render.technique != 1 || r->pathtrace.max_extinction > 0.f, VRHIP_ERR_INVALID,
                "max_extinction must be positive.");
+    if (r->render.technique == VRHIP_TECHNIQUE_MIP) {   // what the maximum intensity projection does not define
+        const vrhip_rendering_params &rp = r->render;
+        VR_REQUIRE(r, !rp.imgEss && !rp.showEss, VRHIP_ERR_UNSUPPORTED,
+                   "maximum intensity projection: image-order ESS and showEss are not supported.");
+        VR_REQUIRE(r, !r->raycast.useAO, VRHIP_ERR_UNSUPPORTED,
+                   "maximum intensity projection: ambient occlusion is not supported.");
+        VR_REQUIRE(r, rp.iteration == 0, VRHIP_ERR_UNSUPPORTED,
+                   "maximum intensity projection: frames do not accumulate (iteration must be 0).");
+        VR_REQUIRE(r, r->channels == 1, VRHIP_ERR_UNSUPPORTED,
+                   "maximum intensity projection: RG / RGBA volumes are not supported.");
+        VR_REQUIRE(r, !r->env, VRHIP_ERR_UNSUPPORTED,
+                   "maximum intensity projection: environment maps are not supported.");
+    }
     // technique 1 and the traffic / downsampling helpers read channel 0 only, like the kernel's
     // .x readers; nothing else to check for CL_RG / CL_RGBA volumes
     // the path-tracing branch returns before the hit image is written (:686-706): its state
@@ -567,6 +597,16 @@ void fill_launch(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t ou
     if (!r->pt_cull) { a->cells.bound = a->cells.cbound = nullptr; a->cells.cdist = nullptr; }
     // the empty bits are those of TF(channel 0): not what a CL_RG / CL_RGBA sample's opacity is
     if (!ray_skip_empty(r)) a->cells.empty = nullptr;
+    if (r->render.technique == VRHIP_TECHNIQUE_MIP) {
+        // (the kernel reads no table made from the transfer function: only the cells' (min, max) and their geometry)
+        a->cells.bound = a->cells.cbound = nullptr;
+        a->cells.cdist = nullptr;
+        a->cells.empty = nullptr;
+        if (mip_skips(r)) {
+            a->cell_minmax_fine = r->cells.eshift != r->cells.shift;
+            a->cell_minmax = cell_minmax_of(r, a->cell_minmax_fine != 0);
+        }
+    }
     a->format = r->format;
     a->use_ess = r->use_ess ? 1 : 0;
     a->instr = r->stats_enabled ? 1 : 0;
@@ -709,7 +749,8 @@ int prepare_render(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t 
         rc = ensure_footprint(r);
         if (rc) return rc;
     }
-    if (r->render.technique == 1 ? r->pt_cull : ray_skip_empty(r)) {
+    if (r->render.technique == 1 ? r->pt_cull : r->render.technique == VRHIP_TECHNIQUE_MIP ? mip_skips(r) : ray_skip_empty(r)) {
+        // (technique 2 reads the (min, max) of the grid the empty bits live on: built with them)
         rc = ensure_cells(r, r->render.technique == 1, r->render.technique != 1);
         if (rc) return rc;
     }
@@ -723,6 +764,8 @@ int count_touched_impl(vrhip_renderer *r, uint32_t width, uint32_t height, uint3
 {
     if (!r) return VRHIP_ERR_INVALID;
     if (set_device(r)) return VRHIP_ERR_HIP;
+    VR_REQUIRE(r, r->render.technique != VRHIP_TECHNIQUE_MIP, VRHIP_ERR_UNSUPPORTED,
+               "vrhip_count_touched / vrhip_count_fetched: not supported with maximum intensity projection.");
     int rc = prepare_render(r, width, height, tile_w, tile_h, tile_ids, n_tiles);
     if (rc) return rc;
     const size_t mb = (size_t)((r->res[0] + 3) / 4) * ((r->res[1] + 3) / 4) * ((r->res[2] + 3) / 4);
@@ -909,12 +952,7 @@ static int download_cells_impl(vrhip_renderer *r, bool fine, float *out_minmax, 
     if (!out_minmax) return VRHIP_OK;
     VR_REQUIRE(r, n_floats == 2 * n_cells, VRHIP_ERR_INVALID, "vrhip_download_cells: size mismatch");
     VR_HIP(r, hipStreamSynchronize(r->stream));
-    const VolumeSlot &s = r->vols[r->timestep];
-    const float2 *src = second ? (s.fine_minmax_valid ? s.fine_minmax : nullptr) : (s.pt_minmax_valid ? s.pt_minmax : nullptr);
-    if (!src && r->vol_owner && r->timestep < r->vol_owner->vols.size()) {   // tables read from the volumes' owner
-        const VolumeSlot &os = r->vol_owner->vols[r->timestep];
-        src = second ? (os.fine_minmax_valid ? os.fine_minmax : nullptr) : (os.pt_minmax_valid ? os.pt_minmax : nullptr);
-    }
+    const float2 *src = cell_minmax_of(r, second);   // (its own tables, or the volumes' owner's)
     VR_REQUIRE(r, src, VRHIP_ERR_NODATA, "vrhip_download_cells: no cell grid");
     VR_HIP(r, hipMemcpy(out_minmax, src, n_cells * sizeof(float2), hipMemcpyDeviceToHost));
     return VRHIP_OK;
@@ -1361,9 +1399,10 @@ int vrhip_render_batch_views(vrhip_renderer *r, uint32_t width, uint32_t height,
     // the frames of a batch are independent: nothing that chains frames, nothing that draws from
     // rendering_params.seed outside the ray set-up
     const vrhip_rendering_params &rp = r->render;
-    VR_REQUIRE(r, rp.technique == 0 && rp.iteration == 0 && !rp.imgEss && !r->raycast.useAO,
+    VR_REQUIRE(r, (rp.technique == 0 || rp.technique == VRHIP_TECHNIQUE_MIP) && rp.iteration == 0 && !rp.imgEss &&
+                      !r->raycast.useAO,
                VRHIP_ERR_UNSUPPORTED,
-               "vrhip_render_batch: ray caster only, iteration 0, no image-order ESS, no ambient occlusion");
+               "vrhip_render_batch: technique 0 or 2 only, iteration 0, no image-order ESS, no ambient occlusion");
     const uint32_t packed = tile_ids ? n_tiles * tile_w * tile_h : width * height;
     VR_REQUIRE(r, out_frame_stride == 0 || out_frame_stride >= packed, VRHIP_ERR_INVALID,
                "vrhip_render_batch: frame stride smaller than a frame");

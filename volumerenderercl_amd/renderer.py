@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib, frontend
 from ._lib import (CameraParams, PathtraceParams, RaycastParams, RenderingParams, Stats,
-                   UCHAR, USHORT, FLOAT)
+                   UCHAR, USHORT, FLOAT, TECH_MIP)
 
 NP_DTYPE = {UCHAR: np.uint8, USHORT: np.uint16, FLOAT: np.float32}
 _MT19937_DEFAULT_SEED = 5489   # std::mt19937 default constructor
@@ -219,6 +219,11 @@ class VolumeRenderCL:
             self._rendering.seed = self._fixed_seed
         self._push_params()
 
+    def _advance_iteration(self):
+        # a maximum intensity projection does not accumulate: every frame of it is iteration 0
+        if self._rendering.technique != TECH_MIP:
+            self._rendering.iteration += 1
+
     def runRaycast(self, width, height, out_dev_ptr=None):
         """volumerendercl.cpp:506-558: frame stays on the GPU; iteration advances (:540)."""
         if not self._vol_loaded:
@@ -226,7 +231,7 @@ class VolumeRenderCL:
         self._begin_frame()
         self._check(self._lib.vrhip_render_frame(self._h, int(width), int(height),
                                                  C.c_void_p(out_dev_ptr), 1 if out_dev_ptr else 0))
-        self._rendering.iteration += 1
+        self._advance_iteration()
 
     def runRaycastNoGL(self, width, height, output=None):
         """volumerendercl.cpp:568-607 with the documented contract honoured:
@@ -237,7 +242,7 @@ class VolumeRenderCL:
         out = np.empty((int(height), int(width), 4), dtype=np.float32)
         self._check(self._lib.vrhip_render_frame(self._h, int(width), int(height),
                                                  out.ctypes.data_as(C.c_void_p), 0))
-        self._rendering.iteration += 1   # accumulation advances in both paths
+        self._advance_iteration()   # accumulation advances in both paths
         if output is not None:
             output[:] = out.reshape(-1).tolist()
         return out
@@ -269,7 +274,7 @@ class VolumeRenderCL:
         out, ptr, dev = self._rgba8_out(out, (int(height), int(width), 4))
         self._begin_frame()
         self._check(self._lib.vrhip_render_frame_rgba8(self._h, int(width), int(height), C.c_void_p(ptr), dev))
-        self._rendering.iteration += 1
+        self._advance_iteration()
         return out
 
     def quantise_rgba8(self, frames, out=None, stream=None):
@@ -680,6 +685,7 @@ class VolumeRenderCL:
         self._rendering.useGradient = 1 if v else 0
 
     def setTechnique(self, tech):
+        """TECH_RAYCAST (0), TECH_PATHTRACE (1) or TECH_MIP (2, maximum intensity projection: include/vrhip.h)."""
         self._rendering.technique = int(tech)
         self._rendering.iteration = 0
 
