@@ -264,6 +264,19 @@ int vrhip_download_cells(vrhip_renderer *r, float *out_minmax, size_t n_floats, 
  * the grid above where the two coincide). */
 int vrhip_download_empty_cells(vrhip_renderer *r, float *out_minmax, size_t n_floats, uint32_t dims[3],
                                uint32_t *shift);
+/* What the renderer derives from those grids and the transfer function (vr_cells.hip), rebuilt for the current time
+ * step and transfer function and copied out; any output may be NULL.  For tests (tests/test_gpu_cell_tables.py).
+ *   out_bound  n_bound = cx*cy*cz floats: the opacity bound of every cell of the grid of vrhip_download_cells
+ *   out_macro  n_macro = ccx*ccy*ccz floats: the bound of every macro cell of 4 x 4 x 4 cells
+ *   out_leap   n_leap = 7 * n_macro bytes: level j = 1..7 (threshold j / 8) at [(j - 1) * n_macro + C]: 0 when macro
+ *              cell C is not free at that level, else 1 + the radius (<= 15) of the free cube of macro cells around it
+ *   out_empty  n_empty = (ecx*ecy*ecz + 31) / 32 words: bit (c & 31) of word c >> 5 = cell c of the grid of
+ *              vrhip_download_empty_cells is empty (every fetch in it reads opacity exactly 0)
+ *   dims       {cx, cy, cz, ccx, ccy, ccz, ecx, ecy, ecz};  shifts  {shift, eshift}
+ * All outputs NULL: dims / shifts only.  A size that does not match is VRHIP_ERR_INVALID. */
+int vrhip_download_cell_tables(vrhip_renderer *r, float *out_bound, size_t n_bound, float *out_macro, size_t n_macro,
+                               uint8_t *out_leap, size_t n_leap, uint32_t *out_empty, size_t n_empty, uint32_t dims[9],
+                               uint32_t shifts[2]);
 
 /* Image-tile gather, root side: the frame from the gathered tiles.  `staging_dev` holds
  * tile slots of tile_w x tile_h RGBA float pixels (the peers' blocks as received, one after the

@@ -81,6 +81,8 @@ SYMBOLS = {
     "vrhip_download_cells": (C.c_int, [_H, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "vrhip_download_empty_cells": (C.c_int, [_H, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32),
                                              C.POINTER(C.c_uint32)]),
+    "vrhip_download_cell_tables": (C.c_int, [_H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "vrhip_assemble_batch": (C.c_int, [_H, C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32,
                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                        C.c_uint32, C.c_void_p]),

@@ -970,6 +970,40 @@ int vrhip_download_empty_cells(vrhip_renderer *r, float *out_minmax, size_t n_fl
     return download_cells_impl(r, true, out_minmax, n_floats, dims, shift);
 }
 
+int vrhip_download_cell_tables(vrhip_renderer *r, float *out_bound, size_t n_bound, float *out_macro, size_t n_macro,
+                               uint8_t *out_leap, size_t n_leap, uint32_t *out_empty, size_t n_empty, uint32_t dims[9],
+                               uint32_t shifts[2])
+{
+    if (!r) return VRHIP_ERR_INVALID;
+    VR_REQUIRE(r, !r->vols.empty() && r->timestep < r->vols.size() && r->vols[r->timestep].dev,
+               VRHIP_ERR_NODATA, "No volume data is loaded.");
+    VR_REQUIRE(r, r->tff && r->tff_n, VRHIP_ERR_NODATA, "No transfer function set.");
+    if (set_device(r)) return VRHIP_ERR_HIP;
+    cells_tables_stale(r);   // (this call always rebuilds the tables)
+    int rc = ensure_cells(r, true, true);
+    if (rc) return rc;
+    const CellView &g = r->cells;
+    const size_t cells = (size_t)g.cx * g.cy * g.cz, macro = (size_t)g.ccx * g.ccy * g.ccz;
+    const size_t words = ((size_t)g.ecx * g.ecy * g.ecz + 31) / 32;
+    if (dims) {
+        const int d[9] = {g.cx, g.cy, g.cz, g.ccx, g.ccy, g.ccz, g.ecx, g.ecy, g.ecz};
+        for (int i = 0; i < 9; ++i) dims[i] = (uint32_t)d[i];
+    }
+    if (shifts) { shifts[0] = (uint32_t)g.shift; shifts[1] = (uint32_t)g.eshift; }
+    if (!out_bound && !out_macro && !out_leap && !out_empty) return VRHIP_OK;
+    VR_REQUIRE(r, (!out_bound || n_bound == cells) && (!out_macro || n_macro == macro) &&
+                  (!out_leap || n_leap == (size_t)kLeapLevels * macro) && (!out_empty || n_empty == words),
+               VRHIP_ERR_INVALID, "vrhip_download_cell_tables: size mismatch");
+    VR_REQUIRE(r, r->cell_bound && r->cell_dist_table && r->cell_empty, VRHIP_ERR_NODATA,
+               "vrhip_download_cell_tables: no cell tables");
+    VR_HIP(r, hipStreamSynchronize(r->stream));
+    if (out_bound) VR_HIP(r, hipMemcpy(out_bound, r->cell_bound, cells * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_macro) VR_HIP(r, hipMemcpy(out_macro, r->cell_bound + cells, macro * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_leap) VR_HIP(r, hipMemcpy(out_leap, r->cell_dist_table, (size_t)kLeapLevels * macro, hipMemcpyDeviceToHost));
+    if (out_empty) VR_HIP(r, hipMemcpy(out_empty, r->cell_empty, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return VRHIP_OK;
+}
+
 int vrhip_get_stream(const vrhip_renderer *r, void **hip_stream)
 {
     if (!r || !hip_stream) return VRHIP_ERR_INVALID;

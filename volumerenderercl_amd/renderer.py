@@ -643,6 +643,24 @@ class VolumeRenderCL:
         self._check(fn(self._h, out.ctypes.data_as(C.c_void_p), out.size, dims, C.byref(shift)))
         return out, int(shift.value)
 
+    def downloadCellTables(self):
+        """What the renderer derives from the cell grids and the transfer function (vrhip_download_cell_tables), rebuilt
+        and copied out: dict of bound [cz, cy, cx] and macro [ccz, ccy, ccx] float32, leap [7, ccz, ccy, ccx] uint8,
+        empty (uint32 words of the fine grid's bits), fine_dims (ecz, ecy, ecx), shift, eshift."""
+        fn = self._lib.vrhip_download_cell_tables
+        dims, shifts = (C.c_uint32 * 9)(), (C.c_uint32 * 2)()
+        self._check(fn(self._h, None, 0, None, 0, None, 0, None, 0, dims, shifts))
+        cx, cy, cz, ccx, ccy, ccz, ecx, ecy, ecz = (int(d) for d in dims)
+        bound = np.empty((cz, cy, cx), dtype=np.float32)
+        macro = np.empty((ccz, ccy, ccx), dtype=np.float32)
+        leap = np.empty((7, ccz, ccy, ccx), dtype=np.uint8)
+        empty = np.empty((ecx * ecy * ecz + 31) // 32, dtype=np.uint32)
+        self._check(fn(self._h, bound.ctypes.data_as(C.c_void_p), bound.size, macro.ctypes.data_as(C.c_void_p), macro.size,
+                       leap.ctypes.data_as(C.c_void_p), leap.size, empty.ctypes.data_as(C.c_void_p), empty.size,
+                       dims, shifts))
+        return {"bound": bound, "macro": macro, "leap": leap, "empty": empty, "fine_dims": (ecz, ecy, ecx),
+                "shift": int(shifts[0]), "eshift": int(shifts[1])}
+
     def lastBricksSeconds(self):
         return float(self._lib.vrhip_last_bricks_seconds(self._h))
 
