@@ -315,6 +315,42 @@ inline void vr_launch_kernel(F k, dim3 grid, dim3 block, size_t lds, hipStream_t
         hipLaunchKernelGGL(k, grid, block, lds, stream, args...);
 }
 
+// A technique that is one launch plus an optional last launch (MIP; the path tracer and its fold): first(start, stop)
+// and last(stop) launch with the events to bind, or nullptr.  The frame's start rides on the first launch and its end
+// on the last one there is; the event between the two (RaycastLaunch::mid_event) is recorded.
+template <typename First, typename Last>
+inline hipError_t vr_launch_bound(const RaycastLaunch &a, hipStream_t stream, bool has_last, First first, Last last)
+{
+    const bool bind_stop = a.bind_events && a.stop_event && a.stop_bound;
+    const bool bind_start = a.bind_events && a.start_event && a.start_bound;
+    first(bind_start ? a.start_event : nullptr, bind_stop && !has_last ? a.stop_event : nullptr);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && bind_start) *a.start_bound = true;
+    if (e == hipSuccess && a.mid_event) e = hipEventRecord(a.mid_event, stream);
+    if (has_last && e == hipSuccess) {
+        last(bind_stop ? a.stop_event : nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && bind_stop) *a.stop_bound = true;
+    return e;
+}
+
+// f(VoxelType<VT>()) for the voxel type of a vrhip_format; an unknown format is an error
+template <typename VT>
+struct VoxelType {
+    using type = VT;
+};
+template <typename F>
+inline hipError_t vr_for_format(int format, F f)
+{
+    switch (format) {
+    case VRHIP_UCHAR: return f(VoxelType<uint8_t>());
+    case VRHIP_USHORT: return f(VoxelType<uint16_t>());
+    case VRHIP_FLOAT: return f(VoxelType<float>());
+    default: return hipErrorInvalidValue;
+    }
+}
+
 hipError_t vr_launch_raycast(const RaycastLaunch &a, hipStream_t stream);
 // FrameView::patch_class for the n_patches patches of a set of set_frames frames (work item p * set_frames = patch
 // p of frame 0); the launch's camera, parameters, skip bitmaps and queue must be those of the frames to come

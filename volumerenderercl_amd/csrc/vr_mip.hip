@@ -18,14 +18,12 @@
 // bound comes from the cell grid (CellView, vr_cells.hip): per cell of 2^shift voxels the (min, max) of the RAW
 // voxels [(c << shift) - 1, ((c + 1) << shift) + 1] per axis.  Two things make `max * inv_max <= m` a proof:
 //
-//  (1) The bound covers the filter's footprint.  The cell is looked up from a linearised texel position
-//      u' = p * res + k * du' (empty_mask's scheme, vr_raycast_kernels.h): the trilinear fetch's low-corner texel is
-//      x0 = floor(u' - 0.5), so x' = floor(u') is x0 or x0 + 1 -- also with the linearisation's error, far below half
-//      a texel over kMipLook steps inside a box of size 2 -- and the voxels x0, x0 + 1 lie in [x' - 1, x' + 1], inside
-//      the extent of the cell of x'.  The nearest fetch reads voxel floor(u) = x' (or a neighbour, with that error).
-//      Positions outside the volume clamp to the border cell like the fetch's clamp-to-edge addressing; the nearest
-//      sampler answers 0 there (border colour), so its bound is max(cell bound, 0).  (The reference's ESS bricks hold
-//      the voxels of the brick alone, no halo: a fetch at a brick face reads a voxel they do not cover.)
+//  (1) The bound covers the filter's footprint.  The cell is looked up from the ray's cell line (vr_sampling.h, "the
+//      cell of a point on a line": floor(u') is the trilinear fetch's low-corner texel or the next one -- also with the
+//      linearisation's error over kMipLook steps -- the halo covers the voxels it reads, positions outside the volume
+//      clamp to the border cell).  The nearest fetch reads voxel floor(u) = x' (or a neighbour, with that error); it
+//      answers 0 outside the volume (border colour), so its bound is max(cell bound, 0).  (The reference's ESS bricks
+//      hold the voxels of the brick alone, no halo: a fetch at a brick face reads a voxel they do not cover.)
 //  (2) The fp32 interpolation stays within [min, max] of its corners.  lerpf(p, q, w) = fmaf(w, d, p) with
 //      d = fl(q - p) = (q - p)(1 + e), |e| <= 2^-24 (exact when the difference is subnormal).  The weights are
 //      w = fl(ub - floor(ub)):
@@ -51,26 +49,13 @@ template <typename V>
 VR_DEV uint32_t mip_need_mask(const CellView &grid, const float2 *mm, const V &vol, const RayCtx &c, float t0, float m,
                               bool linear)
 {
-    const f3 p0 = add3(c.cam, scale3(c.dir, t0 - c.offset));
-    const float inv_e = __uint_as_float((uint32_t)(127 - grid.eshift) << 23);   // 2^-eshift
-    const float su = vol.fw * inv_e, sv = vol.fh * inv_e, ss = vol.fd * inv_e;
-    const float u0 = (p0.x * 0.5f + 0.5f) * su;
-    const float v0 = (p0.y * 0.5f + 0.5f) * sv;
-    const float s0 = (p0.z * 0.5f + 0.5f) * ss;
-    const float du = (c.dir.x * c.stepSize) * (0.5f * su);
-    const float dv = (c.dir.y * c.stepSize) * (0.5f * sv);
-    const float ds = (c.dir.z * c.stepSize) * (0.5f * ss);
-    const float mx = (float)(grid.ecx - 1), my = (float)(grid.ecy - 1), mz = (float)(grid.ecz - 1);
+    const CellLine line = cell_line_ray(add3(c.cam, scale3(c.dir, t0 - c.offset)), c.dir, c.stepSize, vol, grid.eshift,
+                                        grid.ecx, grid.ecy, grid.ecz);
     constexpr float kHalfMax = 0x1.fffffep126f;   // FLT_MAX / 2
     uint32_t need = 0;
 #pragma unroll
     for (int k = 0; k < kMipLook; ++k) {
-        const float fk = (float)k;
-        // (signed clamp in the float domain, then the conversion: see empty_mask)
-        const uint32_t x = (uint32_t)(int)__builtin_amdgcn_fmed3f(__builtin_fmaf(fk, du, u0), 0.f, mx);
-        const uint32_t y = (uint32_t)(int)__builtin_amdgcn_fmed3f(__builtin_fmaf(fk, dv, v0), 0.f, my);
-        const uint32_t z = (uint32_t)(int)__builtin_amdgcn_fmed3f(__builtin_fmaf(fk, ds, s0), 0.f, mz);
-        const float2 b = mm[(z * (uint32_t)grid.ecy + y) * (uint32_t)grid.ecx + x];
+        const float2 b = mm[cell_index_of(cell_at(line, (float)k), grid.ecx, grid.ecy)];
         float bound = b.y * vol.inv_max;
         if (!linear) bound = vmax(bound, 0.f);
         const bool known = b.x <= b.y && fabsf(b.x) <= kHalfMax && fabsf(b.y) <= kHalfMax && bound <= m;
@@ -176,16 +161,13 @@ hipError_t launch_mip(const RaycastLaunch &a, hipStream_t stream)
     // the cell grid the (min, max) pairs live on, in the e* fields: the fine grid, or the only one (ensure_cells)
     CellView g = a.cells;
     if (a.cell_minmax && !a.cell_minmax_fine) { g.ecx = g.cx; g.ecy = g.cy; g.ecz = g.cz; g.eshift = g.shift; }
-    const bool bind_stop = a.bind_events && a.stop_event && a.stop_bound;   // (one launch: it carries the frame's end)
-    const bool bind_start = a.bind_events && a.start_event && a.start_bound;
-    vr_launch_kernel(vr_mip_kernel<VT, VIEWS>, grid, block, 0, stream, bind_start ? a.start_event : nullptr,
-                     bind_stop ? a.stop_event : nullptr, a.vol, a.tf, g, a.cell_minmax, a.frame, a.cam, a.render,
-                     a.raycast);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && bind_start) *a.start_bound = true;
-    if (e == hipSuccess && a.mid_event) e = hipEventRecord(a.mid_event, stream);
-    if (e == hipSuccess && bind_stop) *a.stop_bound = true;
-    return e;
+    return vr_launch_bound(
+        a, stream, false,
+        [&](hipEvent_t start, hipEvent_t stop) {
+            vr_launch_kernel(vr_mip_kernel<VT, VIEWS>, grid, block, 0, stream, start, stop, a.vol, a.tf, g, a.cell_minmax,
+                             a.frame, a.cam, a.render, a.raycast);
+        },
+        [](hipEvent_t) {});
 }
 
 template <typename VT>
@@ -203,10 +185,5 @@ hipError_t vr_launch_mip(const RaycastLaunch &a, hipStream_t stream)
         a.info->work_items = a.frame.n_wave_tiles;
         a.info->empty_skip = a.cell_minmax ? 1u : 0u;
     }
-    switch (a.format) {
-    case VRHIP_UCHAR: return launch_mip_typed<uint8_t>(a, stream);
-    case VRHIP_USHORT: return launch_mip_typed<uint16_t>(a, stream);
-    case VRHIP_FLOAT: return launch_mip_typed<float>(a, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return vr_for_format(a.format, [&](auto vt) { return launch_mip_typed<typename decltype(vt)::type>(a, stream); });
 }

@@ -300,13 +300,7 @@ hipError_t vr_launch_patch_classes(const RaycastLaunch &a, uint32_t n_patches, u
                                    hipStream_t stream)
 {
     if (!n_patches) return hipSuccess;
-    Grid hg;   // (as in launch_variant: what make_grid gives on the device)
-    hg.bw = a.bricks.bw; hg.bh = a.bricks.bh; hg.bd = a.bricks.bd;
-    hg.oob_word = a.skip.n_words;
-    hg.bl0 = 1.f / a.raycast.brickRes[0];
-    hg.bl1 = 1.f / a.raycast.brickRes[1];
-    hg.bl2 = 1.f / a.raycast.brickRes[2];
-    hg.brickDia = sqrtf(((hg.bl0 * hg.bl0) + (hg.bl1 * hg.bl1)) + (hg.bl2 * hg.bl2)) * 2.f;
+    const Grid hg = make_grid_host(a);
     hipLaunchKernelGGL(vr_patch_class_kernel, dim3((n_patches + 3u) / 4u), dim3(kBlockDim), 0, stream, a.skip, a.frame,
                        a.cam, a.render, hg, n_patches, set_frames, cls);
     return hipGetLastError();

@@ -728,40 +728,18 @@ constexpr int kLook1 = VR_LOOK1, kLook2 = VR_LOOK2;
 
 // Bit k set: sample k of the run t0, t0 + stepSize, ... lies in an EMPTY cell (CellView): its
 // fetch can only map to opacity 0, so compositing it changes nothing (:864-879 with alpha == 0).
-// The cell comes from a linearised voxel position u' = p * res (+ k * du'), in cells: the fetch's
-// low-corner texel is x0 = floor(u' - 0.5), so x' = floor(u') is x0 or x0 + 1 -- also with the
-// linearisation's error, which is far below half a texel -- and the voxels x0, x0 + 1 the fetch reads
-// lie in [x' - 1, x' + 1], inside the extent [E c - 1, E c + E + 1] the cell of x' answers for (the
-// halo is there for exactly this).  Three instructions per axis and sample, no voxel access.
-// Positions outside the volume (samples before the entry face, speculative samples past the ray's
-// end) clamp to the nearest border cell, like the fetch's clamp-to-edge addressing.
+// The cell of a sample comes from the ray's cell line (vr_sampling.h, "the cell of a point on a line": why the cell of
+// floor(u') answers for the fetch's voxels, the signed clamp, positions outside the volume).  Three instructions per
+// axis and sample, no voxel access.
 template <typename VT, int INSTR, int kLook, typename V>
 VR_DEV uint32_t empty_mask(const CellView &cv, const V &vol, const RayCtx &c, float t0)
 {
-    const f3 p0 = add3(c.cam, scale3(c.dir, t0 - c.offset));
-    const float inv_e = __uint_as_float((uint32_t)(127 - cv.eshift) << 23);   // 2^-eshift
-    const float su = vol.fw * inv_e, sv = vol.fh * inv_e, ss = vol.fd * inv_e;
-    const float u0 = (p0.x * 0.5f + 0.5f) * su;
-    const float v0 = (p0.y * 0.5f + 0.5f) * sv;
-    const float s0 = (p0.z * 0.5f + 0.5f) * ss;
-    const float du = (c.dir.x * c.stepSize) * (0.5f * su);
-    const float dv = (c.dir.y * c.stepSize) * (0.5f * sv);
-    const float ds = (c.dir.z * c.stepSize) * (0.5f * ss);
-    const float mx = (float)(cv.ecx - 1), my = (float)(cv.ecy - 1), mz = (float)(cv.ecz - 1);
+    const CellLine line = cell_line_ray(add3(c.cam, scale3(c.dir, t0 - c.offset)), c.dir, c.stepSize, vol, cv.eshift,
+                                        cv.ecx, cv.ecy, cv.ecz);
     uint32_t w[kLook], sh[kLook];
 #pragma unroll
     for (int k = 0; k < kLook; ++k) {
-        const float fk = (float)k;
-        // Signed clamp: real samples near tnear lie up to 2 |voxLen| BEFORE the entry face (t - offset, :733 /
-        // :791) and are fetched clamp-to-edge, i.e. they read column 0 -- on an anisotropic grid that is several
-        // cells below 0, and an unsigned clamp would send them to the far border's cell.  The clamp is taken in
-        // the float domain, BEFORE the conversion (one v_med3_f32 instead of an integer max and min: the compiler
-        // cannot prove 0 <= mx for a v_med3_i32): trunc(clamp(v, 0, mx)) == clamp(trunc(v), 0, mx) for every
-        // finite v and integer mx >= 0 -- an index, not an fp32 result of the image.
-        const uint32_t x = (uint32_t)(int)__builtin_amdgcn_fmed3f(__builtin_fmaf(fk, du, u0), 0.f, mx);
-        const uint32_t y = (uint32_t)(int)__builtin_amdgcn_fmed3f(__builtin_fmaf(fk, dv, v0), 0.f, my);
-        const uint32_t z = (uint32_t)(int)__builtin_amdgcn_fmed3f(__builtin_fmaf(fk, ds, s0), 0.f, mz);
-        const uint32_t idx = (z * (uint32_t)cv.ecy + y) * (uint32_t)cv.ecx + x;
+        const uint32_t idx = cell_index_of(cell_at(line, (float)k), cv.ecx, cv.ecy);
         w[k] = cv.empty[idx >> 5];
         sh[k] = idx & 31u;
     }
@@ -1058,26 +1036,6 @@ VR_DEV void write_pixel(const FrameView &fr, const vrhip_rendering_params &rp, c
         fr.hit_any[(size_t)(gy >> 3) * fr.hit_w + (gx >> 3)] = 1;
 }
 
-template <typename VT, int INSTR, bool FP>
-VR_DEV Vol<VT, INSTR, FP> make_vol(const VolView &vv, uint32_t *touched)
-{
-    Vol<VT, INSTR, FP> vol;
-    vol.p = (const VT *)vv.data;
-    vol.w1 = vv.w - 1; vol.h1 = vv.h - 1; vol.d1 = vv.d - 1;
-    vol.fw = vv.fw; vol.fh = vv.fh; vol.fd = vv.fd;
-    vol.inv_max = vv.inv_max;
-    vol.nbx = vv.nbx; vol.nby = vv.nby;
-    vol.ystride = vv.ystride; vol.zstride = (uint32_t)vv.zstride;
-    vol.touched = touched;
-    vol.pc[0] = (const VT *)vv.chan[0]; vol.pc[1] = (const VT *)vv.chan[1];
-    vol.pc[2] = (const VT *)vv.chan[2];
-    vol.channels = vv.channels;
-    vol.fp = (const FpEntry<VT> *)vv.fp;
-    vol.fp_ystride = vv.fp_nbx * 64u;
-    vol.fp_zstride = vv.fp_nbx * vv.fp_nby * 64u;
-    return vol;
-}
-
 VR_DEV Grid make_grid(const BrickView &bricks, const vrhip_raycast_params &rcp, uint32_t oob_word,
                       bool ess)
 {
@@ -1093,6 +1051,20 @@ VR_DEV Grid make_grid(const BrickView &bricks, const vrhip_raycast_params &rcp, 
         g.brickDia = sqrtf(((g.bl0 * g.bl0) + (g.bl1 * g.bl1)) + (g.bl2 * g.bl2)) * 2.f;
     }
     return g;
+}
+
+// make_grid(bricks, rc, n_words, true), computed once on the host with the same IEEE operations: for the kernels that
+// take the grid as an argument (the pre-pass, the patch classes)
+inline Grid make_grid_host(const RaycastLaunch &a)
+{
+    Grid hg;
+    hg.bw = a.bricks.bw; hg.bh = a.bricks.bh; hg.bd = a.bricks.bd;
+    hg.oob_word = a.skip.n_words;
+    hg.bl0 = 1.f / a.raycast.brickRes[0];
+    hg.bl1 = 1.f / a.raycast.brickRes[1];
+    hg.bl2 = 1.f / a.raycast.brickRes[2];
+    hg.brickDia = sqrtf(((hg.bl0 * hg.bl0) + (hg.bl1 * hg.bl1)) + (hg.bl2 * hg.bl2)) * 2.f;
+    return hg;
 }
 
 // What a marching kernel derives once per launch from its arguments, the same in every ray.  (The pre-pass gets grid and
@@ -1915,14 +1887,7 @@ hipError_t launch_variant(const RaycastLaunch &a, hipStream_t stream)
     // the events of the frame's timing ride on the launches themselves (RaycastLaunch::stop_event, start_event)
     hipEvent_t start_ev = (a.bind_events && a.start_bound) ? a.start_event : nullptr;
     if (ESS && INSTR == 0 && frame.live) {
-        // what make_grid(bricks, rc, n_words, true) and 1 / resolution give on the device
-        Grid hg;
-        hg.bw = a.bricks.bw; hg.bh = a.bricks.bh; hg.bd = a.bricks.bd;
-        hg.oob_word = a.skip.n_words;
-        hg.bl0 = 1.f / a.raycast.brickRes[0];
-        hg.bl1 = 1.f / a.raycast.brickRes[1];
-        hg.bl2 = 1.f / a.raycast.brickRes[2];
-        hg.brickDia = sqrtf(((hg.bl0 * hg.bl0) + (hg.bl1 * hg.bl1)) + (hg.bl2 * hg.bl2)) * 2.f;
+        const Grid hg = make_grid_host(a);
         f3 hv;
         hv.x = 1.f / a.vol.fw; hv.y = 1.f / a.vol.fh; hv.z = 1.f / a.vol.fd;
         vr_launch_kernel(vr_dda_prepass_kernel<VT, VIEWS>, dim3(want), block, 0, stream, start_ev, nullptr, a.vol, a.bricks,

@@ -366,6 +366,107 @@ struct Vol {
     }
 };
 
+template <typename VT, int INSTR, bool FP>
+VR_DEV Vol<VT, INSTR, FP> make_vol(const VolView &vv, uint32_t *touched)
+{
+    Vol<VT, INSTR, FP> vol;
+    vol.p = (const VT *)vv.data;
+    vol.w1 = vv.w - 1; vol.h1 = vv.h - 1; vol.d1 = vv.d - 1;
+    vol.fw = vv.fw; vol.fh = vv.fh; vol.fd = vv.fd;
+    vol.inv_max = vv.inv_max;
+    vol.nbx = vv.nbx; vol.nby = vv.nby;
+    vol.ystride = vv.ystride; vol.zstride = (uint32_t)vv.zstride;
+    vol.touched = touched;
+    vol.pc[0] = (const VT *)vv.chan[0]; vol.pc[1] = (const VT *)vv.chan[1];
+    vol.pc[2] = (const VT *)vv.chan[2];
+    vol.channels = vv.channels;
+    vol.fp = (const FpEntry<VT> *)vv.fp;
+    vol.fp_ystride = vv.fp_nbx * 64u;
+    vol.fp_zstride = vv.fp_nbx * vv.fp_nby * 64u;
+    return vol;
+}
+
+// ------------------------------------------------------------------ the cell of a point on a line
+//
+// Every cell-grid lookup of the renderer (CellView: the ray caster's empty runs, MIP's bounds, the path tracer's
+// cull and its leap's landing check) finds the cell of a fetch position from a LINE in cell units,
+// u'(s) = a + b * s per axis with u' = p * res / E (E = 2^shift voxels per cell), with one fma, one float-domain
+// clamp and one truncating conversion per axis: cell_at.  What makes that cell the right one to ask, proved here once:
+//  (1) x' = floor(u') is x0 or x0 + 1.  In voxels, the trilinear fetch's low-corner texel is x0 = floor(u' - 0.5), so
+//      floor(u') is x0 or x0 + 1 -- also with the line's rounding error (the linearisation over a few dozen samples
+//      inside a box of size 2, one fma), which is far below half a texel.  (The nearest fetch reads voxel floor(u) = x',
+//      or a neighbour with that error.)
+//  (2) The halo covers the footprint.  The voxels x0, x0 + 1 the fetch reads lie in [x' - 1, x' + 1], inside the extent
+//      [E c - 1, E c + E + 1] the cell c of x' answers for: the cells' one-texel halo is there for exactly this.
+//  (3) The float-domain signed clamp equals the integer clamp.  trunc(clamp(v, 0, m)) == clamp(trunc(v), 0, m) for
+//      every finite v and integer m >= 0: the conversion truncates towards zero, so a coordinate in (-1, 0) becomes 0
+//      either way.  One v_med3_f32 where the integer clamp is a max and a min (the compiler cannot prove 0 <= m for a
+//      v_med3_i32) -- an index, not an fp32 result of the image.  The clamp is SIGNED: real samples near tnear lie up
+//      to 2 |voxLen| BEFORE the entry face (t - offset, :733 / :791) and read column 0 -- on an anisotropic grid that
+//      is several cells below 0, and an unsigned clamp would send them to the far border's cell.
+//  (4) Positions outside the volume (samples before the entry face, speculative samples past the end of a ray or a
+//      walk) go to the nearest border cell, like the fetch's clamp-to-edge addressing.
+//  (5) trunc(med3(fma(b, s, a), 0, m)) is monotone in s: the fma's single rounding, the clamp and the truncation all
+//      are.  What holds for the cells at both ends of a stretch of the line holds for every cell in between.
+// The two constructors (cell_line_ray, VR_CELL_LINE_WALK) are NOT interchangeable: (p * 0.5 + 0.5) * su and
+// fma(org, h, h) round differently, and each site's cells are part of what its tests pin.  They share the three
+// operations (VR_CELL_AXIS, which cell_at is made of) and the clamp.
+struct CellLine {
+    float ax, bx, ay, by, az, bz;   // per axis: offset a and slope b, in cells
+    float mx, my, mz;               // clamp maximum: cells - 1
+};
+struct Cell {
+    uint32_t x, y, z;
+};
+
+// cell_at's three operations for one axis, and the clamp maximum of an axis of `cells` cells.  Macros, so that the
+// path tracer -- whose register allocation does not survive a CellLine in its kernel -- expands the
+// very same text on its own locals.
+#define VR_CELL_AXIS(a, b, s, m) ((uint32_t)(int)__builtin_amdgcn_fmed3f(__builtin_fmaf(b, s, a), 0.f, m))
+#define VR_CELL_MAX(cells) ((float)((cells) - 1))
+
+// the samples of a marched ray: sample k = origin + dir * (k * step), looked up with s = (float)k
+template <typename V>
+VR_DEV CellLine cell_line_ray(f3 origin, f3 dir, float step, const V &vol, int shift, int cx, int cy, int cz)
+{
+    const float inv_e = __uint_as_float((uint32_t)(127 - shift) << 23);   // 2^-shift
+    const float su = vol.fw * inv_e, sv = vol.fh * inv_e, ss = vol.fd * inv_e;
+    CellLine l;
+    l.ax = (origin.x * 0.5f + 0.5f) * su;
+    l.ay = (origin.y * 0.5f + 0.5f) * sv;
+    l.az = (origin.z * 0.5f + 0.5f) * ss;
+    l.bx = (dir.x * step) * (0.5f * su);
+    l.by = (dir.y * step) * (0.5f * sv);
+    l.bz = (dir.z * step) * (0.5f * ss);
+    l.mx = VR_CELL_MAX(cx); l.my = VR_CELL_MAX(cy); l.mz = VR_CELL_MAX(cz);
+    return l;
+}
+
+// a tracking walk: the step at parameter t = org + wdir * t, looked up with s = t.  Declares the line's offsets ax, ay,
+// az, slopes bx, by, bz and clamp maxima mx, my, mz as locals (in place of a CellLine: see VR_CELL_AXIS).
+#define VR_CELL_LINE_WALK(org, wdir, vol, shift, cx, cy, cz)                                                          \
+    const float inv_e = __uint_as_float((uint32_t)(127 - (shift)) << 23); /* 2^-shift */                             \
+    const float hx = 0.5f * (vol).fw * inv_e, hy = 0.5f * (vol).fh * inv_e, hz = 0.5f * (vol).fd * inv_e;             \
+    const float ax = __builtin_fmaf((org).x, hx, hx), bx = (wdir).x * hx;                                             \
+    const float ay = __builtin_fmaf((org).y, hy, hy), by = (wdir).y * hy;                                             \
+    const float az = __builtin_fmaf((org).z, hz, hz), bz = (wdir).z * hz;                                             \
+    const float mx = VR_CELL_MAX(cx), my = VR_CELL_MAX(cy), mz = VR_CELL_MAX(cz)
+
+VR_DEV Cell cell_at(const CellLine &l, float s)
+{
+    Cell c;
+    c.x = VR_CELL_AXIS(l.ax, l.bx, s, l.mx);
+    c.y = VR_CELL_AXIS(l.ay, l.by, s, l.my);
+    c.z = VR_CELL_AXIS(l.az, l.bz, s, l.mz);
+    return c;
+}
+
+// x-fastest index of a cell in a grid of cx * cy * .. cells
+VR_DEV uint32_t cell_index_of(Cell c, int cx, int cy)
+{
+    return (c.z * (uint32_t)cy + c.y) * (uint32_t)cx + c.x;
+}
+
 // Can a density of voxel type VT lie outside [0, 1]?  UNORM voxels (UCHAR, USHORT) cannot; FLOAT voxels are raw
 // values (a CT volume in Hounsfield units, any simulation field), including +-inf and NaN.
 template <typename VT>
