@@ -43,7 +43,8 @@ public:
     };
     enum scaling_metric { MIN = 0, MAX, AVG, DENSITY };
     // TECH_MIP: maximum intensity projection (VRHIP_TECHNIQUE_MIP, vrhip.h; no reference counterpart)
-    enum technique { TECH_RAYCAST = 0, TECH_PATHTRACE = 1, TECH_MIP = 2 };
+    // TECH_ISO: first-hit isosurface (VRHIP_TECHNIQUE_ISO, vrhip.h; no reference counterpart; 3 is unassigned)
+    enum technique { TECH_RAYCAST = 0, TECH_PATHTRACE = 1, TECH_MIP = 2, TECH_ISO = 4 };
 
     VolumeRenderCL();
     ~VolumeRenderCL();
@@ -86,6 +87,10 @@ public:
     void setUseGradient(bool useGradient);
     void setTechnique(technique tech);
     void setExtinction(const double extinction);
+    // TECH_ISO (no reference counterpart): the threshold, in the units of the transfer function's coordinate (default
+    // 0.5), and the bisection rounds that refine the hit (0-16, default 4); vrhip_iso_params
+    void setIsoValue(float isoValue);
+    void setIsoRefinement(unsigned int refineSteps);
     void setBBox(float bl_x, float bl_y, float bl_z, float tr_x, float tr_y, float tr_z);
     void setTimestep(const size_t t);
 
@@ -192,6 +197,7 @@ private:
     rendering_params _rendering_params;
     raycast_params _raycast_params;
     pathtrace_params _pathtrace_params;
+    vrhip_iso_params _iso_params;
     DatRawReader _dr;
     bool _synthetic = false;
     bool _deviceIngest = false;

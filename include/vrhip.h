@@ -54,7 +54,8 @@ typedef struct vrhip_rendering_params {
     uint32_t showEss;
     uint32_t useLinear;
     uint32_t useGradient;
-    uint32_t technique;  /* 0 ray cast, 1 path tracing, 2 maximum intensity projection (VRHIP_TECHNIQUE_MIP) */
+    uint32_t technique;  /* 0 ray cast, 1 path tracing, 2 maximum intensity projection (VRHIP_TECHNIQUE_MIP),
+                            4 first-hit isosurface (VRHIP_TECHNIQUE_ISO); 3 is unassigned and rejected */
     uint32_t seed;
     uint32_t iteration;
 } vrhip_rendering_params; /* 64 bytes */
@@ -74,6 +75,39 @@ typedef struct vrhip_rendering_params {
  *  vrhip_set_object_ess: on, samples that provably cannot raise m are not fetched (cell grid, vrhip_download_cells);
  *   no pixel changes.  Needs neither ESS bricks nor the prefix sum.  vrhip_get_stats: zeros. */
 #define VRHIP_TECHNIQUE_MIP 2u
+
+/* rendering_params.technique == 4: first-hit isosurface rendering (no reference counterpart; DESIGN.md "First-hit
+ * isosurface").  The value 3 is unassigned: it answers "Unknown rendering technique." like every other value.
+ *  Parameters: vrhip_iso_params below (vrhip_set_iso_params), since rendering_params mirrors the reference's layout.
+ *   isoValue is in the units of the transfer function's coordinate: the normalised channel-0 value for UCHAR and
+ *   USHORT volumes, the raw value for FLOAT.  Defaults: isoValue 0.5, refineSteps 4.  A non-finite isoValue or
+ *   refineSteps > 16: VRHIP_ERR_INVALID from the render calls while technique 4 is selected.
+ *  Ray: exactly technique 0's with object-order ESS off, as for technique 2: t_0 = max(0, tnear),
+ *   t_{k+1} = t_k + stepSize while t_k < tfar, sample k at cam + dir * (t_k - offset); a step that no longer changes t
+ *   ends the sequence.
+ *  Hit: the first k whose normalised, filtered channel-0 value (useLinear: trilinear or nearest) satisfies
+ *   s_k >= isoValue.  A NaN sample never hits.  A ray that starts inside the solid hits at k = 0: the clip box caps
+ *   the surface.
+ *  Refinement (skipped when k = 0 or refineSteps = 0): ta = t_{k-1}, tb = t_k; refineSteps times tm = (ta + tb) * 0.5f,
+ *   s = the fetch at tm (always taken), s >= isoValue ? tb = tm : ta = tm; then t_hit = tb.  One rounded fp32
+ *   operation each.
+ *  Pixel: c = TF(isoValue), the transfer-function read of the ray caster; the surface is opaque, c.a is not used.
+ *   illumType 0: rgb = c.rgb.  illumType 1: g = the ray caster's negated central-difference gradient at the hit
+ *   position, ndl = max(0, g . lgt), spec = hvalid ? powr(max(g . hv, 0), 40) * 0.15 : 0 (lgt, hv, hvalid: the ray
+ *   caster's light and half vector), rgb = ((c * 0.15) + ((c * ndl) * 0.7)) + spec per channel, in this order.
+ *   a = 1.  A ray that misses the box or finds no hit: backgroundColor unchanged, alpha included.
+ *  Ignored: useGradient, contours, aerial.  VRHIP_ERR_UNSUPPORTED: illumType 2-5, imgEss, showEss, useAO,
+ *   iteration > 0, RG / RGBA volumes, a set environment map, vrhip_render_samples, vrhip_count_touched*,
+ *   vrhip_count_fetched.
+ *  vrhip_set_object_ess: on, march samples that provably lie below isoValue are not fetched (cell grid,
+ *   vrhip_download_cells); no pixel changes.  Needs neither ESS bricks nor the prefix sum.  vrhip_get_stats: zeros. */
+#define VRHIP_TECHNIQUE_ISO 4u
+
+typedef struct vrhip_iso_params {
+    float isoValue;
+    uint32_t refineSteps;
+    uint32_t reserved[2];
+} vrhip_iso_params; /* 16 bytes */
 
 typedef struct vrhip_raycast_params {
     float samplingRate;
@@ -216,6 +250,8 @@ int vrhip_set_camera_params(vrhip_renderer *r, const vrhip_camera_params *p);
 int vrhip_set_rendering_params(vrhip_renderer *r, const vrhip_rendering_params *p);
 int vrhip_set_raycast_params(vrhip_renderer *r, const vrhip_raycast_params *p);
 int vrhip_set_pathtrace_params(vrhip_renderer *r, const vrhip_pathtrace_params *p);
+/* technique 4 (VRHIP_TECHNIQUE_ISO above); stored as given, checked by the render calls */
+int vrhip_set_iso_params(vrhip_renderer *r, const vrhip_iso_params *p);
 /* setObjEss (volumerendercl.cpp:1006-1019): the reference recompiles with/without -DESS;
  * here it selects the kernel variant. Default on (:150). */
 int vrhip_set_object_ess(vrhip_renderer *r, int enabled);
@@ -368,9 +404,9 @@ int vrhip_assemble_batch_rgba8(vrhip_renderer *r, void *hip_stream, const uint32
  * tile_ids == NULL: whole frames, out_dev[n_frames][height][width][4]; else the tile subset like
  * vrhip_render_tiles, out_dev[n_frames][n_tiles][tile_h][tile_w][4]; out_frame_stride != 0 gives the
  * distance between the frames of out_dev in pixels (>= one frame).  DEVICE output only (the
- * renderer's own frame buffer is not meaningful afterwards).  Ray caster or maximum intensity
- * projection (technique 0 or 2), iteration 0, no image-order ESS, no ambient occlusion: anything else is
- * VRHIP_ERR_UNSUPPORTED. */
+ * renderer's own frame buffer is not meaningful afterwards).  Ray caster, maximum intensity
+ * projection or first-hit isosurface (technique 0, 2 or 4), iteration 0, no image-order ESS, no ambient
+ * occlusion: anything else is VRHIP_ERR_UNSUPPORTED. */
 int vrhip_render_batch(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t tile_w,
                        uint32_t tile_h, const uint32_t *tile_ids, uint32_t n_tiles,
                        const uint32_t *seeds, uint32_t n_frames, float *out_dev,
@@ -399,7 +435,7 @@ int vrhip_render_batch_views(vrhip_renderer *r, uint32_t width, uint32_t height,
  * out_rgba[n_tiles][tile_h][tile_w][4].  out_rgba may be NULL (the image stays in the frame buffer), host memory or
  * (out_is_device) device memory.  vrhip_get_stats: the sums over all samples; vrhip_last_kernel_seconds and
  * vrhip_last_launch_info: the last set, its fold included (with phase timing on, phase 2 is the fold).
- * Technique 0 or 2: VRHIP_ERR_UNSUPPORTED.  n_samples == 0 or seeds == NULL: VRHIP_ERR_INVALID. */
+ * Technique 0, 2 or 4: VRHIP_ERR_UNSUPPORTED.  n_samples == 0 or seeds == NULL: VRHIP_ERR_INVALID. */
 int vrhip_render_samples(vrhip_renderer *r, uint32_t width, uint32_t height,
                          uint32_t tile_w, uint32_t tile_h, const uint32_t *tile_ids, uint32_t n_tiles,
                          const uint32_t *seeds, uint32_t n_samples, uint32_t samples_per_launch /* 0 = default */,
@@ -425,8 +461,9 @@ int vrhip_set_frame_timing(vrhip_renderer *r, int enabled);
  * are the ones that ran -- e.g. that the timed frames of the benchmark and the frames compared with the
  * oracle came out of the same kernels. */
 typedef struct vrhip_launch_info {
-    uint32_t technique;      /* 0 ray caster, 1 path tracer, 2 maximum intensity projection (then only  */
-                             /* frames, work_items, empty_skip and views are filled, the rest is 0)     */
+    uint32_t technique;      /* 0 ray caster, 1 path tracer, 2 maximum intensity projection, 4 first-   */
+                             /* hit isosurface (2 and 4: only frames, work_items, empty_skip and views  */
+                             /* are filled, the rest is 0)                                              */
     uint32_t frames;         /* frames of the launch set (vrhip_render_batch), else 1                   */
     uint32_t work_items;     /* 8x8 patches in the work queue, all frames                               */
     uint32_t prepass;        /* 1: vr_dda_prepass_kernel ran                                            */
@@ -437,6 +474,7 @@ typedef struct vrhip_launch_info {
     uint32_t footprint;      /* 1: the kernels read the footprint volume                                */
     uint32_t empty_skip;     /* 1: the empty-run lookahead is on (cell grid handed to the kernels);     */
                              /* technique 2: samples below the running maximum are skipped by that grid */
+                             /* technique 4: march samples below isoValue are                           */
     uint32_t skip_in_lds;    /* 1: the ESS skip bitmap is staged in LDS (phase 1)                       */
     uint32_t instrumented;   /* 0 production kernels, 1 work counters, 2 / 3 + touched bitmap           */
     uint32_t extras;         /* 1: the variants with the rarer modes (illumType 2-5, AO, contours, ...) */

@@ -13,8 +13,10 @@ LIB_PATH = os.environ.get("VRHIP_LIB_PATH") or os.path.join(_HERE, "libvrhip.so"
 
 OK, ERR_INVALID, ERR_HIP, ERR_NODATA, ERR_UNSUPPORTED = range(5)
 UCHAR, USHORT, FLOAT = 0, 1, 2
-# rendering_params.technique: ray caster, path tracer, maximum intensity projection (VRHIP_TECHNIQUE_MIP)
+# rendering_params.technique: ray caster, path tracer, maximum intensity projection (VRHIP_TECHNIQUE_MIP), first-hit
+# isosurface (VRHIP_TECHNIQUE_ISO; 3 is unassigned)
 TECH_RAYCAST, TECH_PATHTRACE, TECH_MIP = 0, 1, 2
+TECH_ISO = 4
 
 
 class CameraParams(C.Structure):
@@ -42,6 +44,11 @@ class PathtraceParams(C.Structure):
     _fields_ = [("max_extinction", C.c_float)]
 
 
+class IsoParams(C.Structure):
+    """vrhip_iso_params: the parameters of technique 4 (no reference counterpart)."""
+    _fields_ = [("isoValue", C.c_float), ("refineSteps", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class Stats(C.Structure):
     _fields_ = [("samples_taken", C.c_uint64), ("samples_nominal", C.c_uint64),
                 ("samples_shaded", C.c_uint64), ("bricks_visited", C.c_uint64),
@@ -64,7 +71,7 @@ class LaunchInfo(C.Structure):
 
 assert C.sizeof(LaunchInfo) == 128
 assert C.sizeof(CameraParams) == 128 and C.sizeof(RenderingParams) == 64
-assert C.sizeof(RaycastParams) == 32 and C.sizeof(PathtraceParams) == 4
+assert C.sizeof(RaycastParams) == 32 and C.sizeof(PathtraceParams) == 4 and C.sizeof(IsoParams) == 16
 
 _H = C.c_void_p
 _U3 = C.POINTER(C.c_uint32)
@@ -132,6 +139,7 @@ SYMBOLS = {
     "vrhip_set_rendering_params": (C.c_int, [_H, C.POINTER(RenderingParams)]),
     "vrhip_set_raycast_params": (C.c_int, [_H, C.POINTER(RaycastParams)]),
     "vrhip_set_pathtrace_params": (C.c_int, [_H, C.POINTER(PathtraceParams)]),
+    "vrhip_set_iso_params": (C.c_int, [_H, C.POINTER(IsoParams)]),
     "vrhip_set_object_ess": (C.c_int, [_H, C.c_int]),
     "vrhip_render_frame": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int]),
     "vrhip_render_tiles": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

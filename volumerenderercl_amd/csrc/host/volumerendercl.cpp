@@ -27,6 +27,7 @@ VolumeRenderCL::VolumeRenderCL() : _modelScale{1.0f, 1.0f, 1.0f}
     _raycast_params.samplingRate = 1.5f;
     for (int i = 0; i < 3; ++i) _raycast_params.brickRes[i] = 1.f;
     _pathtrace_params.max_extinction = 100.f;
+    _iso_params = vrhip_iso_params{0.5f, 4u, {0u, 0u}};
 }
 
 VolumeRenderCL::~VolumeRenderCL()
@@ -133,6 +134,7 @@ void VolumeRenderCL::pushParams()
     check("setRenderingArgs", vrhip_set_rendering_params(_r, &_rendering_params));
     check("setRaycastArgs", vrhip_set_raycast_params(_r, &_raycast_params));
     check("setPathtraceArgs", vrhip_set_pathtrace_params(_r, &_pathtrace_params));
+    check("setIsoArgs", vrhip_set_iso_params(_r, &_iso_params));
 }
 
 void VolumeRenderCL::beginFrame()   // setMemObjectsRaycast (:194-218): fresh seed per frame
@@ -349,16 +351,26 @@ void VolumeRenderCL::setBackground(std::array<float, 4> color)   // :1025-1030
 }
 
 // A frame was rendered: the accumulating techniques move on to the next iteration; a maximum intensity
-// projection does not accumulate, every frame of it is iteration 0 (the library rejects anything else).
+// projection or an isosurface does not accumulate, every frame of it is iteration 0 (the library rejects anything else).
 void VolumeRenderCL::advanceIteration()
 {
-    if (_rendering_params.technique != TECH_MIP) _rendering_params.iteration++;
+    if (_rendering_params.technique != TECH_MIP && _rendering_params.technique != TECH_ISO) _rendering_params.iteration++;
 }
 
 void VolumeRenderCL::setTechnique(technique tech)   // :1042-1047
 {
     _rendering_params.technique = static_cast<uint>(tech);
     _rendering_params.iteration = 0;
+}
+
+void VolumeRenderCL::setIsoValue(float isoValue)
+{
+    _iso_params.isoValue = isoValue;
+}
+
+void VolumeRenderCL::setIsoRefinement(unsigned int refineSteps)
+{
+    _iso_params.refineSteps = refineSteps;
 }
 
 void VolumeRenderCL::setExtinction(const double extinction)
@@ -472,6 +484,7 @@ std::unique_ptr<VolumeRenderCL> VolumeRenderCL::shareVolumes()
     twin->_rendering_params = _rendering_params;
     twin->_raycast_params = _raycast_params;
     twin->_pathtrace_params = _pathtrace_params;
+    twin->_iso_params = _iso_params;
     twin->_seedPinned = _seedPinned;
     twin->_pinnedSeed = _pinnedSeed;
     twin->_volLoaded = true;

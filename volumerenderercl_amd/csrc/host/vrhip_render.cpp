@@ -412,6 +412,14 @@ void write_rgba8(const std::string &out, const std::vector<unsigned char> &frame
         "                                           one frame, --independent, --frames-per-launch, --camera-path / --orbit;\n"
         "                                           combines with --rgba8; not with --pathtrace, --ao, --show-ess, --img-ess,\n"
         "                                           --env)\n"
+        "         [--iso V [--iso-refine N]]       (technique 4, first-hit isosurface at V -- in the units of the transfer\n"
+        "                                           function's coordinate: normalised for UCHAR / USHORT, raw for FLOAT --\n"
+        "                                           coloured TF(V), shaded with --illum 1 (the default) or flat with\n"
+        "                                           --illum 0; N bisection rounds refine the hit, 0-16, default 4\n"
+        "                                           (--iso-refine needs --iso);\n"
+        "                                           independent frames like --mip; combines with --orbit, --camera-path,\n"
+        "                                           --frames-per-launch, --rgba8 and --ranks; not with --pathtrace, --mip,\n"
+        "                                           --ao, --show-ess, --img-ess, --env)\n"
         "         [--samples-per-launch K]         (--pathtrace: the N samples in launch sets of K -- vrhip_render_samples,\n"
         "                                           the same image bit for bit; 0 = the library's default set size, the\n"
         "                                           default; 1 = one launch per sample, as before; with --bench: one\n"
@@ -464,7 +472,10 @@ int main(int argc, char **argv)
     size_t W = 1024, H = 1024;
     double q[4] = {1, 0, 0, 0}, tr[3] = {0, 0, 2};
     bool have_view = false, ess = true, ortho = false, linear = true, gradient_bg = false, pin = false;
-    bool pathtrace = false, mip = false, device_ingest = false;
+    bool pathtrace = false, mip = false, iso = false, device_ingest = false;
+    double iso_value = 0.5;
+    int iso_refine = 4;
+    bool have_iso_refine = false;
     double extinction = 100.0;
     int downsample = 0;
     std::string state_file, tf_stops, tf_easing = "linear", dump_tf;
@@ -510,6 +521,8 @@ int main(int argc, char **argv)
         else if (a == "--frames") { need(i, 1); frames = std::atoi(argv[++i]); }
         else if (a == "--pathtrace") pathtrace = true;
         else if (a == "--mip") mip = true;
+        else if (a == "--iso") { need(i, 1); iso = true; iso_value = std::atof(argv[++i]); }
+        else if (a == "--iso-refine") { need(i, 1); have_iso_refine = true; iso_refine = std::atoi(argv[++i]); }
         else if (a == "--device-ingest") device_ingest = true;
         else if (a == "--downsample") { need(i, 1); downsample = std::atoi(argv[++i]); }
         else if (a == "--state") { need(i, 1); state_file = argv[++i]; }
@@ -549,6 +562,8 @@ int main(int argc, char **argv)
     }
     if (have_path_arg && (camera_path.empty() || have_orbit)) usage();
     if (mip && pathtrace) usage();
+    if (iso && (pathtrace || mip || use_ao_flag || show_ess_flag || img_ess || !env_file.empty())) usage();
+    if (have_iso_refine && (!iso || iso_refine < 0 || iso_refine > 16)) usage();
     if (rgba8 && ranks > 0) {
         std::cerr << "--rgba8 cannot be combined with --ranks: the C++ tile gather carries float pixels "
                      "(8-bit frames over several GPUs: the Python TileDriver, pixel_format=\"rgba8\")" << std::endl;
@@ -673,6 +688,11 @@ int main(int argc, char **argv)
             vr.setExtinction(extinction);
         }
         if (mip) vr.setTechnique(VolumeRenderCL::TECH_MIP);
+        if (iso) {
+            vr.setTechnique(VolumeRenderCL::TECH_ISO);
+            vr.setIsoValue(float(iso_value));
+            vr.setIsoRefinement(unsigned(iso_refine));
+        }
         if (pin) vr.setSeed(seed);
         vr.updateOutputImg(W, H, 0);
         vr.updateView(have_view ? view : view_matrix(q, tr));

@@ -268,6 +268,7 @@ struct RaycastLaunch {
     vrhip_rendering_params render;
     vrhip_raycast_params raycast;
     vrhip_pathtrace_params pathtrace;
+    vrhip_iso_params iso;
     CellView cells;
     int format;            // vrhip_format
     int use_ess;
@@ -297,7 +298,7 @@ struct RaycastLaunch {
     uint32_t sample_plane;
     float4 *fold_out;
     int keep_stats;            // launch_timed: the counters go on from the set before (chained sets of samples)
-    // technique 2 with object-order ESS: the (min, max) pairs of the cell grid of the current time step -- the fine grid
+    // technique 2 or 4 with object-order ESS: the (min, max) pairs of the cell grid of the current time step -- the fine grid
     // (cells.ecx.., cells.eshift) when cell_minmax_fine is set, else the coarse one (cells.cx.., cells.shift) -- or
     // nullptr: every sample is fetched
     const float2 *cell_minmax;
@@ -315,7 +316,7 @@ inline void vr_launch_kernel(F k, dim3 grid, dim3 block, size_t lds, hipStream_t
         hipLaunchKernelGGL(k, grid, block, lds, stream, args...);
 }
 
-// A technique that is one launch plus an optional last launch (MIP; the path tracer and its fold): first(start, stop)
+// A technique that is one launch plus an optional last launch (MIP, the isosurface; the path tracer and its fold): first(start, stop)
 // and last(stop) launch with the events to bind, or nullptr.  The frame's start rides on the first launch and its end
 // on the last one there is; the event between the two (RaycastLaunch::mid_event) is recorded.
 template <typename First, typename Last>
@@ -389,12 +390,15 @@ hipError_t vr_launch_cell_leap_radius(const CellView &grid, const float *cbound,
                                       hipStream_t stream);
 // technique 2 (maximum intensity projection): one launch, one wave per 8x8 patch of every frame; vr_mip.hip
 hipError_t vr_launch_mip(const RaycastLaunch &a, hipStream_t stream);
+// technique 4 (first-hit isosurface): one launch of the same shape; vr_iso.hip
+hipError_t vr_launch_iso(const RaycastLaunch &a, hipStream_t stream);
 // the frame launch for a.render.technique
 inline hipError_t vr_launch_frame(const RaycastLaunch &a, hipStream_t stream)
 {
-    return a.render.technique == VRHIP_TECHNIQUE_MIP ? vr_launch_mip(a, stream)
-           : a.render.technique == 1               ? vr_launch_pathtrace(a, stream)
-                                                   : vr_launch_raycast(a, stream);
+    return a.render.technique == VRHIP_TECHNIQUE_ISO   ? vr_launch_iso(a, stream)
+           : a.render.technique == VRHIP_TECHNIQUE_MIP ? vr_launch_mip(a, stream)
+           : a.render.technique == 1                   ? vr_launch_pathtrace(a, stream)
+                                                       : vr_launch_raycast(a, stream);
 }
 
 // skip bitmap from bricks + TF + prefix

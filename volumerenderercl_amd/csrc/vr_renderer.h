@@ -145,6 +145,7 @@ struct vrhip_renderer {
     vrhip_rendering_params render;
     vrhip_raycast_params raycast;
     vrhip_pathtrace_params pathtrace;
+    vrhip_iso_params iso;
     bool use_ess = true;
 
     DevBuf<float4> fb;
@@ -236,6 +237,9 @@ struct vrhip_renderer {
         raycast.samplingRate = 1.5f;
         for (int i = 0; i < 3; ++i) raycast.brickRes[i] = 1.f;
         pathtrace.max_extinction = 100.f;
+        iso.isoValue = 0.5f;
+        iso.refineSteps = 4;
+        iso.reserved[0] = iso.reserved[1] = 0;
     }
 };
 
@@ -396,8 +400,8 @@ int prepare_slot(vrhip_renderer *r, const uint32_t res[3], int format, uint32_t 
 //     skip_version)                                  |                     | sum, current step
 //   cell (min,max) of a slot, coarse and fine        | ensure_cells        | that slot's voxels
 //     (pt_minmax_valid, fine_minmax_valid)           |                     |
-//     (read as they are by technique 2, which       |                     |
-//     derives nothing of its own from them)          |                     |
+//     (read as they are by techniques 2 and 4, which|                     |
+//     derive nothing of their own from them)         |                     |
 //   opacity bounds / macro bounds / leap radii,      | ensure_cells        | cell (min,max) of the current step, TF,
 //     empty bits (cells_have_bound / _empty)         |                     | current step
 //   footprint volume (fp_valid, fp_timestep;         | ensure_footprint    | voxels of the current step, current step

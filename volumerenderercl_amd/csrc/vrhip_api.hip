@@ -117,9 +117,11 @@ bool ray_skip_empty(const vrhip_renderer *r)
     return std::max(r->brick_edge[0], std::max(r->brick_edge[1], r->brick_edge[2])) >= (4u << eshift);
 }
 
-// Technique 2 steps over samples that cannot raise the running maximum when object-order ESS is on
-// (VRHIP_NO_EMPTY_SKIP=1 disables this like the ray caster's empty runs).
+// Technique 2 steps over samples that cannot raise the running maximum when object-order ESS is on, technique 4
+// over march samples that cannot reach isoValue (VRHIP_NO_EMPTY_SKIP=1 disables this like the ray caster's empty runs).
 bool mip_skips(const vrhip_renderer *r) { return r->use_ess && r->skip_empty; }
+// the techniques that are one launch over the cells' (min, max): maximum intensity projection, first-hit isosurface
+bool minmax_technique(uint32_t t) { return t == VRHIP_TECHNIQUE_MIP || t == VRHIP_TECHNIQUE_ISO; }
 
 // The (min, max) pairs of a cell grid of the current time step as ensure_cells left them: the renderer's own, or
 // -- for a renderer that shares another one's voxels -- the owner's.  nullptr: not built.
@@ -218,7 +220,8 @@ int check_renderable(vrhip_renderer *r, uint32_t width, uint32_t height)
         VR_REQUIRE(r, r->prefix && r->prefix_n, VRHIP_ERR_NODATA,
                    "No transfer function prefix sum set.");
     }
-    VR_REQUIRE(r, r->render.technique <= VRHIP_TECHNIQUE_MIP, VRHIP_ERR_INVALID, "Unknown rendering technique.");
+    VR_REQUIRE(r, r->render.technique <= VRHIP_TECHNIQUE_MIP || r->render.technique == VRHIP_TECHNIQUE_ISO, VRHIP_ERR_INVALID,
+               "Unknown rendering technique.");   // (3 is unassigned)
     // the path-tracing branch of the kernel returns before illumType is looked at (:686-706); technique 2 ignores it
     VR_REQUIRE(r, r->render.illumType <= 5 || r->render.technique != 0, VRHIP_ERR_INVALID,
                "Unknown illumination type.");
@@ -236,6 +239,20 @@ int check_renderable(vrhip_renderer *r, uint32_t width, uint32_t height)
                    "maximum intensity projection: RG / RGBA volumes are not supported.");
         VR_REQUIRE(r, !r->env, VRHIP_ERR_UNSUPPORTED,
                    "maximum intensity projection: environment maps are not supported.");
+    }
+    if (r->render.technique == VRHIP_TECHNIQUE_ISO) {   // what the first-hit isosurface does not define
+        const vrhip_rendering_params &rp = r->render;
+        VR_REQUIRE(r, std::isfinite(r->iso.isoValue), VRHIP_ERR_INVALID, "isosurface: isoValue must be finite.");
+        VR_REQUIRE(r, r->iso.refineSteps <= 16u, VRHIP_ERR_INVALID, "isosurface: refineSteps must be at most 16.");
+        VR_REQUIRE(r, rp.illumType <= 1, VRHIP_ERR_UNSUPPORTED,
+                   "isosurface: illumType 0 (flat) and 1 (central differences) only.");
+        VR_REQUIRE(r, !rp.imgEss && !rp.showEss, VRHIP_ERR_UNSUPPORTED,
+                   "isosurface: image-order ESS and showEss are not supported.");
+        VR_REQUIRE(r, !r->raycast.useAO, VRHIP_ERR_UNSUPPORTED, "isosurface: ambient occlusion is not supported.");
+        VR_REQUIRE(r, rp.iteration == 0, VRHIP_ERR_UNSUPPORTED,
+                   "isosurface: frames do not accumulate (iteration must be 0).");
+        VR_REQUIRE(r, r->channels == 1, VRHIP_ERR_UNSUPPORTED, "isosurface: RG / RGBA volumes are not supported.");
+        VR_REQUIRE(r, !r->env, VRHIP_ERR_UNSUPPORTED, "isosurface: environment maps are not supported.");
     }
     // technique 1 and the traffic / downsampling helpers read channel 0 only, like the kernel's
     // .x readers; nothing else to check for CL_RG / CL_RGBA volumes
@@ -593,11 +610,12 @@ void fill_launch(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t ou
     a->render = r->render;
     a->raycast = r->raycast;
     a->pathtrace = r->pathtrace;
+    a->iso = r->iso;
     a->cells = r->cells;
     if (!r->pt_cull) { a->cells.bound = a->cells.cbound = nullptr; a->cells.cdist = nullptr; }
     // the empty bits are those of TF(channel 0): not what a CL_RG / CL_RGBA sample's opacity is
     if (!ray_skip_empty(r)) a->cells.empty = nullptr;
-    if (r->render.technique == VRHIP_TECHNIQUE_MIP) {
+    if (minmax_technique(r->render.technique)) {
         // (the kernel reads no table made from the transfer function: only the cells' (min, max) and their geometry)
         a->cells.bound = a->cells.cbound = nullptr;
         a->cells.cdist = nullptr;
@@ -749,8 +767,8 @@ int prepare_render(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t 
         rc = ensure_footprint(r);
         if (rc) return rc;
     }
-    if (r->render.technique == 1 ? r->pt_cull : r->render.technique == VRHIP_TECHNIQUE_MIP ? mip_skips(r) : ray_skip_empty(r)) {
-        // (technique 2 reads the (min, max) of the grid the empty bits live on: built with them)
+    if (r->render.technique == 1 ? r->pt_cull : minmax_technique(r->render.technique) ? mip_skips(r) : ray_skip_empty(r)) {
+        // (techniques 2 and 4 read the (min, max) of the grid the empty bits live on: built with them)
         rc = ensure_cells(r, r->render.technique == 1, r->render.technique != 1);
         if (rc) return rc;
     }
@@ -766,6 +784,8 @@ int count_touched_impl(vrhip_renderer *r, uint32_t width, uint32_t height, uint3
     if (set_device(r)) return VRHIP_ERR_HIP;
     VR_REQUIRE(r, r->render.technique != VRHIP_TECHNIQUE_MIP, VRHIP_ERR_UNSUPPORTED,
                "vrhip_count_touched / vrhip_count_fetched: not supported with maximum intensity projection.");
+    VR_REQUIRE(r, r->render.technique != VRHIP_TECHNIQUE_ISO, VRHIP_ERR_UNSUPPORTED,
+               "vrhip_count_touched / vrhip_count_fetched: not supported with isosurface rendering.");
     int rc = prepare_render(r, width, height, tile_w, tile_h, tile_ids, n_tiles);
     if (rc) return rc;
     const size_t mb = (size_t)((r->res[0] + 3) / 4) * ((r->res[1] + 3) / 4) * ((r->res[2] + 3) / 4);
@@ -1364,6 +1384,13 @@ int vrhip_set_pathtrace_params(vrhip_renderer *r, const vrhip_pathtrace_params *
     return VRHIP_OK;
 }
 
+int vrhip_set_iso_params(vrhip_renderer *r, const vrhip_iso_params *p)
+{
+    if (!r || !p) return VRHIP_ERR_INVALID;
+    r->iso = *p;   // (checked at render time, and only when technique 4 is selected: check_renderable)
+    return VRHIP_OK;
+}
+
 int vrhip_set_object_ess(vrhip_renderer *r, int enabled)
 {
     if (!r) return VRHIP_ERR_INVALID;
@@ -1433,10 +1460,10 @@ int vrhip_render_batch_views(vrhip_renderer *r, uint32_t width, uint32_t height,
     // the frames of a batch are independent: nothing that chains frames, nothing that draws from
     // rendering_params.seed outside the ray set-up
     const vrhip_rendering_params &rp = r->render;
-    VR_REQUIRE(r, (rp.technique == 0 || rp.technique == VRHIP_TECHNIQUE_MIP) && rp.iteration == 0 && !rp.imgEss &&
+    VR_REQUIRE(r, (rp.technique == 0 || minmax_technique(rp.technique)) && rp.iteration == 0 && !rp.imgEss &&
                       !r->raycast.useAO,
                VRHIP_ERR_UNSUPPORTED,
-               "vrhip_render_batch: technique 0 or 2 only, iteration 0, no image-order ESS, no ambient occlusion");
+               "vrhip_render_batch: technique 0, 2 or 4 only, iteration 0, no image-order ESS, no ambient occlusion");
     const uint32_t packed = tile_ids ? n_tiles * tile_w * tile_h : width * height;
     VR_REQUIRE(r, out_frame_stride == 0 || out_frame_stride >= packed, VRHIP_ERR_INVALID,
                "vrhip_render_batch: frame stride smaller than a frame");

@@ -11,8 +11,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, frontend
-from ._lib import (CameraParams, PathtraceParams, RaycastParams, RenderingParams, Stats,
-                   UCHAR, USHORT, FLOAT, TECH_MIP)
+from ._lib import (CameraParams, IsoParams, PathtraceParams, RaycastParams, RenderingParams, Stats,
+                   UCHAR, USHORT, FLOAT, TECH_MIP, TECH_ISO)
 
 NP_DTYPE = {UCHAR: np.uint8, USHORT: np.uint16, FLOAT: np.float32}
 _MT19937_DEFAULT_SEED = 5489   # std::mt19937 default constructor
@@ -44,6 +44,7 @@ class VolumeRenderCL:
         self._raycast.samplingRate = 1.5
         self._raycast.brickRes[:] = [1, 1, 1, 0]
         self._pathtrace = PathtraceParams(100.0)
+        self._iso = IsoParams(0.5, 4)
         self._timestep = 0
         self._res = [0, 0, 0, 1]
         self._thickness = [1.0, 1.0, 1.0]
@@ -70,6 +71,7 @@ class VolumeRenderCL:
         self._check(self._lib.vrhip_set_rendering_params(self._h, C.byref(self._rendering)))
         self._check(self._lib.vrhip_set_raycast_params(self._h, C.byref(self._raycast)))
         self._check(self._lib.vrhip_set_pathtrace_params(self._h, C.byref(self._pathtrace)))
+        self._check(self._lib.vrhip_set_iso_params(self._h, C.byref(self._iso)))
 
     @property
     def handle(self):
@@ -118,7 +120,7 @@ class VolumeRenderCL:
         twin._model_scale = self._model_scale.copy()
         twin._timestep = self._timestep
         twin._props = getattr(self, "_props", None)
-        for name in ("_camera", "_rendering", "_raycast", "_pathtrace"):
+        for name in ("_camera", "_rendering", "_raycast", "_pathtrace", "_iso"):
             C.memmove(C.byref(getattr(twin, name)), C.byref(getattr(self, name)),
                       C.sizeof(getattr(self, name)))
         twin._fixed_seed = self._fixed_seed
@@ -220,8 +222,8 @@ class VolumeRenderCL:
         self._push_params()
 
     def _advance_iteration(self):
-        # a maximum intensity projection does not accumulate: every frame of it is iteration 0
-        if self._rendering.technique != TECH_MIP:
+        # a maximum intensity projection or an isosurface does not accumulate: every frame of it is iteration 0
+        if self._rendering.technique not in (TECH_MIP, TECH_ISO):
             self._rendering.iteration += 1
 
     def runRaycast(self, width, height, out_dev_ptr=None):
@@ -703,12 +705,23 @@ class VolumeRenderCL:
         self._rendering.useGradient = 1 if v else 0
 
     def setTechnique(self, tech):
-        """TECH_RAYCAST (0), TECH_PATHTRACE (1) or TECH_MIP (2, maximum intensity projection: include/vrhip.h)."""
+        """TECH_RAYCAST (0), TECH_PATHTRACE (1), TECH_MIP (2, maximum intensity projection) or TECH_ISO (4, first-hit
+        isosurface: setIsoValue, setIsoRefinement); include/vrhip.h."""
         self._rendering.technique = int(tech)
         self._rendering.iteration = 0
 
     def setExtinction(self, extinction):
         self._pathtrace.max_extinction = float(extinction)
+
+    def setIsoValue(self, value):
+        """TECH_ISO: the threshold, in the units of the transfer function's coordinate (normalised for UCHAR / USHORT
+        volumes, the raw value for FLOAT).  Default 0.5."""
+        self._iso.isoValue = float(value)
+
+    def setIsoRefinement(self, steps):
+        """TECH_ISO: bisection rounds between the last sample below and the first at or above the threshold (0-16).
+        Default 4."""
+        self._iso.refineSteps = int(steps)
 
     def setBBox(self, bl_x, bl_y, bl_z, tr_x, tr_y, tr_z):
         self._camera.bbox_bl[:] = [bl_x, bl_y, bl_z, 0]
@@ -804,3 +817,7 @@ class VolumeRenderCL:
         self._rendering.modelScale[:] = [float(self._model_scale[0]), float(self._model_scale[1]),
                                          float(self._model_scale[2]), 0.0]
         return self._camera, self._rendering, self._raycast, self._pathtrace
+
+    def isoParams(self):
+        """The IsoParams of TECH_ISO as they will be pushed (setIsoValue, setIsoRefinement)."""
+        return self._iso
