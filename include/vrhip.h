@@ -482,7 +482,9 @@ typedef struct vrhip_launch_info {
     uint32_t sorted_phase2;  /* 1: suspended rays were counting-sorted, longest first                   */
     uint32_t views;          /* 1: per-frame cameras (vrhip_render_batch_views with cams != NULL)       */
     uint32_t samples;        /* 1: the sample variant of the path tracer and its fold (vrhip_render_samples) */
-    uint32_t reserved[15];
+    uint32_t reserved[14];
+    uint32_t pixel_major;    /* 1: phase 1 drew the set's rays pixel by pixel across its frames (vr_regroup_kernel  */
+                             /* ran: vrhip_render_batch sets of >= 2 frames), 0: in the pre-pass's order            */
 } vrhip_launch_info;
 /* VRHIP_ERR_NODATA before the first render call. */
 int vrhip_last_launch_info(const vrhip_renderer *r, vrhip_launch_info *out);

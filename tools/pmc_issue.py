@@ -16,7 +16,7 @@ import re
 import sys
 from collections import defaultdict
 
-PASS = ("vr_dda_prepass_kernel", "vr_raycast_rays_kernel", "vr_raycast_kernel", "vr_raycast_split_kernel",
+PASS = ("vr_dda_prepass_kernel", "vr_regroup_kernel", "vr_raycast_rays_kernel", "vr_raycast_kernel", "vr_raycast_split_kernel",
         "vr_cont_hist_kernel", "vr_cont_scatter_kernel", "vr_pathtrace_kernel")
 
 

@@ -63,7 +63,7 @@ class LaunchInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in (
         "technique", "frames", "work_items", "prepass", "ray_list", "phase1_waves", "phase2_waves", "round_budget",
         "footprint", "empty_skip", "skip_in_lds", "instrumented", "extras", "patch_classes", "sorted_phase2",
-        "views", "samples")] + [("reserved", C.c_uint32 * 15)]
+        "views", "samples")] + [("reserved", C.c_uint32 * 14), ("pixel_major", C.c_uint32)]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}

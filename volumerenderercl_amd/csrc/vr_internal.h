@@ -174,7 +174,9 @@ struct FrameView {
     // with SAMPLES = true -- vr_pathtrace.hip: one byte per record of `out`, 1 = traced sample, 0 = the ray missed
     // the box.  Same size, same offsets.)
     uint8_t *sample_mark;
-    uint32_t arg_pad[2];
+    // (The other two hold the pixel-major block of a launch set of one camera, or nullptr: the pre-pass's ray order.
+    // See "pixel-major ray order" below.  Same size, same offsets.)
+    uint32_t *pm;
     // Phase-2 scheduling: `cost` keeps, per pixel, the phase-2 rounds the pixel's ray needed in the
     // previous frame.  Suspended rays are sorted by it, longest first (counting sort into
     // `order`), so that the longest chains start first and the 16 rays of a group are alike.
@@ -207,8 +209,30 @@ constexpr uint32_t kLiveBase = 4 + 2 * kSortBins;        // first list counter, 
 // position; a wave starts at counter (its number mod kDrawCounters) and moves on when one has run out.
 constexpr uint32_t kDrawCounters = 8;
 constexpr uint32_t kDrawBase = kLiveBase + kLiveLists * kLiveStride;
-constexpr uint32_t kControlWords = kDrawBase + kDrawCounters * kLiveStride;   // queue head, cont count, cont head, live-tile count, sort_ws, list counters, draw counters
+// Pixel-major ray order (FrameView::pm; launch sets of >= 2 frames with one camera).  The frames of such a set differ in
+// the jitter seed only: the rays of one pixel in the set's frames cross the same cells, leave their empty runs and end
+// within a round of each other.  Phase 1 therefore draws the set's rays pixel by pixel -- the live rays of a pixel in
+// frames 0 .. set_frames - 1, then the next pixel of the same patch, patches in the queue's order -- through an INDEX
+// into the pre-pass's ray lists.  The pre-pass appends its records as ever and notes, per work item q, the ballot of
+// its live rays and the position of its first record; vr_regroup_kernel (one wave per patch, vr_raycast.hip) turns the
+// set_frames notes of a patch into index entries, appended to list (patch % kLiveLists) through kLiveLists counters
+// of their own in the control words.  A patch's entries are padded to a multiple of the group size with kPmNone, so
+// that the 64 rays a wave draws at once come from one patch.  The block, in words:
+//   [0, 2 n)   live ballots of the n work items       [2 n, 3 n)   position of the item's first record in live_rays
+//   [3 n, ..)  kLiveLists index lists of pm_list_cap(n, set_frames) entries each
+constexpr uint32_t kPmBase = kDrawBase + kDrawCounters * kLiveStride;          // first index-list counter, in control words
+constexpr uint32_t kControlWords = kPmBase + kLiveLists * kLiveStride;   // queue head, cont count, cont head, live-tile count, sort_ws, list counters, draw counters, index-list counters
+constexpr uint32_t kPmNone = 0xffffffffu;
 __host__ __device__ inline uint32_t live_list_cap(uint32_t n_items) { return ((n_items + kLiveLists - 1u) / kLiveLists) * 64u; }
+// entries per index list: ceil(patches / kLiveLists) patches of at most 64 set_frames entries (a multiple of every
+// group size) -- bounded without a division by (n_items + 7 set_frames) 8 <= 8 n_items + 64 set_frames
+__host__ __device__ inline uint32_t pm_list_cap(uint32_t n_items, uint32_t set_frames) { return 8u * n_items + 64u * set_frames; }
+// the whole block, in 64 bits: the host uses the order only where this fits 32 bits (the kernels index with 32 bits,
+// and pm_list_cap itself would wrap beyond)
+inline unsigned long long pm_block_words(uint32_t n_items, uint32_t set_frames)
+{
+    return 3ull * n_items + (unsigned long long)kLiveLists * (8ull * n_items + 64ull * set_frames);
+}
 // first kernel of a set of launches, first workgroup: the control words of the next set (FrameView::next_ctrl)
 #define VR_ZERO_NEXT_CTRL(fr)                                                                              \
     do {                                                                                                   \
@@ -275,6 +299,7 @@ struct RaycastLaunch {
     int instr;             // 0 none, 1 stats, 2 stats + touched bitmap
     int occ3;              // phase 1 on the ray list at three waves per SIMD (vr_raycast_kernels.h kWavesWide): a schedule, not a result
     int occ3_split;        // the same for phase 2
+    uint32_t pm_group;     // pixel-major order (frame.pm): a patch's index entries are padded to a multiple of this (1, 32 or 64)
     DevStats *stats;
     uint32_t *touched;
     int num_cus;

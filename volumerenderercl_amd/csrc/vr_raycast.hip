@@ -1,6 +1,6 @@
 // vr_raycast.hip -- the ray caster's launch entry (vr_launch_raycast: the format switch over the units
 // vr_raycast_int.hip and vr_raycast_f32.hip, whose kernels live in vr_raycast_kernels.h) and the kernels that do
-// not depend on the voxel type: patch classes, the phase-2 counting sort, the image-order ESS resolve, the skip
+// not depend on the voxel type: patch classes, the pixel-major index, the phase-2 counting sort, the image-order ESS resolve, the skip
 // bitmaps.
 #include "vr_raycast_kernels.h"
 
@@ -80,6 +80,51 @@ __global__ __launch_bounds__(kBlockDim) void vr_patch_class_kernel(SkipView skip
     bool clear = false;
     if (inside && all_hit && skip.near_bits) clear = patch_is_clear(skip, grid, c, lane);
     if (lane == 0) cls[pi] = clear ? 1 : 0;
+}
+
+// ------------------------------------------------------------------ pixel-major ray order
+
+// The index of a launch set's rays in pixel-major order (vr_internal.h "pixel-major ray order"): one wave per patch of
+// the set, behind the pre-pass.  The patch's set_frames notes (live ballot, first record) become one run of index
+// entries -- pixel 0 in frames 0 .. set_frames - 1, pixel 1, ... -- appended as a whole to index list (patch %
+// kLiveLists) and padded with kPmNone to a multiple of `group` (a power of two that divides 64).  A patch that is
+// dead in every frame leaves at once.  The (pixel, frame) pairs are walked 64 at a time, so the writes are contiguous.
+__global__ __launch_bounds__(kBlockDim) void vr_regroup_kernel(FrameView fr, uint32_t group)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t n = fr.n_wave_tiles, sf = fr.set_frames;
+    const uint32_t p = blockIdx.x * (kBlockDim / 64) + (threadIdx.x >> 6);
+    if (p >= n / sf) return;
+    const uint32_t *notes = fr.pm + 2u * (size_t)p * sf;
+    const uint32_t *first = fr.pm + 2u * (size_t)n + (size_t)p * sf;
+    uint32_t total = 0;
+    for (uint32_t f0 = 0; f0 < sf; f0 += 64u) {
+        const uint32_t f = f0 + lane;
+        const uint32_t c = f < sf ? (uint32_t)(__builtin_popcount(notes[2u * f]) + __builtin_popcount(notes[2u * f + 1u])) : 0u;
+        total += (uint32_t)wave_sum((unsigned long long)c);
+    }
+    total = __builtin_amdgcn_readfirstlane(total);
+    if (!total) return;
+    const uint32_t padded = (total + group - 1u) & ~(group - 1u);   // <= 64 sf: within pm_list_cap for every patch of the list
+    const uint32_t list = p % kLiveLists;
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(fr.live_list_count + (kPmBase - kLiveBase) + list * kLiveStride, padded);
+    base = __builtin_amdgcn_readfirstlane(base);
+    uint32_t *out = fr.pm + 3u * (size_t)n + (size_t)list * pm_list_cap(n, sf) + base;
+    // pair i = pixel * sf + frame, i = 64 step + lane: both advance by 64 per step without a division in the loop
+    const uint32_t dq = 64u / sf, dr = 64u % sf;
+    uint32_t px = lane / sf, f = lane % sf, pos = 0;
+    for (uint32_t step = 0; step < sf; ++step) {
+        const unsigned long long m = (unsigned long long)notes[2u * f] | ((unsigned long long)notes[2u * f + 1u] << 32);
+        const bool live = (m >> px) & 1ull;
+        const unsigned long long b = __ballot(live);
+        if (live) out[pos + VR_LANE_RANK(b)] = first[f] + (uint32_t)__builtin_popcountll(m & ((1ull << px) - 1ull));
+        pos += (uint32_t)__builtin_popcountll(b);
+        px += dq;
+        f += dr;
+        if (f >= sf) { f -= sf; ++px; }
+    }
+    for (uint32_t i = total + lane; i < padded; i += 64u) out[i] = kPmNone;
 }
 
 // ------------------------------------------------------------------ phase-2 ordering
@@ -293,6 +338,15 @@ hipError_t vr_launch_skipmap(const BrickView &bricks, int format, float inv_max,
         break;
     default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+hipError_t vr_launch_regroup(const FrameView &frame, uint32_t group, hipStream_t stream)
+{
+    if (!frame.pm || !frame.set_frames || (group != 1u && group != 32u && group != 64u)) return hipErrorInvalidValue;
+    const uint32_t n_patches = frame.n_wave_tiles / frame.set_frames;
+    if (!n_patches) return hipSuccess;
+    hipLaunchKernelGGL(vr_regroup_kernel, dim3((n_patches + kBlockDim / 64 - 1u) / (kBlockDim / 64)), dim3(kBlockDim), 0, stream, frame, group);
     return hipGetLastError();
 }
 

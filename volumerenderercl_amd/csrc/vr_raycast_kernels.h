@@ -48,6 +48,8 @@ hipError_t vr_launch_raycast_u16(const RaycastLaunch &a, hipStream_t stream);
 hipError_t vr_launch_raycast_f32(const RaycastLaunch &a, hipStream_t stream);
 // between the phases: the counting sort of the suspended rays (FrameView::order); vr_raycast.hip
 hipError_t vr_launch_cont_sort(const FrameView &frame, hipStream_t stream);
+// between the pre-pass and phase 1, pixel-major order only (FrameView::pm): the index into the ray lists; vr_raycast.hip
+hipError_t vr_launch_regroup(const FrameView &frame, uint32_t group, hipStream_t stream);
 #if defined(VR_MARCH_STATS) || defined(VR_STAMPS)
 // Diagnostic builds: every unit has its own copy of the arrays its kernels write (g_march_stats, g_stamps,
 // g_wave_span).  A unit's reader ADDS its copy of array `which` to sum[0, n) and clears the copy on request; the
@@ -159,6 +161,17 @@ struct RayDyn {   // marching state
         base = atomicAdd(COUNTER, (uint32_t)__builtin_popcountll(MASK));       \
     base = __shfl(base, __builtin_ctzll(MASK), 64)
 #define VR_LANE_RANK(MASK) ((uint32_t)__builtin_popcountll(MASK & ((1ull << lane) - 1ull)))
+// Pixel-major order: the pre-pass's note for work item q -- the ballot of its live rays and the position of the first of
+// their records in live_rays (vr_internal.h; vr_regroup_kernel reads them).  Every wave of the pre-pass leaves one,
+// whichever way it ends: nothing else initialises the block.
+#define VR_PM_NOTE(fr, q, MASK, FIRST)                                      \
+    do {                                                                    \
+        if ((fr).pm && lane == 0) {                                         \
+            (fr).pm[2u * (q)] = (uint32_t)(MASK);                           \
+            (fr).pm[2u * (q) + 1u] = (uint32_t)((MASK) >> 32);              \
+            (fr).pm[2u * (fr).n_wave_tiles + (q)] = (FIRST);                \
+        }                                                                   \
+    } while (0)
 
 struct Grid {     // wave-uniform brick-grid constants
     int bw, bh, bd;
@@ -1186,6 +1199,7 @@ __global__ __launch_bounds__(kBlockDim) void vr_dda_prepass_kernel(
         const float4 o = make_float4(rp.backgroundColor[0], rp.backgroundColor[1], rp.backgroundColor[2], 0.f);
         fr.fb[(size_t)gy * fr.W + gx] = o;
         if (fr.out) fr.out[out_index] = o;
+        VR_PM_NOTE(fr, q, 0ull, 0u);
         return;
     }
     const uint32_t seed = fr.seeds ? fr.seeds[wt_frame(wt)] : rp.seed;
@@ -1200,11 +1214,15 @@ __global__ __launch_bounds__(kBlockDim) void vr_dda_prepass_kernel(
     } else {
         setup_ray_head<false>(gx, gy, inside, fr, cam, rp, c, d, seed, rnd);   // (nothing is shaded here)
     }
-    if (rp.imgEss && image_ess_patch(fr, rp, c, wt, lane, inside, gx, gy, out_index)) return;
+    if (rp.imgEss && image_ess_patch(fr, rp, c, wt, lane, inside, gx, gy, out_index)) {
+        VR_PM_NOTE(fr, q, 0ull, 0u);
+        return;
+    }
     if (skip.near_bits && patch_is_clear(skip, grid, c, lane)) {
         // no ray of this patch can meet a brick that is not skipped: what the walk would leave
         // (step size and DDA set-up are not needed for that)
         if (inside) write_pixel<true>(fr, rp, c, d, voxLen, gx, gy, out_index);
+        VR_PM_NOTE(fr, q, 0ull, 0u);
         return;
     }
     setup_ray_tail<true>(rc, resf, voxLen, grid, c, d, rnd);
@@ -1240,10 +1258,13 @@ __global__ __launch_bounds__(kBlockDim) void vr_dda_prepass_kernel(
             const uint32_t list = q % kLiveLists;
             VR_WAVE_APPEND(base, fr.live_list_count + list * kLiveStride, m);
             base += list * live_list_cap(fr.n_wave_tiles);
+            VR_PM_NOTE(fr, q, m, base);
             if (live) {
                 VR_PACK_RAY(r, (uint32_t)out_index, wt_frame(wt), 0);
                 fr.live_rays[base + VR_LANE_RANK(m)] = r;
             }
+        } else {
+            VR_PM_NOTE(fr, q, 0ull, 0u);
         }
         return;
     }
@@ -1281,11 +1302,16 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_rays_kernel(
     // The pre-pass (previous kernel on the stream) has written kLiveLists lists; they are read interleaved, 64 rays from
     // each in turn: virtual ray v is ray (v / 64 / kLiveLists) * 64 + v % 64 of list (v / 64) % kLiveLists, and there are
     // kLiveLists * 64 * ceil(longest list / 64) virtual rays (those beyond a list's end do not exist: idle lanes).
+    // Pixel-major order (fr.pm, never with VIEWS): the same walk over the kLiveLists INDEX lists that vr_regroup_kernel
+    // has written behind the pre-pass -- their counters sit kPmBase - kLiveBase control words behind the ray lists' --,
+    // and a refill reads the index entry, then the record it names.
+    const bool pm_order = !VIEWS && fr.pm != nullptr;
+    const uint32_t *const list_count = fr.live_list_count + (pm_order ? kPmBase - kLiveBase : 0u);
     __shared__ uint32_t s_live_n[kLiveLists];
     uint32_t longest = 0;
 #pragma unroll
     for (uint32_t k = 0; k < kLiveLists; ++k) {
-        const uint32_t n_k = fr.live_list_count[k * kLiveStride];
+        const uint32_t n_k = list_count[k * kLiveStride];
         longest = n_k > longest ? n_k : longest;
         if (threadIdx.x == k) s_live_n[k] = n_k;
     }
@@ -1344,8 +1370,13 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_rays_kernel(
                         const uint32_t chunk = v >> 6, list = chunk % kLiveLists;
                         const uint32_t pos = ((chunk / kLiveLists) << 6) | (v & 63u);
                         have = v < n_rays && pos < s_live_n[list];
+                        uint32_t at = list * list_cap + pos;
+                        if (pm_order) {   // (entries that pad a patch's group name no ray)
+                            at = have ? fr.pm[3u * fr.n_wave_tiles + list * pm_list_cap(fr.n_wave_tiles, fr.set_frames) + pos] : kPmNone;
+                            have = at != kPmNone;
+                        }
                         if (have) {
-                            const ContRec rec = fr.live_rays[list * list_cap + pos];
+                            const ContRec rec = fr.live_rays[at];
                             // (per lane: the lanes of a wave may hold rays of different frames)
                             VR_UNPACK_RAY(rec, frame_idx,
                                 if constexpr (VIEWS) {
@@ -1870,6 +1901,8 @@ hipError_t launch_variant(const RaycastLaunch &a, hipStream_t stream)
     if (grid.x == 0) return hipSuccess;
     FrameView frame = a.frame;
     if (XS || INSTR != 0 || !ESS) frame.live_rays = nullptr;   // the ray list serves the default kernels
+    // ... and the pixel-major index is an index into that list, for the frames of one camera
+    if (VIEWS || !frame.live || !frame.live_rays || frame.set_frames < 2u || frame.n_wave_tiles % frame.set_frames) frame.pm = nullptr;
     if (a.info) {   // what this call launches, for vrhip_last_launch_info (completed below)
         vrhip_launch_info &li = *a.info;
         li.technique = 0;
@@ -1897,8 +1930,14 @@ hipError_t launch_variant(const RaycastLaunch &a, hipStream_t stream)
         if (start_ev) { *a.start_bound = true; start_ev = nullptr; }
         if (a.info) { a.info->prepass = 1; a.info->patch_classes = frame.patch_class ? 1u : 0u; }
         if (VIEWS && frame.patch_class) return hipErrorInvalidValue;   // (classes hold for one camera: the host turns them off)
+        if (frame.pm) {
+            pe = vr_launch_regroup(frame, a.pm_group, stream);
+            if (pe != hipSuccess) return pe;
+            if (a.info) a.info->pixel_major = 1;
+        }
     } else {
         frame.live = nullptr;
+        frame.pm = nullptr;
     }
     hipError_t e;
     const bool resolve_follows = a.render.imgEss && a.hit_out && a.frame.n_wave_tiles;

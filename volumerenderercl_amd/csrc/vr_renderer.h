@@ -176,6 +176,9 @@ struct vrhip_renderer {
     DevBuf<uint32_t> order;           // sorted permutation of the suspended rays
     DevBuf<ContRec> live_rays;        // pre-pass output: live rays with their DDA state (phase 1's list)
     bool ray_list = true;             // VRHIP_NO_RAYLIST=1: phase 1 walks the live patches instead
+    DevBuf<uint32_t> pm;              // FrameView::pm: the pixel-major block of a launch set (notes and index lists)
+    bool pixel_major = true;          // VRHIP_PIXEL_MAJOR=0: launch sets keep the pre-pass's ray order (A/B)
+    uint32_t pm_group = 64;           // VRHIP_PM_GROUP=1|32|64: a patch's index entries are padded to a multiple of it
     DevBuf<uint32_t> seeds_dev;       // kMaxBatchFrames jitter seeds of a batch of frames
     DevBuf<vrhip_camera_params> cams_dev;   // kMaxBatchFrames cameras of a batch of per-frame views
     DevBuf<> samples_dev;             // vrhip_render_samples: the records and marks of a set of samples (lazily, reused)

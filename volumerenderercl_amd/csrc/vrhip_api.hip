@@ -886,6 +886,11 @@ int vrhip_create(int device_id, vrhip_renderer **out)
         if (v >= 0 && v <= 64) r->cull_radius = (uint32_t)v;
     }
     if (getenv("VRHIP_NO_SORT")) r->sort_cont = false;         // experiments: phase 2 in append order
+    if (const char *e = getenv("VRHIP_PIXEL_MAJOR")) r->pixel_major = atoi(e) != 0;   // A/B: the ray order of launch sets
+    if (const char *e = getenv("VRHIP_PM_GROUP")) {
+        const int v = atoi(e);
+        if (v == 1 || v == 32 || v == 64) r->pm_group = (uint32_t)v;
+    }
     if (getenv("VRHIP_NO_PATCH_CLASS")) r->use_patch_classes = false;   // A/B: every patch sets up its rays
     auto occ_env = [](const char *name, int dflt) {
         const char *e = getenv(name);
@@ -1485,6 +1490,21 @@ int vrhip_render_batch_views(vrhip_renderer *r, uint32_t width, uint32_t height,
     a.frame.out = (float4 *)out_dev;
     a.frame.seeds = r->seeds_dev;
     a.frame.cams = cams ? r->cams_dev : nullptr;
+    // Pixel-major ray order (vr_internal.h): the frames of ONE camera differ in the jitter only, so the rays of a pixel
+    // march alike and phase 1 draws them side by side.  A camera per frame: the same pixel is not the same ray.
+    if (r->pixel_major && !cams && n_frames >= 2 && rp.technique == 0 && a.frame.live_rays) {
+        // The block is sized for the worst case, every ray of the set live: 268 bytes per work item (140 MB for 1024^2
+        // x 32 frames, beside the 2 GB of ray records that case needs).  It is optional: where it does not fit 32-bit
+        // indices or cannot be allocated, the set keeps the pre-pass's order and the launch info says so.
+        const unsigned long long words = pm_block_words(r->queue_n, n_frames);
+        if (words <= 0xffffffffull) {
+            if ((rc = grow(r, r->pm, (size_t)words * sizeof(uint32_t), kGrowTolerate))) return rc;
+            if (r->pm.p) {
+                a.frame.pm = r->pm;
+                a.pm_group = r->pm_group;
+            }
+        }
+    }
     return launch_timed(r, a);
 }
 
