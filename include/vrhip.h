@@ -494,6 +494,28 @@ int vrhip_last_launch_info(const vrhip_renderer *r, vrhip_launch_info *out);
  * the 4-lane kernel -- the key suspended rays are sorted by.  n = width * height.  For tools (tools/costmap.py). */
 int vrhip_download_cost_map(vrhip_renderer *r, uint16_t *out, size_t n);
 
+/* The pixel-major ray order of the launch set just rendered (no reference counterpart; a schedule, not a result):
+ * what the pre-pass noted, the ray records it appended and the index vr_regroup_kernel made of them, copied out
+ * as they lie in device memory.  VRHIP_ERR_NODATA unless the last render call on this renderer was a launch set
+ * whose launch info says pixel_major == 1.  Synchronises the renderer's stream; launches nothing and changes
+ * nothing.  For tests (tests/test_gpu_ray_order.py).
+ *   sizes        {set_frames, n = work items, group, live_list_cap(n), pm_list_cap(n, set_frames),
+ *                 R = records of the eight ray lists together, E = entries of the eight index lists together, 0};
+ *                R and E count at most a list's capacity per list (a counter beyond it is reported as it is in
+ *                out_counters, and the copy stops at the capacity)
+ *   out_items    3 n words: (patch column, patch row, frame) of every work item, in queue order
+ *   out_notes    3 n words as the pre-pass left them: the live ballot of item q at [2 q] (pixels 0-31 of the
+ *                patch, bit = 8 * row + column) and [2 q + 1] (pixels 32-63), the position of its first record
+ *                in the ray lists at [2 n + q]
+ *   out_counters 16 words: the eight ray-list counters, then the eight index-list counters
+ *   out_records  4 R words: (gx, gy, frame, position in the ray lists) of every record, list 0 first
+ *   out_index    E words: the entries of the index lists, list 0 first: a position in the ray lists, or
+ *                0xffffffff where an entry pads a patch's run to a multiple of the group
+ * Any output may be NULL; all NULL: sizes only.  A size that does not match is VRHIP_ERR_INVALID. */
+int vrhip_download_ray_order(vrhip_renderer *r, uint32_t sizes[8], uint32_t *out_items, size_t n_items,
+                             uint32_t *out_notes, size_t n_notes, uint32_t out_counters[16], uint32_t *out_records,
+                             size_t n_records, uint32_t *out_index, size_t n_index);
+
 /* ---- measurement helpers ------------------------------------------- */
 /* When enabled, render calls run the instrumented kernel variant that accumulates
  * vrhip_stats (one atomic per wave). */

@@ -123,6 +123,12 @@ struct ContRec {
     uint32_t pad;
 };
 
+// What a record says about its ray without the kernels' locals (VR_PACK_RAY / VR_UNPACK_RAY, vr_raycast_kernels.h, are
+// the code that packs and unpacks whole records): pixel and frame of the batch.  Host side, vrhip_download_ray_order.
+inline uint32_t rec_gx(const ContRec &c) { return c.pix & 0xffffu; }
+inline uint32_t rec_gy(const ContRec &c) { return c.pix >> 16; }
+inline uint32_t rec_frame(const ContRec &c) { return (uint32_t)c.state >> 8; }
+
 struct FrameView {
     uint32_t W, H;         // frame size in pixels
     uint32_t gsx, gsy;     // padded launch size the reference derives the camera from

@@ -179,6 +179,10 @@ struct vrhip_renderer {
     DevBuf<uint32_t> pm;              // FrameView::pm: the pixel-major block of a launch set (notes and index lists)
     bool pixel_major = true;          // VRHIP_PIXEL_MAJOR=0: launch sets keep the pre-pass's ray order (A/B)
     uint32_t pm_group = 64;           // VRHIP_PM_GROUP=1|32|64: a patch's index entries are padded to a multiple of it
+    // vrhip_download_ray_order: the last render call was a pixel-major set, of pm_last_frames frames, on control block
+    // pm_last_ctrl (queue, ray lists and block are as that set left them: prepare_render forgets it)
+    bool pm_last = false;
+    uint32_t pm_last_ctrl = 0, pm_last_frames = 0;
     DevBuf<uint32_t> seeds_dev;       // kMaxBatchFrames jitter seeds of a batch of frames
     DevBuf<vrhip_camera_params> cams_dev;   // kMaxBatchFrames cameras of a batch of per-frame views
     DevBuf<> samples_dev;             // vrhip_render_samples: the records and marks of a set of samples (lazily, reused)

@@ -745,6 +745,7 @@ int prepare_render(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t 
                    uint32_t tile_h, const uint32_t *tile_ids, uint32_t n_tiles, uint32_t n_frames = 1,
                    uint32_t frame_stride = 0)
 {
+    r->pm_last = false;   // (whatever renders next rebuilds or reuses the queue, the ray lists and a control block)
     int rc = check_renderable(r, width, height);
     if (rc) return rc;
     if (tile_ids) {
@@ -1505,7 +1506,14 @@ int vrhip_render_batch_views(vrhip_renderer *r, uint32_t width, uint32_t height,
             }
         }
     }
-    return launch_timed(r, a);
+    const uint32_t ctrl_used = r->ctrl_sel;
+    rc = launch_timed(r, a);
+    if (!rc && r->last_info.pixel_major) {   // vrhip_download_ray_order
+        r->pm_last = true;
+        r->pm_last_ctrl = ctrl_used;
+        r->pm_last_frames = n_frames;
+    }
+    return rc;
 }
 
 int vrhip_render_samples(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h,
@@ -1601,6 +1609,76 @@ int vrhip_download_cost_map(vrhip_renderer *r, uint16_t *out, size_t n)
                "vrhip_download_cost_map: no cost map of this size (render a frame first)");
     VR_HIP(r, hipStreamSynchronize(r->stream));
     VR_HIP(r, hipMemcpy(out, r->cost, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return VRHIP_OK;
+}
+
+int vrhip_download_ray_order(vrhip_renderer *r, uint32_t sizes[8], uint32_t *out_items, size_t n_items,
+                             uint32_t *out_notes, size_t n_notes, uint32_t out_counters[16], uint32_t *out_records,
+                             size_t n_records, uint32_t *out_index, size_t n_index)
+{
+    if (!r) return VRHIP_ERR_INVALID;
+    if (set_device(r)) return VRHIP_ERR_HIP;
+    VR_REQUIRE(r, r->pm_last && r->pm && r->live_rays && r->queue_dev && r->queue_head, VRHIP_ERR_NODATA,
+               "vrhip_download_ray_order: the last render call was not a launch set in pixel-major order");
+    const uint32_t n = r->queue_n, sf = r->pm_last_frames;
+    const uint32_t ray_cap = live_list_cap(n), idx_cap = pm_list_cap(n, sf);
+    VR_HIP(r, hipStreamSynchronize(r->stream));
+    // the control words of that set: the set after next clears them (FrameView::next_ctrl), nothing before
+    std::vector<uint32_t> ctrl(kControlWords);
+    VR_HIP(r, hipMemcpy(ctrl.data(), r->queue_head + (size_t)r->pm_last_ctrl * kControlWords, kControlWords * sizeof(uint32_t),
+                        hipMemcpyDeviceToHost));
+    uint32_t counters[2 * kLiveLists], take[2 * kLiveLists];
+    size_t n_rec = 0, n_ent = 0;
+    for (uint32_t k = 0; k < kLiveLists; ++k) {
+        counters[k] = ctrl[kLiveBase + k * kLiveStride];
+        counters[kLiveLists + k] = ctrl[kPmBase + k * kLiveStride];
+        take[k] = counters[k] < ray_cap ? counters[k] : ray_cap;
+        take[kLiveLists + k] = counters[kLiveLists + k] < idx_cap ? counters[kLiveLists + k] : idx_cap;
+        n_rec += take[k];
+        n_ent += take[kLiveLists + k];
+    }
+    if (sizes) {
+        const uint32_t s[8] = {sf, n, r->pm_group, ray_cap, idx_cap, (uint32_t)n_rec, (uint32_t)n_ent, 0u};
+        std::memcpy(sizes, s, sizeof s);
+    }
+    if (out_counters) std::memcpy(out_counters, counters, sizeof counters);
+    VR_REQUIRE(r, (!out_items || n_items == 3 * (size_t)n) && (!out_notes || n_notes == 3 * (size_t)n) &&
+                  (!out_records || n_records == 4 * n_rec) && (!out_index || n_index == n_ent),
+               VRHIP_ERR_INVALID, "vrhip_download_ray_order: size mismatch");
+    if (out_items) {
+        std::vector<WaveTile> q(n);
+        if (n) VR_HIP(r, hipMemcpy(q.data(), r->queue_dev, (size_t)n * sizeof(WaveTile), hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < n; ++i) {
+            out_items[3 * (size_t)i] = wt_col(q[i]);
+            out_items[3 * (size_t)i + 1] = wt_row(q[i]);
+            out_items[3 * (size_t)i + 2] = wt_frame(q[i]);
+        }
+    }
+    if (out_notes && n) VR_HIP(r, hipMemcpy(out_notes, r->pm, 3 * (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_records) {
+        std::vector<ContRec> recs;
+        for (uint32_t k = 0; k < kLiveLists; ++k) {
+            recs.resize(take[k]);
+            if (take[k])
+                VR_HIP(r, hipMemcpy(recs.data(), r->live_rays + (size_t)k * ray_cap, (size_t)take[k] * sizeof(ContRec),
+                                    hipMemcpyDeviceToHost));
+            for (uint32_t i = 0; i < take[k]; ++i) {
+                out_records[0] = rec_gx(recs[i]);
+                out_records[1] = rec_gy(recs[i]);
+                out_records[2] = rec_frame(recs[i]);
+                out_records[3] = k * ray_cap + i;
+                out_records += 4;
+            }
+        }
+    }
+    if (out_index)
+        for (uint32_t k = 0; k < kLiveLists; ++k) {
+            const uint32_t c = take[kLiveLists + k];
+            if (c)
+                VR_HIP(r, hipMemcpy(out_index, r->pm + 3 * (size_t)n + (size_t)k * idx_cap, (size_t)c * sizeof(uint32_t),
+                                    hipMemcpyDeviceToHost));
+            out_index += c;
+        }
     return VRHIP_OK;
 }
 

@@ -764,6 +764,35 @@ class VolumeRenderCL:
         self._check(self._lib.vrhip_last_launch_info(self._h, C.byref(li)))
         return li.as_dict()
 
+    def downloadRayOrder(self):
+        """The pixel-major ray order of the launch set just rendered (vrhip_download_ray_order; RuntimeError unless the
+        last render call was a set with lastLaunchInfo()["pixel_major"] == 1), as a dict: set_frames, n_items, group,
+        live_list_cap, pm_list_cap; items int64 [n, 3] (patch column, patch row, frame) in queue order; ballot uint64 [n]
+        (bit = 8 * row + column of the patch) and first int64 [n] (position of the item's first record), from notes
+        (the 3 n words as they are); ray_counts and index_counts (eight each); records, a list of eight int64
+        [count, 4] (gx, gy, frame, position in the ray lists); index, a list of eight uint32 arrays (0xffffffff pads)."""
+        fn = self._lib.vrhip_download_ray_order
+        sizes, counters = (C.c_uint32 * 8)(), (C.c_uint32 * 16)()
+        self._check(fn(self._h, sizes, None, 0, None, 0, counters, None, 0, None, 0))
+        sf, n, group, ray_cap, idx_cap, n_rec, n_ent = (int(v) for v in sizes[:7])
+        items = np.empty((n, 3), dtype=np.uint32)
+        notes = np.empty(3 * n, dtype=np.uint32)
+        recs = np.empty((n_rec, 4), dtype=np.uint32)
+        ents = np.empty(n_ent, dtype=np.uint32)
+        self._check(fn(self._h, sizes, items.ctypes.data_as(C.c_void_p), items.size, notes.ctypes.data_as(C.c_void_p),
+                       notes.size, counters, recs.ctypes.data_as(C.c_void_p), recs.size, ents.ctypes.data_as(C.c_void_p),
+                       ents.size))
+        ray_counts = [int(v) for v in counters[:8]]
+        index_counts = [int(v) for v in counters[8:]]
+        rcut = np.cumsum([0] + [min(c, ray_cap) for c in ray_counts])
+        icut = np.cumsum([0] + [min(c, idx_cap) for c in index_counts])
+        ballot = notes[0:2 * n:2].astype(np.uint64) | (notes[1:2 * n:2].astype(np.uint64) << np.uint64(32))
+        return {"set_frames": sf, "n_items": n, "group": group, "live_list_cap": ray_cap, "pm_list_cap": idx_cap,
+                "items": items.astype(np.int64), "notes": notes, "ballot": ballot, "first": notes[2 * n:].astype(np.int64),
+                "ray_counts": ray_counts, "index_counts": index_counts,
+                "records": [recs[rcut[k]:rcut[k + 1]].astype(np.int64) for k in range(8)],
+                "index": [ents[icut[k]:icut[k + 1]].copy() for k in range(8)]}
+
     # ---- test / bench conveniences (not in the reference)
     def setSeed(self, seed):
         """Pin the per-frame jitter seed (None restores the mt19937 sequence).  params() shows a pinned seed at
