@@ -150,6 +150,39 @@ public:
                            unsigned char *dev_out);
     void renderFramesRGBA8(size_t width, size_t height, const std::vector<unsigned int> &seeds,
                            const std::vector<std::array<float, 16>> &views, float *dev_frames, unsigned char *dev_out);
+    // ---- slice views (no reference counterpart; vrhip.h "slice views"): 2-D cuts through the voxels -- a plane, or a
+    // slab reduced by max / min / mean over parallel planes -- coloured by the transfer function or as the filtered
+    // value itself.  One launch for all slices of a call.  Reads the volume of the current time step, the transfer
+    // function, setLinearInterpolation and setBackground; camera, technique, iteration and seed are neither read nor
+    // touched, so progressive frames carry on around a slice bit for bit.
+    typedef vrhip_slice_params slice_params;
+    enum slice_mode { SLICE_MAX = VRHIP_SLICE_MAX, SLICE_MIN = VRHIP_SLICE_MIN, SLICE_MEAN = VRHIP_SLICE_MEAN };
+    enum slice_output { SLICE_TF = VRHIP_SLICE_TF, SLICE_VALUE = VRHIP_SLICE_VALUE };
+    // The full cross-section of the box [-1, 1]^3 perpendicular to axis 0 | 1 | 2 (x | y | z) at `position` along it;
+    // thickness (box units, along +axis, centred on position) and samples make it a slab.  Orientation: axis z: right
+    // = +x, up = +y; axis y: right = -x, up = +z; axis x: right = +y, up = +z -- each seen from the positive side of its
+    // axis, u x v = +axis.  The image spans the whole box whatever its size in pixels: the caller picks width : height
+    // from the model scale.
+    static slice_params axisSlice(int axis, float position, float thickness = 0.f, unsigned int samples = 1,
+                                  slice_mode mode = SLICE_MAX, slice_output output = SLICE_TF);
+    // An oblique plane through `origin` perpendicular to `normal`: v = halfHeight * the unit vector of `up` made
+    // orthogonal to the normal, u = halfWidth * (v^ x n^), w = thickness * n^ (computed in double, stored as float).
+    // Throws std::invalid_argument for a zero normal or an up vector parallel to it.
+    static slice_params planeSlice(const std::array<float, 3> &origin, const std::array<float, 3> &normal,
+                                   const std::array<float, 3> &up, float halfWidth, float halfHeight, float thickness = 0.f,
+                                   unsigned int samples = 1, slice_mode mode = SLICE_MAX, slice_output output = SLICE_TF);
+    // n parallel copies of `s` stepped along its normal (along w for a slab, else u x v) over `span` box units centred
+    // on s.origin: copy k at origin + ((k + 0.5) / n - 0.5) * span * normal
+    static std::vector<slice_params> sliceStack(const slice_params &s, unsigned int n, float span);
+    // `output` receives slices.size() images of width*height*4 floats, row 0 = top ...
+    void renderSlices(size_t width, size_t height, const std::vector<slice_params> &slices, std::vector<float> &output);
+    // ... or DEVICE memory dev_out[n][height][width][4] does (16-byte aligned); returns without waiting
+    void renderSlices(size_t width, size_t height, const std::vector<slice_params> &slices, float *dev_out);
+    // the device form with the images also as 8-bit pixels (vrhip_quantise_rgba8 on the same stream): the floats into
+    // DEVICE memory dev_frames[n][height][width][4], their bytes into out[n][height][width][4] -- device memory
+    // (returns without waiting), or host memory with outIsDevice = false (returns when the bytes have arrived)
+    void renderSlicesRGBA8(size_t width, size_t height, const std::vector<slice_params> &slices, float *dev_frames,
+                           unsigned char *out, bool outIsDevice = true);
     // ---- the progressive path tracer (technique 1), many samples per call (vrhip_render_samples): seeds.size()
     // consecutive iterations of the accumulated image -- sample k with jitter seed seeds[k] at iteration
     // (current iteration + k) -- in as few launch sets as possible, bit for bit what seeds.size() runRaycastNoGL calls

@@ -269,6 +269,48 @@ int vrhip_render_frame(vrhip_renderer *r, uint32_t width, uint32_t height, float
 int vrhip_render_tiles(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t tile_w,
                        uint32_t tile_h, const uint32_t *tile_ids, uint32_t n_tiles,
                        float *out_tiles_dev);
+/* ---- slice views: oblique planes and thick slabs through the voxels (no reference counterpart; DESIGN.md "Slice
+ * views").  An entry point of its own, not a technique: it casts no ray and reads no camera.
+ *  All arithmetic is fp32, every operation below rounded on its own, in the order written.
+ *  Pixel position: pixel (gx, gy) of a width x height image, row 0 at the top:
+ *   sx = (2.f * ((float)gx + 0.5f)) / (float)W - 1.f,  sy = 1.f - (2.f * ((float)gy + 0.5f)) / (float)H,
+ *   p = (origin + sx * u) + sy * v per component, in box space: the volume is [-1, 1]^3.
+ *  Samples: k = 0 .. N - 1: a_k = ((float)k + 0.5f) / (float)N - 0.5f, q_k = p + a_k * w, tex = q_k * 0.5f + 0.5f.
+ *   A sample is TAKEN when 0 <= tex <= 1 holds for all three components (a NaN fails).  Its value s_k is the
+ *   normalised, filtered channel-0 value at tex of the current time step, exactly what techniques 2 and 4 see
+ *   (useLinear: trilinear, clamp to edge; else nearest).
+ *  Reduction over the taken samples, in order of k: VRHIP_SLICE_MAX `s > m ? s : m` from -inf, VRHIP_SLICE_MIN
+ *   `s < m ? s : m` from +inf (a NaN never replaces either), VRHIP_SLICE_MEAN sum = sum + s from 0.f, then
+ *   sum / (float)count.  With N = 1 the three modes give the same bits.
+ *  Pixel: no sample taken: backgroundColor, all four components.  VRHIP_SLICE_TF: technique 2's pixel, c = TF(val),
+ *   rgb = c.rgb * c.a + bg.rgb * (1 - c.a), a = c.a + bg.a * (1 - c.a).  VRHIP_SLICE_VALUE: (val, val, val, 1), the
+ *   data readout; a NaN val is written as the quiet NaN 0x7fc00000 whatever its sign and payload (fp32 arithmetic
+ *   defines neither: a NaN pixel does not depend on how the hardware negates or hands on a NaN).
+ *  Output: slice i goes to out_rgba + i * W * H * 4: device memory when out_is_device != 0 (16-byte aligned; the
+ *   call returns without synchronising), else host memory through a staging buffer the renderer owns (the call
+ *   returns after the copy has completed).
+ *  State: reads the volume, the time step, the transfer function, useLinear and backgroundColor -- no camera,
+ *   technique, illumination, ESS switch, iteration, seed or environment map -- and writes nothing a render entry
+ *   point reads later: not the frame buffer, the hit images, the launch sets' control words or
+ *   vrhip_last_launch_info.  A slice between two progressive frames does not disturb them.
+ *  VRHIP_ERR_INVALID: n_slices == 0, NULL pointers, samples 0 or above VRHIP_SLICE_MAX_SAMPLES, mode > 2,
+ *   output > 1, reserved != 0, a non-finite component of origin, u, v or w, a width or height vrhip_render_frame
+ *   refuses, more than 2^32 - 1 patches of 8 x 8 pixels in all.  VRHIP_ERR_UNSUPPORTED: RG / RGBA volumes.
+ *   VRHIP_ERR_NODATA as from vrhip_render_frame: no volume; no transfer function while a slice has output TF. */
+#define VRHIP_SLICE_MAX_SAMPLES 256u
+enum { VRHIP_SLICE_MAX = 0, VRHIP_SLICE_MIN = 1, VRHIP_SLICE_MEAN = 2 };   /* mode   */
+enum { VRHIP_SLICE_TF = 0, VRHIP_SLICE_VALUE = 1 };                        /* output */
+typedef struct vrhip_slice_params {
+    float origin[4];   /* image centre in box space: the volume is [-1,1]^3 (texture coordinate = q*0.5+0.5); [3] unused */
+    float u[4];        /* image centre -> centre of the right edge  */
+    float v[4];        /* image centre -> centre of the top edge    */
+    float w[4];        /* slab: from its first to its last face, across the plane; all zero for a thin slice */
+    uint32_t samples;  /* N: 1 .. VRHIP_SLICE_MAX_SAMPLES */
+    uint32_t mode, output, reserved;   /* reserved must be 0 */
+} vrhip_slice_params;   /* 80 bytes */
+int vrhip_render_slices(vrhip_renderer *r, uint32_t width, uint32_t height, const vrhip_slice_params *slices,
+                        uint32_t n_slices, float *out_rgba, int out_is_device);
+
 /* createEnvironmentMap (volumerendercl.cpp:1121-1150): float RGBA texels, row-major, width*height*4
  * floats (the host layer decodes the Radiance .hdr file).  The kernel samples it in place of the
  * background colour when it is wider than one texel (volumeraycast.cl:506-510, :655-656);

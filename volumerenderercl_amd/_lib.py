@@ -49,6 +49,18 @@ class IsoParams(C.Structure):
     _fields_ = [("isoValue", C.c_float), ("refineSteps", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+# vrhip_slice_params.mode / .output (slice views, vrhip_render_slices)
+SLICE_MAX, SLICE_MIN, SLICE_MEAN = 0, 1, 2
+SLICE_TF, SLICE_VALUE = 0, 1
+SLICE_MAX_SAMPLES = 256
+
+
+class SliceParams(C.Structure):
+    """vrhip_slice_params: one slice view -- a plane or a slab through the box [-1, 1]^3 (no reference counterpart)."""
+    _fields_ = [("origin", C.c_float * 4), ("u", C.c_float * 4), ("v", C.c_float * 4), ("w", C.c_float * 4),
+                ("samples", C.c_uint32), ("mode", C.c_uint32), ("output", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Stats(C.Structure):
     _fields_ = [("samples_taken", C.c_uint64), ("samples_nominal", C.c_uint64),
                 ("samples_shaded", C.c_uint64), ("bricks_visited", C.c_uint64),
@@ -72,6 +84,7 @@ class LaunchInfo(C.Structure):
 assert C.sizeof(LaunchInfo) == 128
 assert C.sizeof(CameraParams) == 128 and C.sizeof(RenderingParams) == 64
 assert C.sizeof(RaycastParams) == 32 and C.sizeof(PathtraceParams) == 4 and C.sizeof(IsoParams) == 16
+assert C.sizeof(SliceParams) == 80
 
 _H = C.c_void_p
 _U3 = C.POINTER(C.c_uint32)
@@ -142,6 +155,7 @@ SYMBOLS = {
     "vrhip_set_iso_params": (C.c_int, [_H, C.POINTER(IsoParams)]),
     "vrhip_set_object_ess": (C.c_int, [_H, C.c_int]),
     "vrhip_render_frame": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int]),
+    "vrhip_render_slices": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int]),
     "vrhip_render_tiles": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_void_p, C.c_uint32, C.c_void_p]),
     "vrhip_set_environment_map": (C.c_int, [_H, C.c_void_p, C.c_uint32, C.c_uint32]),

@@ -4,6 +4,8 @@
 #include "hdrloader.h"
 #include "volumerendercl.h"
 
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <iostream>
 #include <numeric>
@@ -582,6 +584,113 @@ void VolumeRenderCL::renderFramesRGBA8(size_t width, size_t height, const std::v
     renderFrames(width, height, seeds, views, dev_frames);
     check("renderFramesRGBA8", vrhip_quantise_rgba8(_r, stream(), dev_frames, uint32_t(seeds.size()), uint32_t(width * height),
                                                     uint32_t(width * height), dev_out, 1));
+}
+
+// ---- slice views (vrhip_render_slices; the helpers compute in double and store floats, as frontend.py's do)
+
+namespace {
+
+VolumeRenderCL::slice_params make_slice(const double o[3], const double u[3], const double v[3], const double w[3],
+                                        unsigned int samples, unsigned int mode, unsigned int output)
+{
+    VolumeRenderCL::slice_params s;
+    std::memset(&s, 0, sizeof s);
+    for (int i = 0; i < 3; ++i) {
+        s.origin[i] = float(o[i]);
+        s.u[i] = float(u[i]);
+        s.v[i] = float(v[i]);
+        s.w[i] = float(w[i]);
+    }
+    s.samples = samples;
+    s.mode = mode;
+    s.output = output;
+    return s;
+}
+
+} // namespace
+
+VolumeRenderCL::slice_params VolumeRenderCL::axisSlice(int axis, float position, float thickness, unsigned int samples,
+                                                       slice_mode mode, slice_output output)
+{
+    if (axis < 0 || axis > 2) throw std::invalid_argument("axisSlice: the axis is 0, 1 or 2");
+    const int right = axis == 0 ? 1 : 0, up = axis == 2 ? 1 : 2;
+    double o[3] = {0, 0, 0}, u[3] = {0, 0, 0}, v[3] = {0, 0, 0}, w[3] = {0, 0, 0};
+    o[axis] = position;
+    u[right] = axis == 1 ? -1.0 : 1.0;   // (u x v = +axis for all three)
+    v[up] = 1.0;
+    w[axis] = thickness;
+    return make_slice(o, u, v, w, samples, mode, output);
+}
+
+VolumeRenderCL::slice_params VolumeRenderCL::planeSlice(const std::array<float, 3> &origin, const std::array<float, 3> &normal,
+                                                        const std::array<float, 3> &up, float halfWidth, float halfHeight,
+                                                        float thickness, unsigned int samples, slice_mode mode,
+                                                        slice_output output)
+{
+    double n[3] = {normal[0], normal[1], normal[2]}, upv[3] = {up[0], up[1], up[2]};
+    const double ln = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    if (!(ln > 0.0)) throw std::invalid_argument("planeSlice: the normal must not be zero");
+    for (double &c : n) c /= ln;
+    const double d = upv[0] * n[0] + upv[1] * n[1] + upv[2] * n[2];
+    double vv[3] = {upv[0] - n[0] * d, upv[1] - n[1] * d, upv[2] - n[2] * d};
+    const double lv = std::sqrt(vv[0] * vv[0] + vv[1] * vv[1] + vv[2] * vv[2]);
+    const double lu = std::sqrt(upv[0] * upv[0] + upv[1] * upv[1] + upv[2] * upv[2]);
+    if (!(lv > 1e-12 * std::max(1.0, lu))) throw std::invalid_argument("planeSlice: up must not be parallel to the normal");
+    for (double &c : vv) c /= lv;
+    const double uu[3] = {vv[1] * n[2] - vv[2] * n[1], vv[2] * n[0] - vv[0] * n[2], vv[0] * n[1] - vv[1] * n[0]};   // v^ x n^
+    double o[3], u[3], v[3], w[3];
+    for (int i = 0; i < 3; ++i) {
+        o[i] = origin[size_t(i)];
+        u[i] = uu[i] * double(halfWidth);
+        v[i] = vv[i] * double(halfHeight);
+        w[i] = n[i] * double(thickness);
+    }
+    return make_slice(o, u, v, w, samples, mode, output);
+}
+
+std::vector<VolumeRenderCL::slice_params> VolumeRenderCL::sliceStack(const slice_params &s, unsigned int n, float span)
+{
+    if (n < 1) throw std::invalid_argument("sliceStack: n >= 1");
+    double nrm[3] = {s.w[0], s.w[1], s.w[2]};
+    if (nrm[0] == 0.0 && nrm[1] == 0.0 && nrm[2] == 0.0) {
+        const double u[3] = {s.u[0], s.u[1], s.u[2]}, v[3] = {s.v[0], s.v[1], s.v[2]};
+        nrm[0] = u[1] * v[2] - u[2] * v[1];
+        nrm[1] = u[2] * v[0] - u[0] * v[2];
+        nrm[2] = u[0] * v[1] - u[1] * v[0];
+    }
+    const double l = std::sqrt(nrm[0] * nrm[0] + nrm[1] * nrm[1] + nrm[2] * nrm[2]);
+    if (!(l > 0.0)) throw std::invalid_argument("sliceStack: the slice has no normal (u x v and w are zero)");
+    std::vector<slice_params> out(n, s);
+    for (unsigned int k = 0; k < n; ++k)
+        for (int i = 0; i < 3; ++i)
+            out[k].origin[i] = float(double(s.origin[i]) + ((double(k) + 0.5) / double(n) - 0.5) * double(span) * (nrm[i] / l));
+    return out;
+}
+
+void VolumeRenderCL::renderSlices(size_t width, size_t height, const std::vector<slice_params> &slices,
+                                  std::vector<float> &output)
+{
+    if (!_volLoaded) throw std::runtime_error("No volume data is loaded.");
+    pushParams();
+    output.resize(slices.size() * width * height * 4);
+    check("renderSlices", vrhip_render_slices(_r, uint32_t(width), uint32_t(height), slices.data(), uint32_t(slices.size()),
+                                              output.data(), 0));
+}
+
+void VolumeRenderCL::renderSlices(size_t width, size_t height, const std::vector<slice_params> &slices, float *dev_out)
+{
+    if (!_volLoaded) throw std::runtime_error("No volume data is loaded.");
+    pushParams();
+    check("renderSlices", vrhip_render_slices(_r, uint32_t(width), uint32_t(height), slices.data(), uint32_t(slices.size()),
+                                              dev_out, 1));
+}
+
+void VolumeRenderCL::renderSlicesRGBA8(size_t width, size_t height, const std::vector<slice_params> &slices,
+                                       float *dev_frames, unsigned char *out, bool outIsDevice)
+{
+    renderSlices(width, height, slices, dev_frames);
+    check("renderSlicesRGBA8", vrhip_quantise_rgba8(_r, stream(), dev_frames, uint32_t(slices.size()), uint32_t(width * height),
+                                                    uint32_t(width * height), out, outIsDevice ? 1 : 0));
 }
 
 // ---- the progressive path tracer, many samples per call (vrhip_render_samples)

@@ -459,6 +459,19 @@ void write_rgba8(const std::string &out, const std::vector<unsigned char> &frame
         "         [--rgba8]                        (also the frame as 8-bit RGBA, the reference's display format, quantised\n"
         "                                           on the GPU: PREFIX.rgba.u8 (W*H*4 bytes), with several frames\n"
         "                                           PREFIX.frames.rgba.u8, and PREFIX.ppm from those bytes; not with --ranks)\n"
+        "         [--slice-axis X|Y|Z POS | --slice OX OY OZ UX UY UZ VX VY VZ]\n"
+        "         [--slab T N max|min|mean] [--slice-stack N] [--slice-value]\n"
+        "                                          (slice views instead of a rendered frame: the full cross-section of the\n"
+        "                                           box [-1,1]^3 perpendicular to an axis at POS (Z: right +x, up +y; Y: right\n"
+        "                                           -x, up +z; X: right +y, up +z), or the plane with centre O, O + U the\n"
+        "                                           centre of the right edge and O + V of the top edge; --slab: max, min or\n"
+        "                                           mean of N (1-256) parallel planes over thickness T along the normal;\n"
+        "                                           --slice-stack: N such slices spanning the box along the normal, one\n"
+        "                                           launch; --slice-value: the filtered value in r, g, b instead of the\n"
+        "                                           transfer function's colour; uses --size, --tf, --bg, --nearest; the\n"
+        "                                           slices go to PREFIX.frames.rgba.f32, the last to PREFIX.rgba.f32, with\n"
+        "                                           --rgba8 also as bytes; not with --mip, --iso, --pathtrace, --orbit,\n"
+        "                                           --camera-path, --ranks)\n"
         "writes PREFIX.rgba.f32 (W*H*4 float32, row 0 = top), PREFIX.ppm and prints one JSON line\n";
     std::exit(2);
 }
@@ -494,6 +507,11 @@ int main(int argc, char **argv)
     bool have_path_arg = false, have_orbit = false;
     double orbit_axis[3] = {0, 1, 0};
     int orbit_n = 0;
+    // slice views (--slice-axis / --slice, --slab, --slice-stack, --slice-value)
+    bool have_slice_axis = false, have_slice_plane = false, have_slab = false, have_stack = false, slice_value = false;
+    int slice_axis = 2, slab_n = 1, stack_n = 0;
+    double slice_pos = 0.0, slice_vec[9] = {0, 0, 0, 1, 0, 0, 0, 1, 0}, slab_t = 0.0;
+    std::string slab_mode = "max";
 
     auto need = [&](int i, int n) { if (i + n >= argc) usage(); };
     for (int i = 1; i < argc; ++i) {
@@ -557,6 +575,17 @@ int main(int argc, char **argv)
             orbit_n = std::atoi(argv[++i]);
             have_orbit = true;
         }
+        else if (a == "--slice-axis") {
+            need(i, 2);
+            const std::string ax = argv[++i];
+            slice_axis = ax == "X" || ax == "x" ? 0 : ax == "Y" || ax == "y" ? 1 : ax == "Z" || ax == "z" ? 2 : -1;
+            slice_pos = std::atof(argv[++i]);
+            have_slice_axis = true;
+        }
+        else if (a == "--slice") { need(i, 9); for (int k = 0; k < 9; ++k) slice_vec[k] = std::atof(argv[++i]); have_slice_plane = true; }
+        else if (a == "--slab") { need(i, 3); slab_t = std::atof(argv[++i]); slab_n = std::atoi(argv[++i]); slab_mode = argv[++i]; have_slab = true; }
+        else if (a == "--slice-stack") { need(i, 1); stack_n = std::atoi(argv[++i]); have_stack = true; }
+        else if (a == "--slice-value") slice_value = true;
         else if (a == "--dump-views") { need(i, 1); dump_views = argv[++i]; }
         else usage();
     }
@@ -568,6 +597,23 @@ int main(int argc, char **argv)
         std::cerr << "--rgba8 cannot be combined with --ranks: the C++ tile gather carries float pixels "
                      "(8-bit frames over several GPUs: the Python TileDriver, pixel_format=\"rgba8\")" << std::endl;
         return 2;
+    }
+    const bool slicing = have_slice_axis || have_slice_plane;
+    if ((have_slab || have_stack || slice_value) && !slicing) usage();
+    if (slicing) {
+        if (have_slice_axis && have_slice_plane) usage();
+        if (mip || iso || pathtrace || have_orbit || have_path_arg || ranks > 0) usage();
+        if (have_slice_axis && (slice_axis < 0 || !std::isfinite(slice_pos))) usage();
+        for (double c : slice_vec) if (!std::isfinite(c)) usage();
+        if (have_slab && (slab_n < 1 || slab_n > int(VRHIP_SLICE_MAX_SAMPLES) || !std::isfinite(slab_t) ||
+                          (slab_mode != "max" && slab_mode != "min" && slab_mode != "mean")))
+            usage();
+        if (have_stack && (stack_n < 1 || stack_n > 1 << 16)) usage();
+        if (have_slice_plane && (have_slab || have_stack)) {   // these need the plane's normal
+            const double *u = slice_vec + 3, *v = slice_vec + 6;
+            const double n[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
+            if (n[0] * n[0] + n[1] * n[1] + n[2] * n[2] == 0.0) usage();
+        }
     }
     if (have_orbit && (orbit_n < 1 || orbit_n > 1 << 20 ||
                        orbit_axis[0] * orbit_axis[0] + orbit_axis[1] * orbit_axis[1] + orbit_axis[2] * orbit_axis[2] == 0.0))
@@ -851,6 +897,78 @@ int main(int argc, char **argv)
         std::vector<float> frame, all_frames;
         std::vector<unsigned char> frame8, all_frames8;   // --rgba8
         double kernel_s = 0.0;
+        if (slicing) {
+            // ---- slice views (VolumeRenderCL::renderSlices): the slices of the options in calls of <= 64, written like
+            // the frames of --orbit
+            const VolumeRenderCL::slice_mode mode = slab_mode == "min" ? VolumeRenderCL::SLICE_MIN
+                                                    : slab_mode == "mean" ? VolumeRenderCL::SLICE_MEAN : VolumeRenderCL::SLICE_MAX;
+            const VolumeRenderCL::slice_output output = slice_value ? VolumeRenderCL::SLICE_VALUE : VolumeRenderCL::SLICE_TF;
+            VolumeRenderCL::slice_params sp;
+            double nrm[3] = {0, 0, 0};   // the unit normal
+            if (have_slice_axis) {
+                sp = VolumeRenderCL::axisSlice(slice_axis, float(slice_pos), float(slab_t), unsigned(slab_n), mode, output);
+                nrm[slice_axis] = 1.0;
+            } else {
+                std::memset(&sp, 0, sizeof sp);
+                const double *u = slice_vec + 3, *v = slice_vec + 6;
+                const double c[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
+                const double l = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+                for (int k = 0; k < 3; ++k) {
+                    nrm[k] = l > 0.0 ? c[k] / l : 0.0;
+                    sp.origin[k] = float(slice_vec[k]);
+                    sp.u[k] = float(u[k]);
+                    sp.v[k] = float(v[k]);
+                    sp.w[k] = float(slab_t * nrm[k]);
+                }
+                sp.samples = unsigned(slab_n);
+                sp.mode = unsigned(mode);
+                sp.output = unsigned(output);
+            }
+            std::vector<VolumeRenderCL::slice_params> slices{sp};
+            if (have_stack) {
+                // spanning the box along the normal: centred where the normal's line through the box centre meets the
+                // plane's parallel through it, over the box's extent along the normal
+                const double d = sp.origin[0] * nrm[0] + sp.origin[1] * nrm[1] + sp.origin[2] * nrm[2];
+                VolumeRenderCL::slice_params base = sp;
+                for (int k = 0; k < 3; ++k) base.origin[k] = float(double(sp.origin[k]) - d * nrm[k]);
+                const double span = 2.0 * (std::fabs(nrm[0]) + std::fabs(nrm[1]) + std::fabs(nrm[2]));
+                slices = VolumeRenderCL::sliceStack(base, unsigned(stack_n), float(span));
+            }
+            auto hip_ok = [](hipError_t e, const char *what) {
+                if (e != hipSuccess) throw std::runtime_error(std::string("ERROR: ") + what + " (" + hipGetErrorString(e) + ")");
+            };
+            hip_ok(hipSetDevice(device), "hipSetDevice");
+            const size_t chunk = std::min<size_t>(64, slices.size()), px = W * H * 4;
+            float *dev = nullptr;
+            hip_ok(hipMalloc(reinterpret_cast<void **>(&dev), chunk * px * sizeof(float)), "hipMalloc slices");
+            all_frames.resize(slices.size() * px);
+            if (rgba8) all_frames8.resize(slices.size() * px);
+            for (size_t at = 0; at < slices.size(); at += chunk) {
+                const size_t n = std::min(chunk, slices.size() - at);
+                const std::vector<VolumeRenderCL::slice_params> part(slices.begin() + long(at), slices.begin() + long(at + n));
+                if (rgba8) vr.renderSlicesRGBA8(W, H, part, dev, all_frames8.data() + at * px, false);
+                else vr.renderSlices(W, H, part, dev);
+                hip_ok(hipStreamSynchronize(static_cast<hipStream_t>(vr.stream())), "hipStreamSynchronize");
+                hip_ok(hipMemcpy(all_frames.data() + at * px, dev, n * px * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy");
+            }
+            (void)hipFree(dev);
+            frame.assign(all_frames.end() - long(px), all_frames.end());
+            std::ofstream af(out + ".frames.rgba.f32", std::ios::binary);
+            af.write(reinterpret_cast<const char *>(all_frames.data()), std::streamsize(all_frames.size() * sizeof(float)));
+            std::ofstream raw(out + ".rgba.f32", std::ios::binary);
+            raw.write(reinterpret_cast<const char *>(frame.data()), std::streamsize(frame.size() * sizeof(float)));
+            write_ppm(out + ".ppm", frame, W, H);
+            if (rgba8) {
+                frame8.assign(all_frames8.end() - long(px), all_frames8.end());
+                write_rgba8(out, frame8, all_frames8, W, H);
+            }
+            auto res = vr.getResolution();
+            std::printf("{\"device\": \"%s\", \"volume\": [%u, %u, %u], \"width\": %zu, \"height\": %zu, \"slices\": %zu, "
+                        "\"samples\": %d, \"mode\": \"%s\", \"output\": \"%s\", \"out\": \"%s.rgba.f32\"}\n",
+                        vr.getCurrentDeviceName().c_str(), res[0], res[1], res[2], W, H, slices.size(), slab_n,
+                        slab_mode.c_str(), slice_value ? "value" : "tf", out.c_str());
+            return 0;
+        }
         if (frames_per_launch > 0) {
             // ---- the throughput path on one GPU: F renderers over one shared volume take launch sets of <= K
             // independent frames in turn (what bench.py times; volumerenderwidget.cpp:464-486 is the one-frame-per-

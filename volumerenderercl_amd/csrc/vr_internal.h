@@ -423,6 +423,11 @@ hipError_t vr_launch_cell_leap_radius(const CellView &grid, const float *cbound,
 hipError_t vr_launch_mip(const RaycastLaunch &a, hipStream_t stream);
 // technique 4 (first-hit isosurface): one launch of the same shape; vr_iso.hip
 hipError_t vr_launch_iso(const RaycastLaunch &a, hipStream_t stream);
+// slice views (vrhip_render_slices): n_slices images of W x H pixels, one wave per 8x8 patch of every slice, into
+// out_dev[n_slices][H][W]; slices_dev: the n_slices parameter blocks in device memory; vr_slice.hip
+hipError_t vr_launch_slices(const VolView &vol, int format, const TfView &tf, const vrhip_slice_params *slices_dev,
+                            uint32_t n_slices, uint32_t W, uint32_t H, uint32_t use_linear, const float bg[4],
+                            float4 *out_dev, hipStream_t stream);
 // the frame launch for a.render.technique
 inline hipError_t vr_launch_frame(const RaycastLaunch &a, hipStream_t stream)
 {

@@ -1,5 +1,5 @@
 // vr_renderer.h -- the host state of one renderer (vrhip_renderer, include/vrhip.h), shared by the units that
-// implement the C ABI: vrhip_api.hip, vrhip_gather.hip, vrhip_ingest_api.hip.  Host only.
+// implement the C ABI: vrhip_api.hip, vrhip_gather.hip, vrhip_ingest_api.hip, vrhip_slice_api.hip.  Host only.
 //  * DevBuf / Handle: device memory, events and the stream, freed with the object that holds them;
 //  * grow(): the one place that (re)allocates a renderer's buffer;
 //  * the invalidation functions: one per cause, next to the table of what depends on what.
@@ -214,6 +214,13 @@ struct vrhip_renderer {
     // on the device and the pinned block they are copied through; grown on demand, kept, freed with the renderer
     DevBuf<uint32_t> rgba8_dev;
     PinnedBuf rgba8_host;
+
+    // slice views (vrhip_render_slices, vrhip_slice_api.hip): the parameter blocks of a call in device memory, and --
+    // for a host destination -- the images on the device and the pinned block they are copied through; grown on
+    // demand, kept, freed with the renderer.  No render entry point reads them.
+    DevBuf<vrhip_slice_params> slice_params_dev;
+    DevBuf<float4> slice_out_dev;
+    PinnedBuf slice_host;
 
     // device-side ingest (vrhip_ingest_raw, vrhip_volume_histogram): the running maximum and the 256 64-bit
     // histogram counters in device memory, the events around its kernels (all created on first use)

@@ -363,3 +363,108 @@ def orbit_views(axis, n, rotation=DEFAULT_ROTATION, translation=DEFAULT_TRANSLAT
         raise ValueError("orbit_views: n >= 1")
     return [view_matrix(quat_mul(rotation, quat_from_axis_angle(axis, 360.0 * k / int(n))), translation)
             for k in range(int(n))]
+
+
+# ---- slice views (include/vrhip.h "slice views"; VolumeRenderCL.render_slices).  The contract is the 80-byte
+# vrhip_slice_params block; the helpers below compute in float64 and store float32.
+
+_SLICE_MODES = {"max": 0, "min": 1, "mean": 2}
+_SLICE_OUTPUTS = {"tf": 0, "value": 1}
+
+
+def make_slice(origin, u, v, w=(0.0, 0.0, 0.0), samples=1, mode="max", output="tf"):
+    """A SliceParams from its vectors in box space (the volume is [-1, 1]^3): origin = image centre, u = centre ->
+    centre of the right edge, v = centre -> centre of the top edge, w = the slab from its first to its last face
+    (zeros: a thin slice).  mode "max" | "min" | "mean" over `samples` planes; output "tf" (transfer function over
+    the background) or "value" (the filtered value itself in r, g, b; alpha 1)."""
+    from ._lib import SliceParams
+    if mode not in _SLICE_MODES:
+        raise ValueError("slice mode must be 'max', 'min' or 'mean'")
+    if output not in _SLICE_OUTPUTS:
+        raise ValueError("slice output must be 'tf' or 'value'")
+    if not 1 <= int(samples) <= 256:
+        raise ValueError("slice samples must be 1 .. 256")
+    s = SliceParams()
+    for name, vec in (("origin", origin), ("u", u), ("v", v), ("w", w)):
+        vec = np.asarray(vec, dtype=np.float64).reshape(-1)
+        if vec.size != 3 or not np.all(np.isfinite(vec)):
+            raise ValueError("slice %s must be three finite numbers" % name)
+        getattr(s, name)[:] = [float(np.float32(x)) for x in vec] + [0.0]
+    s.samples, s.mode, s.output, s.reserved = int(samples), _SLICE_MODES[mode], _SLICE_OUTPUTS[output], 0
+    return s
+
+
+def axis_slice(axis, position, thickness=0.0, samples=1, mode="max", output="tf"):
+    """The full cross-section of the box perpendicular to `axis` ("x", "y", "z" or 0, 1, 2) at `position` in [-1, 1]
+    along it; thickness (box units, along +axis, centred on position) and samples make it a slab.
+    Orientation, for a volume array vol[z, y, x] (row 0 of an image is its top):
+      axis z (axial):    right = +x, up = +y    image[r, c] ~ vol[iz, ny - 1 - r, c]
+      axis y (coronal):  right = -x, up = +z    image[r, c] ~ vol[nz - 1 - r, iy, nx - 1 - c]
+      axis x (sagittal): right = +y, up = +z    image[r, c] ~ vol[nz - 1 - r, c, ix]
+    i.e. each is seen from the positive side of its axis: u x v points along +axis, at the viewer, and slice_stack
+    steps from -1 towards +1.
+    The image always spans the whole box, whatever its size in pixels: the caller picks width : height from the
+    model scale (VolumeRenderCL.params()[1].modelScale; the box's physical extent along an axis is 2 / modelScale)
+    -- or width, height = the resolution along right and up for one pixel per voxel."""
+    a = {"x": 0, "y": 1, "z": 2}.get(axis.lower(), None) if isinstance(axis, str) else int(axis)
+    if a not in (0, 1, 2):
+        raise ValueError("slice axis must be 'x', 'y' or 'z'")
+    right, up = ((1, 2), (0, 2), (0, 1))[a]
+    origin, u, v, w = np.zeros(3), np.zeros(3), np.zeros(3), np.zeros(3)
+    origin[a] = float(position)
+    u[right] = -1.0 if a == 1 else 1.0
+    v[up] = 1.0
+    w[a] = float(thickness)
+    return make_slice(origin, u, v, w, samples, mode, output)
+
+
+def plane_slice(origin, normal, up, half_width, half_height, thickness=0.0, samples=1, mode="max", output="tf"):
+    """An oblique plane through `origin` (box space) perpendicular to `normal`: v = half_height * the unit vector of
+    `up` made orthogonal to the normal, u = half_width * (v^ x n^) -- seen from the side the normal points to, right
+    is to the right (normal +z, up +y: right = +x) -- and w = thickness * n^."""
+    n = np.asarray(normal, dtype=np.float64).reshape(-1)
+    upv = np.asarray(up, dtype=np.float64).reshape(-1)
+    if n.size != 3 or upv.size != 3 or not np.all(np.isfinite(n)) or not np.all(np.isfinite(upv)):
+        raise ValueError("plane_slice: normal and up must be three finite numbers")
+    ln = np.linalg.norm(n)
+    if not ln > 0:
+        raise ValueError("plane_slice: the normal must not be zero")
+    n = n / ln
+    vv = upv - n * np.dot(upv, n)
+    lv = np.linalg.norm(vv)
+    if not lv > 1e-12 * max(1.0, np.linalg.norm(upv)):
+        raise ValueError("plane_slice: up must not be parallel to the normal")
+    vv = vv / lv
+    uu = np.cross(vv, n)
+    return make_slice(origin, uu * float(half_width), vv * float(half_height), n * float(thickness), samples, mode, output)
+
+
+def slice_normal(s):
+    """The unit normal of a SliceParams (float64): along w for a slab, else u x v."""
+    w = np.array(s.w[:3], dtype=np.float64)
+    if not np.any(w != 0):
+        w = np.cross(np.array(s.u[:3], dtype=np.float64), np.array(s.v[:3], dtype=np.float64))
+    ln = np.linalg.norm(w)
+    if not ln > 0:
+        raise ValueError("slice has no normal (u x v and w are zero)")
+    return w / ln
+
+
+def slice_stack(s, n, span):
+    """n parallel copies of slice `s` stepped along its normal over `span` box units centred on s.origin: copy k
+    sits at origin + ((k + 0.5) / n - 0.5) * span * normal, k = 0 .. n - 1 (span 2 and n = the resolution along an
+    axis: one axis_slice through every voxel centre, from -1 towards +1)."""
+    from ._lib import SliceParams
+    import ctypes as C
+    if int(n) < 1:
+        raise ValueError("slice_stack: n >= 1")
+    nrm = slice_normal(s)
+    o = np.array(s.origin[:3], dtype=np.float64)
+    out = []
+    for k in range(int(n)):
+        c = SliceParams()
+        C.memmove(C.byref(c), C.byref(s), C.sizeof(SliceParams))
+        p = o + ((k + 0.5) / int(n) - 0.5) * float(span) * nrm
+        c.origin[:] = [float(np.float32(x)) for x in p] + [0.0]
+        out.append(c)
+    return out

@@ -404,6 +404,33 @@ class VolumeRenderCL:
         self._rendering.iteration += int(sd.size)
         return out
 
+    # ---- slice views (no reference counterpart; include/vrhip.h "slice views")
+    def render_slices(self, width, height, slices, out_dev_ptr=None):
+        """2-D cuts through the voxels (vrhip_render_slices): `slices` is a SliceParams or a sequence of them
+        (frontend.axis_slice, plane_slice, slice_stack build them), all rendered by one launch at width x height.
+        Returns float32 [n, height, width, 4], row 0 = top; with out_dev_ptr (device memory of that size, 16-byte
+        aligned) the images are written there without a wait and None is returned.  Reads the volume of the current
+        time step, the transfer function, setLinearInterpolation and setBackground; the camera, the technique, the
+        iteration and the seed are neither read nor touched: progressive frames carry on around it bit for bit."""
+        if not self._vol_loaded:
+            raise RuntimeError("No volume data is loaded.")
+        if isinstance(slices, _lib.SliceParams):
+            slices = [slices]
+        slices = list(slices)
+        for s in slices:
+            if not isinstance(s, _lib.SliceParams):
+                raise ValueError("render_slices: a sequence of SliceParams")
+        arr = (_lib.SliceParams * max(1, len(slices)))(*slices)
+        self._push_params()
+        out = None
+        if out_dev_ptr is None:
+            out = np.empty((len(slices), int(height), int(width), 4), dtype=np.float32)
+        self._check(self._lib.vrhip_render_slices(
+            self._h, int(width), int(height), C.cast(arr, C.c_void_p), len(slices),
+            out.ctypes.data_as(C.c_void_p) if out is not None else C.c_void_p(out_dev_ptr),
+            0 if out is not None else 1))
+        return out
+
     # ---- volume
     def loadVolumeData(self, props, ingest="host"):
         """volumerendercl.cpp:765-805. `props` is a datraw.Properties (dat_file_name or
