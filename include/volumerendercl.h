@@ -183,6 +183,33 @@ public:
     // (returns without waiting), or host memory with outIsDevice = false (returns when the bytes have arrived)
     void renderSlicesRGBA8(size_t width, size_t height, const std::vector<slice_params> &slices, float *dev_frames,
                            unsigned char *out, bool outIsDevice = true);
+    // ---- depth images and picking (no reference counterpart; vrhip.h "depth images and picking"): where along its
+    // ray each pixel's "thing" lies -- the first sample at or above a value (DEPTH_ISO, refined as technique 4 refines),
+    // the first sample that attains the ray's maximum (DEPTH_MAX), or the sample at which the ray caster's accumulated
+    // opacity reaches a threshold (DEPTH_OPACITY).  The rays are the current camera's, with the jitter seed of the frame
+    // last rendered (or the one pinned with setSeed): a pick lands in the frame on the screen.  Technique, iteration and
+    // frame buffer are neither read nor touched, so progressive frames carry on around a depth call bit for bit.
+    enum depth_mode { DEPTH_ISO = VRHIP_DEPTH_ISO, DEPTH_MAX = VRHIP_DEPTH_MAX, DEPTH_OPACITY = VRHIP_DEPTH_OPACITY };
+    enum depth_kind { DEPTH_MISS = VRHIP_DEPTH_MISS, DEPTH_NO_HIT = VRHIP_DEPTH_NO_HIT, DEPTH_HIT = VRHIP_DEPTH_HIT };
+    struct depth_image {
+        size_t width = 0, height = 0;      // of the rectangle answered
+        std::vector<float> xyzt;           // [height][width][4]: hit position in box space ([-1, 1]^3) and ray parameter t;
+                                           // (0, 0, 0, +inf) without a hit
+        std::vector<float> aux;            // [height][width]: ISO the value at the hit, MAX the maximum, OPACITY the opacity reached
+        std::vector<unsigned char> kind;   // [height][width]: depth_kind
+    };
+    // rect = {x0, y0, w, h}: that rectangle of the width x height frame; all zero: the whole frame.  Row 0 = top.
+    void renderDepth(size_t width, size_t height, depth_mode mode, float threshold, depth_image &output,
+                     unsigned int refineSteps = 4, const std::array<unsigned int, 4> &rect = {{0, 0, 0, 0}});
+    struct pick_result {
+        bool hit = false;
+        std::array<float, 3> pos{{0.f, 0.f, 0.f}};     // box space
+        float t = 0.f, aux = 0.f;
+        std::array<double, 3> voxel{{0., 0., 0.}};     // (pos * 0.5 + 0.5) * resolution: continuous voxel coordinates
+    };
+    // the 3-D point under pixel (x, y) of the width x height frame: renderDepth on a 1 x 1 rectangle
+    pick_result pick(size_t width, size_t height, unsigned int x, unsigned int y, depth_mode mode, float threshold = 0.5f,
+                     unsigned int refineSteps = 4);
     // ---- the progressive path tracer (technique 1), many samples per call (vrhip_render_samples): seeds.size()
     // consecutive iterations of the accumulated image -- sample k with jitter seed seeds[k] at iteration
     // (current iteration + k) -- in as few launch sets as possible, bit for bit what seeds.size() runRaycastNoGL calls

@@ -311,6 +311,67 @@ typedef struct vrhip_slice_params {
 int vrhip_render_slices(vrhip_renderer *r, uint32_t width, uint32_t height, const vrhip_slice_params *slices,
                         uint32_t n_slices, float *out_rgba, int out_is_device);
 
+/* ---- depth images and picking: where along its ray a pixel's "thing" lies (no reference counterpart; DESIGN.md
+ * "Depth images and picking").  An entry point of its own, not a technique: values 3 and 5 of
+ * rendering_params.technique stay unassigned.  All arithmetic is fp32, every operation rounded on its own, in the
+ * order written.
+ *  Ray: exactly technique 0's ray for pixel (gx, gy) of the width x height frame with object-order ESS off, as for
+ *   techniques 2 and 4: the renderer's camera, ortho, bbox_bl / bbox_tr, rendering_params.seed (jitter) and
+ *   raycast_params.samplingRate.  Samples: t_0 = max(0, tnear), t_{k+1} = t_k + stepSize while t_k < tfar; a step
+ *   that no longer changes t ends the sequence.  Sample k sits at cam + dir * (t_k - offset); its value s_k is the
+ *   normalised, filtered channel-0 value of the current time step (useLinear: trilinear, else nearest).
+ *  Hit, by mode:
+ *   VRHIP_DEPTH_ISO: technique 4's hit and refinement, word for word, with isoValue = threshold: the first k with
+ *    s_k >= isoValue (a NaN never hits); unless k = 0 or refineSteps = 0, ta = t_{k-1}, tb = t_k, refineSteps times
+ *    tm = (ta + tb) * 0.5f, s = the fetch at tm, s >= isoValue ? tb = tm : ta = tm; t = tb.
+ *   VRHIP_DEPTH_MAX: m starts at -inf and sample k replaces it only when s_k > m; t is the t_k of the last
+ *    replacement, i.e. of the first sample that attains the maximum.  A ray whose samples never replace m (all NaN
+ *    or -inf) is NO_HIT.
+ *   VRHIP_DEPTH_OPACITY: technique 0's accumulated opacity without the aerial depth cue: c = TF(s_k), the ray
+ *    caster's transfer-function read; refInterval = 1.f / samplingRate; opacity = 1.f - powr(1.f - c.a, refInterval)
+ *    with the ray caster's powr; alpha = alpha + opacity * (1.f - alpha) from alpha = 0.  The hit is the first k with
+ *    alpha >= threshold after sample k's update, t = t_k.  Threshold 0 hits at k = 0; a threshold above 1 never hits.
+ *  Outputs, each dense over the w x h rectangle, row 0 at the top; any may be NULL, not all three:
+ *   out_xyzt, four floats per pixel.  HIT: d = t - offset, then (cam.x + dir.x * d, cam.y + dir.y * d,
+ *    cam.z + dir.z * d, t): the position in box space, the volume being [-1, 1]^3 (texture coordinate = p * 0.5 + 0.5),
+ *    and the ray parameter.  NO_HIT and MISS: (0, 0, 0, +inf).
+ *   out_aux, one float per pixel.  ISO: the value fetched at t -- the fetch that last answered >= isoValue, sample
+ *    k's when nothing was refined.  MAX: m.  OPACITY: alpha where the ray stopped, whether it hit or ran out of
+ *    samples.  MISS in any mode, and NO_HIT in ISO: 0.
+ *   out_kind, one byte per pixel: VRHIP_DEPTH_MISS when the ray misses the box, else VRHIP_DEPTH_NO_HIT or
+ *    VRHIP_DEPTH_HIT.
+ *   Host memory goes through a staging block the renderer owns and the call returns after the copy; with
+ *   out_is_device != 0 the three pointers are device memory, out_xyzt 16-byte aligned, and the call returns without
+ *   synchronising.
+ *  vrhip_set_object_ess: on, samples whose outcome is known from the cell grid are not fetched -- ISO and MAX as
+ *   techniques 4 and 2, OPACITY samples in cells whose every fetch maps to opacity exactly 0; no output bit changes.
+ *  State: reads the volume, the time step, the camera, seed, useLinear, samplingRate and the object-ESS switch, in
+ *   OPACITY mode the transfer function -- not the technique, illumination, aerial, imgEss, showEss, useAO, iteration,
+ *   vrhip_iso_params or the environment map -- and writes nothing a render entry point reads later: not the frame
+ *   buffer, the hit images, the launch sets' control words or vrhip_last_launch_info.
+ *  VRHIP_ERR_INVALID: a NULL r or p, all outputs NULL, mode > 2, reserved != 0, a non-finite threshold in ISO or
+ *   OPACITY, refineSteps > 16 in ISO, a width or height vrhip_render_frame refuses, a rectangle that is not inside
+ *   the frame or has exactly one of w, h zero.  VRHIP_ERR_UNSUPPORTED: RG / RGBA volumes.  VRHIP_ERR_NODATA: no
+ *   volume; no transfer function in OPACITY mode. */
+enum { VRHIP_DEPTH_ISO = 0, VRHIP_DEPTH_MAX = 1, VRHIP_DEPTH_OPACITY = 2 };   /* mode */
+enum { VRHIP_DEPTH_MISS = 0, VRHIP_DEPTH_NO_HIT = 1, VRHIP_DEPTH_HIT = 2 };   /* kind */
+typedef struct vrhip_depth_params {
+    uint32_t mode;
+    float threshold;       /* ISO: isoValue, in the transfer function's coordinate, as vrhip_iso_params.isoValue;
+                              OPACITY: the accumulated opacity to reach; MAX: not read */
+    uint32_t refineSteps;  /* ISO only, <= 16 */
+    uint32_t x0, y0, w, h; /* the rectangle of the width x height frame to answer; w == h == 0: the whole frame */
+    uint32_t reserved;     /* must be 0 */
+} vrhip_depth_params;      /* 32 bytes */
+int vrhip_render_depth(vrhip_renderer *r, uint32_t width, uint32_t height, const vrhip_depth_params *p,
+                       float *out_xyzt, float *out_aux, uint8_t *out_kind, int out_is_device);
+/* What the last vrhip_render_depth launched: its mode, the 8 x 8 patches of its rectangle, and whether the kernel
+ * was handed the cell grid (1) or fetched every sample (0).  VRHIP_ERR_NODATA before the first call. */
+typedef struct vrhip_depth_info {
+    uint32_t mode, work_items, empty_skip, reserved[5];
+} vrhip_depth_info;        /* 32 bytes */
+int vrhip_last_depth_info(const vrhip_renderer *r, vrhip_depth_info *out);
+
 /* createEnvironmentMap (volumerendercl.cpp:1121-1150): float RGBA texels, row-major, width*height*4
  * floats (the host layer decodes the Radiance .hdr file).  The kernel samples it in place of the
  * background colour when it is wider than one texel (volumeraycast.cl:506-510, :655-656);

@@ -61,6 +61,26 @@ class SliceParams(C.Structure):
                 ("samples", C.c_uint32), ("mode", C.c_uint32), ("output", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# vrhip_depth_params.mode and the bytes of out_kind (depth images, vrhip_render_depth)
+DEPTH_ISO, DEPTH_MAX, DEPTH_OPACITY = 0, 1, 2
+DEPTH_MISS, DEPTH_NO_HIT, DEPTH_HIT = 0, 1, 2
+
+
+class DepthParams(C.Structure):
+    """vrhip_depth_params: what a depth image looks for, and the rectangle of the frame it answers."""
+    _fields_ = [("mode", C.c_uint32), ("threshold", C.c_float), ("refineSteps", C.c_uint32), ("x0", C.c_uint32),
+                ("y0", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DepthInfo(C.Structure):
+    """vrhip_depth_info: what the last vrhip_render_depth launched."""
+    _fields_ = [("mode", C.c_uint32), ("work_items", C.c_uint32), ("empty_skip", C.c_uint32),
+                ("reserved", C.c_uint32 * 5)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 class Stats(C.Structure):
     _fields_ = [("samples_taken", C.c_uint64), ("samples_nominal", C.c_uint64),
                 ("samples_shaded", C.c_uint64), ("bricks_visited", C.c_uint64),
@@ -85,6 +105,7 @@ assert C.sizeof(LaunchInfo) == 128
 assert C.sizeof(CameraParams) == 128 and C.sizeof(RenderingParams) == 64
 assert C.sizeof(RaycastParams) == 32 and C.sizeof(PathtraceParams) == 4 and C.sizeof(IsoParams) == 16
 assert C.sizeof(SliceParams) == 80
+assert C.sizeof(DepthParams) == 32 and C.sizeof(DepthInfo) == 32
 
 _H = C.c_void_p
 _U3 = C.POINTER(C.c_uint32)
@@ -156,6 +177,9 @@ SYMBOLS = {
     "vrhip_set_object_ess": (C.c_int, [_H, C.c_int]),
     "vrhip_render_frame": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int]),
     "vrhip_render_slices": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int]),
+    "vrhip_render_depth": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(DepthParams), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int]),
+    "vrhip_last_depth_info": (C.c_int, [_H, C.POINTER(DepthInfo)]),
     "vrhip_render_tiles": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_void_p, C.c_uint32, C.c_void_p]),
     "vrhip_set_environment_map": (C.c_int, [_H, C.c_void_p, C.c_uint32, C.c_uint32]),

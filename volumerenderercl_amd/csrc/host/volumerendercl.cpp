@@ -685,6 +685,51 @@ void VolumeRenderCL::renderSlices(size_t width, size_t height, const std::vector
                                               dev_out, 1));
 }
 
+void VolumeRenderCL::renderDepth(size_t width, size_t height, depth_mode mode, float threshold, depth_image &output,
+                                 unsigned int refineSteps, const std::array<unsigned int, 4> &rect)
+{
+    if (!_volLoaded) throw std::runtime_error("No volume data is loaded.");
+    vrhip_depth_params p{};
+    p.mode = uint32_t(mode);
+    p.threshold = threshold;
+    p.refineSteps = refineSteps;
+    p.x0 = rect[0]; p.y0 = rect[1]; p.w = rect[2]; p.h = rect[3];
+    const bool whole = rect[2] == 0 && rect[3] == 0;
+    output.width = whole ? width : rect[2];
+    output.height = whole ? height : rect[3];
+    const size_t n = output.width * output.height;
+    output.xyzt.resize(n * 4);
+    output.aux.resize(n);
+    output.kind.resize(n);
+    // the rays of the frame last rendered: its seed is still in the parameters; a pinned seed (setSeed) holds at once
+    if (_seedPinned) _rendering_params.seed = _pinnedSeed;
+    pushParams();
+    // (an empty rectangle -- exactly one of w, h zero -- is the library's to refuse: the pointers only must not be null)
+    float none_f[4];
+    unsigned char none_k;
+    check("renderDepth", vrhip_render_depth(_r, uint32_t(width), uint32_t(height), &p, n ? output.xyzt.data() : none_f,
+                                            n ? output.aux.data() : none_f, n ? output.kind.data() : &none_k, 0));
+}
+
+VolumeRenderCL::pick_result VolumeRenderCL::pick(size_t width, size_t height, unsigned int x, unsigned int y,
+                                                 depth_mode mode, float threshold, unsigned int refineSteps)
+{
+    depth_image d;
+    renderDepth(width, height, mode, threshold, d, refineSteps, {{x, y, 1u, 1u}});
+    pick_result res;
+    res.hit = d.kind[0] == DEPTH_HIT;
+    if (!res.hit) return res;
+    uint32_t r4[4] = {0, 0, 0, 0};
+    check("pick", vrhip_get_resolution(_r, r4));
+    for (int i = 0; i < 3; ++i) {
+        res.pos[i] = d.xyzt[i];
+        res.voxel[i] = (double(d.xyzt[i]) * 0.5 + 0.5) * double(r4[i]);
+    }
+    res.t = d.xyzt[3];
+    res.aux = d.aux[0];
+    return res;
+}
+
 void VolumeRenderCL::renderSlicesRGBA8(size_t width, size_t height, const std::vector<slice_params> &slices,
                                        float *dev_frames, unsigned char *out, bool outIsDevice)
 {

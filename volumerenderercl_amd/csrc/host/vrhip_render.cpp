@@ -15,6 +15,7 @@
 #include <map>
 #include <cctype>
 #include <iterator>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -472,6 +473,19 @@ void write_rgba8(const std::string &out, const std::vector<unsigned char> &frame
         "                                           slices go to PREFIX.frames.rgba.f32, the last to PREFIX.rgba.f32, with\n"
         "                                           --rgba8 also as bytes; not with --mip, --iso, --pathtrace, --orbit,\n"
         "                                           --camera-path, --ranks)\n"
+        "         [--depth iso V | max | opacity A] [--depth-refine N] [--depth-rect X Y W H]\n"
+        "                                          (a depth image instead of a rendered frame: per pixel of the camera's\n"
+        "                                           frame the first sample at or above V, refined by N (0-16, default 4)\n"
+        "                                           bisections (iso), the first sample that attains the ray's maximum (max),\n"
+        "                                           or the sample at which the accumulated opacity reaches A (opacity);\n"
+        "                                           --depth-rect: that rectangle of the frame only; writes\n"
+        "                                           PREFIX.depth.f32 (x y z t per pixel: box-space position and ray\n"
+        "                                           parameter, 0 0 0 inf without a hit), PREFIX.depth.aux.f32 (the value\n"
+        "                                           found), PREFIX.depth.kind.u8 (0 miss, 1 no hit, 2 hit) and PREFIX.ppm\n"
+        "                                           (grey: finite t between its minimum and maximum, non-hits black); not\n"
+        "                                           with --pathtrace, --mip, --iso, the slice options, --ranks,\n"
+        "                                           --frames-per-launch, --orbit, --camera-path, --frames, --rgba8,\n"
+        "                                           --img-ess; --depth-refine and --depth-rect need --depth)\n"
         "writes PREFIX.rgba.f32 (W*H*4 float32, row 0 = top), PREFIX.ppm and prints one JSON line\n";
     std::exit(2);
 }
@@ -512,6 +526,12 @@ int main(int argc, char **argv)
     int slice_axis = 2, slab_n = 1, stack_n = 0;
     double slice_pos = 0.0, slice_vec[9] = {0, 0, 0, 1, 0, 0, 0, 1, 0}, slab_t = 0.0;
     std::string slab_mode = "max";
+    // depth images (--depth, --depth-refine, --depth-rect)
+    bool depth = false, have_depth_refine = false, have_depth_rect = false;
+    std::string depth_mode;
+    double depth_threshold = 0.5;
+    int depth_refine = 4;
+    long depth_rect[4] = {0, 0, 0, 0};
 
     auto need = [&](int i, int n) { if (i + n >= argc) usage(); };
     for (int i = 1; i < argc; ++i) {
@@ -587,6 +607,14 @@ int main(int argc, char **argv)
         else if (a == "--slice-stack") { need(i, 1); stack_n = std::atoi(argv[++i]); have_stack = true; }
         else if (a == "--slice-value") slice_value = true;
         else if (a == "--dump-views") { need(i, 1); dump_views = argv[++i]; }
+        else if (a == "--depth") {
+            need(i, 1);
+            depth = true;
+            depth_mode = argv[++i];
+            if (depth_mode == "iso" || depth_mode == "opacity") { need(i, 1); depth_threshold = std::atof(argv[++i]); }
+        }
+        else if (a == "--depth-refine") { need(i, 1); have_depth_refine = true; depth_refine = std::atoi(argv[++i]); }
+        else if (a == "--depth-rect") { need(i, 4); for (int k = 0; k < 4; ++k) depth_rect[k] = std::atol(argv[++i]); have_depth_rect = true; }
         else usage();
     }
     if (have_path_arg && (camera_path.empty() || have_orbit)) usage();
@@ -613,6 +641,21 @@ int main(int argc, char **argv)
             const double *u = slice_vec + 3, *v = slice_vec + 6;
             const double n[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
             if (n[0] * n[0] + n[1] * n[1] + n[2] * n[2] == 0.0) usage();
+        }
+    }
+    if ((have_depth_refine || have_depth_rect) && !depth) usage();
+    if (depth) {
+        if (depth_mode != "iso" && depth_mode != "max" && depth_mode != "opacity") usage();
+        if (pathtrace || mip || iso || slicing || have_slab || have_stack || slice_value || ranks > 0 || frames_per_launch > 0)
+            usage();
+        // one depth image of one camera: what asks for several frames, or for a frame's own state, has nothing to act on
+        if (have_orbit || have_path_arg || frames != 1 || rgba8 || img_ess) usage();
+        if (!std::isfinite(depth_threshold) || depth_refine < 0 || depth_refine > 16) usage();
+        if (have_depth_rect) {
+            for (long c : depth_rect) if (c < 0 || c > 16384) usage();
+            if (depth_rect[2] < 1 || depth_rect[3] < 1 || depth_rect[0] + depth_rect[2] > long(W) ||
+                depth_rect[1] + depth_rect[3] > long(H))
+                usage();
         }
     }
     if (have_orbit && (orbit_n < 1 || orbit_n > 1 << 20 ||
@@ -967,6 +1010,52 @@ int main(int argc, char **argv)
                         "\"samples\": %d, \"mode\": \"%s\", \"output\": \"%s\", \"out\": \"%s.rgba.f32\"}\n",
                         vr.getCurrentDeviceName().c_str(), res[0], res[1], res[2], W, H, slices.size(), slab_n,
                         slab_mode.c_str(), slice_value ? "value" : "tf", out.c_str());
+            return 0;
+        }
+        if (depth) {
+            // ---- a depth image (VolumeRenderCL::renderDepth) of the options' camera
+            const VolumeRenderCL::depth_mode mode = depth_mode == "max" ? VolumeRenderCL::DEPTH_MAX
+                                                    : depth_mode == "opacity" ? VolumeRenderCL::DEPTH_OPACITY
+                                                                              : VolumeRenderCL::DEPTH_ISO;
+            VolumeRenderCL::depth_image d;
+            std::array<unsigned int, 4> rect{{0, 0, 0, 0}};
+            if (have_depth_rect) for (size_t k = 0; k < 4; ++k) rect[k] = unsigned(depth_rect[k]);
+            vr.renderDepth(W, H, mode, float(depth_threshold), d, unsigned(depth_refine), rect);
+            const size_t n = d.width * d.height;
+            size_t hits = 0;
+            float t_min = std::numeric_limits<float>::infinity(), t_max = -std::numeric_limits<float>::infinity();
+            for (size_t i = 0; i < n; ++i) {
+                if (d.kind[i] != VolumeRenderCL::DEPTH_HIT) continue;
+                ++hits;
+                t_min = std::min(t_min, d.xyzt[4 * i + 3]);
+                t_max = std::max(t_max, d.xyzt[4 * i + 3]);
+            }
+            // grey: near = bright; finite t scaled between its minimum and maximum, non-hits black
+            frame.assign(n * 4, 0.f);
+            for (size_t i = 0; i < n; ++i) {
+                frame[4 * i + 3] = 1.f;
+                if (d.kind[i] != VolumeRenderCL::DEPTH_HIT) continue;
+                const float g = t_max > t_min ? 1.f - (d.xyzt[4 * i + 3] - t_min) / (t_max - t_min) : 1.f;
+                frame[4 * i] = frame[4 * i + 1] = frame[4 * i + 2] = g;
+            }
+            std::ofstream fx(out + ".depth.f32", std::ios::binary);
+            fx.write(reinterpret_cast<const char *>(d.xyzt.data()), std::streamsize(d.xyzt.size() * sizeof(float)));
+            std::ofstream fa(out + ".depth.aux.f32", std::ios::binary);
+            fa.write(reinterpret_cast<const char *>(d.aux.data()), std::streamsize(d.aux.size() * sizeof(float)));
+            std::ofstream fk(out + ".depth.kind.u8", std::ios::binary);
+            fk.write(reinterpret_cast<const char *>(d.kind.data()), std::streamsize(d.kind.size()));
+            write_ppm(out + ".ppm", frame, d.width, d.height);
+            char t_lo[32] = "null", t_hi[32] = "null";
+            if (hits) {
+                std::snprintf(t_lo, sizeof t_lo, "%.9g", double(t_min));
+                std::snprintf(t_hi, sizeof t_hi, "%.9g", double(t_max));
+            }
+            auto res = vr.getResolution();
+            std::printf("{\"device\": \"%s\", \"volume\": [%u, %u, %u], \"width\": %zu, \"height\": %zu, "
+                        "\"rect\": [%u, %u, %zu, %zu], \"mode\": \"%s\", \"hits\": %zu, \"t_min\": %s, \"t_max\": %s, "
+                        "\"out\": \"%s.depth.f32\"}\n",
+                        vr.getCurrentDeviceName().c_str(), res[0], res[1], res[2], W, H, rect[0], rect[1], d.width, d.height,
+                        depth_mode.c_str(), hits, t_lo, t_hi, out.c_str());
             return 0;
         }
         if (frames_per_launch > 0) {

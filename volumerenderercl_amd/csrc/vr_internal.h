@@ -428,6 +428,26 @@ hipError_t vr_launch_iso(const RaycastLaunch &a, hipStream_t stream);
 hipError_t vr_launch_slices(const VolView &vol, int format, const TfView &tf, const vrhip_slice_params *slices_dev,
                             uint32_t n_slices, uint32_t W, uint32_t H, uint32_t use_linear, const float bg[4],
                             float4 *out_dev, hipStream_t stream);
+// depth images (vrhip_render_depth): one wave per 8x8 patch of the rectangle params.(x0, y0, w, h) -- w, h resolved,
+// never 0 -- of the frame.W x frame.H frame; the outputs are dense over the rectangle, any of them nullptr.
+// frame: W, H, gsx, gsy and the ray_* fields only (nothing else of it is read).  Skipping: cell_minmax (ISO, MAX; its
+// grid in cells' e* fields, as for vr_launch_mip) or cells.empty (OPACITY), nullptr: every sample is fetched; vr_depth.hip
+struct DepthLaunch {
+    VolView vol;
+    TfView tf;
+    CellView cells;
+    const float2 *cell_minmax;
+    FrameView frame;
+    vrhip_camera_params cam;
+    vrhip_rendering_params render;
+    vrhip_raycast_params raycast;
+    vrhip_depth_params params;
+    int format;            // vrhip_format
+    float4 *out_xyzt;
+    float *out_aux;
+    uint8_t *out_kind;
+};
+hipError_t vr_launch_depth(const DepthLaunch &a, hipStream_t stream);
 // the frame launch for a.render.technique
 inline hipError_t vr_launch_frame(const RaycastLaunch &a, hipStream_t stream)
 {

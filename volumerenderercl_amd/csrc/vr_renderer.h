@@ -1,5 +1,5 @@
 // vr_renderer.h -- the host state of one renderer (vrhip_renderer, include/vrhip.h), shared by the units that
-// implement the C ABI: vrhip_api.hip, vrhip_gather.hip, vrhip_ingest_api.hip, vrhip_slice_api.hip.  Host only.
+// implement the C ABI: vrhip_api.hip, vrhip_gather.hip, vrhip_ingest_api.hip, vrhip_slice_api.hip, vrhip_depth_api.hip.  Host only.
 //  * DevBuf / Handle: device memory, events and the stream, freed with the object that holds them;
 //  * grow(): the one place that (re)allocates a renderer's buffer;
 //  * the invalidation functions: one per cause, next to the table of what depends on what.
@@ -222,6 +222,14 @@ struct vrhip_renderer {
     DevBuf<float4> slice_out_dev;
     PinnedBuf slice_host;
 
+    // depth images (vrhip_render_depth, vrhip_depth_api.hip): for host destinations, the three outputs of a call in
+    // one device block and the pinned block they are copied through; what the last call launched
+    // (vrhip_last_depth_info).  Grown on demand, kept, freed with the renderer.  No render entry point reads them.
+    DevBuf<> depth_out_dev;
+    PinnedBuf depth_host;
+    vrhip_depth_info depth_info;
+    bool have_depth_info = false;
+
     // device-side ingest (vrhip_ingest_raw, vrhip_volume_histogram): the running maximum and the 256 64-bit
     // histogram counters in device memory, the events around its kernels (all created on first use)
     size_t ingest_slab_bytes = (size_t)256 << 20;   // VRHIP_INGEST_SLAB_BYTES: staging per slab
@@ -399,9 +407,34 @@ inline TfView make_tf_view(const vrhip_renderer *r)
     return t;
 }
 
+// what make_ray derives the camera from: the frame size and the reference's padded launch size
+inline void set_frame_geometry(FrameView *f, uint32_t width, uint32_t height)
+{
+    f->W = width;
+    f->H = height;
+    // padded NDRange of the reference (volumerendercl.cpp:513-514): a full extra group
+    // when the size is already a multiple of 8; the camera is derived from it.
+    f->gsx = width + (8u - width % 8u);
+    f->gsy = height + (8u - height % 8u);
+    const float gsx = (float)f->gsx, gsy = (float)f->gsy;
+    float aspect = gsy / gsx;
+    const float other = gsx / gsy;
+    aspect = other < aspect ? other : aspect;   // vmin(aspect, other), vr_device_math.h
+    f->ray_aspect = aspect;
+    f->ray_psx = 2.f / gsx;
+    f->ray_psy = 2.f / gsy;
+}
+
 // (re)allocate a slot for `timestep`, checking that res/format agree with other timesteps (vrhip_api.hip)
 int prepare_slot(vrhip_renderer *r, const uint32_t res[3], int format, uint32_t timestep, VolumeSlot **slot,
                  int channels = 1);
+// the cell grids of the current time step, and what the units outside vrhip_api.hip ask of them (vrhip_api.hip):
+// ensure_cells builds what is stale (tables = false: the (min, max) pairs and the geometry only, nothing made from
+// the transfer function); cell_minmax_of: the pairs as ensure_cells left them; mip_skips: do techniques 2 and 4 --
+// and the depth images -- step over samples with object-order ESS on
+int ensure_cells(vrhip_renderer *r, bool need_bound, bool need_empty, bool tables = true);
+const float2 *cell_minmax_of(const vrhip_renderer *r, bool fine);
+bool mip_skips(const vrhip_renderer *r);
 
 // ---- derived state: what is built lazily from what, and what makes it stale
 //

@@ -117,24 +117,8 @@ bool ray_skip_empty(const vrhip_renderer *r)
     return std::max(r->brick_edge[0], std::max(r->brick_edge[1], r->brick_edge[2])) >= (4u << eshift);
 }
 
-// Technique 2 steps over samples that cannot raise the running maximum when object-order ESS is on, technique 4
-// over march samples that cannot reach isoValue (VRHIP_NO_EMPTY_SKIP=1 disables this like the ray caster's empty runs).
-bool mip_skips(const vrhip_renderer *r) { return r->use_ess && r->skip_empty; }
 // the techniques that are one launch over the cells' (min, max): maximum intensity projection, first-hit isosurface
 bool minmax_technique(uint32_t t) { return t == VRHIP_TECHNIQUE_MIP || t == VRHIP_TECHNIQUE_ISO; }
-
-// The (min, max) pairs of a cell grid of the current time step as ensure_cells left them: the renderer's own, or
-// -- for a renderer that shares another one's voxels -- the owner's.  nullptr: not built.
-const float2 *cell_minmax_of(const vrhip_renderer *r, bool fine)
-{
-    const VolumeSlot &s = r->vols[r->timestep];
-    const float2 *src = fine ? (s.fine_minmax_valid ? s.fine_minmax.p : nullptr) : (s.pt_minmax_valid ? s.pt_minmax.p : nullptr);
-    if (!src && r->vol_owner && r->timestep < r->vol_owner->vols.size()) {
-        const VolumeSlot &os = r->vol_owner->vols[r->timestep];
-        src = fine ? (os.fine_minmax_valid ? os.fine_minmax.p : nullptr) : (os.pt_minmax_valid ? os.pt_minmax.p : nullptr);
-    }
-    return src;
-}
 
 // Sharers of `owner` lose their (borrowed) volumes: nothing of theirs points into the owner any more.
 void detach_sharers(vrhip_renderer *owner)
@@ -148,6 +132,24 @@ void detach_sharers(vrhip_renderer *owner)
 }
 
 } // namespace
+
+// (declared in vr_renderer.h: vrhip_depth_api.hip asks the same questions)
+// Technique 2 steps over samples that cannot raise the running maximum when object-order ESS is on, technique 4
+// over march samples that cannot reach isoValue (VRHIP_NO_EMPTY_SKIP=1 disables this like the ray caster's empty runs).
+bool mip_skips(const vrhip_renderer *r) { return r->use_ess && r->skip_empty; }
+
+// The (min, max) pairs of a cell grid of the current time step as ensure_cells left them: the renderer's own, or
+// -- for a renderer that shares another one's voxels -- the owner's.  nullptr: not built.
+const float2 *cell_minmax_of(const vrhip_renderer *r, bool fine)
+{
+    const VolumeSlot &s = r->vols[r->timestep];
+    const float2 *src = fine ? (s.fine_minmax_valid ? s.fine_minmax.p : nullptr) : (s.pt_minmax_valid ? s.pt_minmax.p : nullptr);
+    if (!src && r->vol_owner && r->timestep < r->vol_owner->vols.size()) {
+        const VolumeSlot &os = r->vol_owner->vols[r->timestep];
+        src = fine ? (os.fine_minmax_valid ? os.fine_minmax.p : nullptr) : (os.pt_minmax_valid ? os.pt_minmax.p : nullptr);
+    }
+    return src;
+}
 
 // (re)allocate a slot for `timestep`, checking that res/format agree with other timesteps
 int prepare_slot(vrhip_renderer *r, const uint32_t res[3], int format, uint32_t timestep,
@@ -386,11 +388,13 @@ static int build_cell_minmax(vrhip_renderer *r, VolumeSlot &s, const CellView &g
     return VRHIP_OK;
 }
 
+} // namespace
+
 // (Re)build what the coming frame needs of the cell grids when the volume, the timestep or the TF
 // changed: the opacity bounds (path tracer; cells of 2^shift voxels, at most 256 per axis: shift 3
 // up to 2048^3) and / or the empty bits (ray caster; cells of 2^eshift voxels, at most 512 per axis:
 // shift 2 up to 2048^3, 16 MiB of bits).
-int ensure_cells(vrhip_renderer *r, bool need_bound, bool need_empty)
+int ensure_cells(vrhip_renderer *r, bool need_bound, bool need_empty, bool tables)
 {
     if ((!need_bound || r->cells_have_bound) && (!need_empty || r->cells_have_empty)) return VRHIP_OK;
     VolumeSlot &s = r->vols[r->timestep];
@@ -442,13 +446,17 @@ int ensure_cells(vrhip_renderer *r, bool need_bound, bool need_empty)
     }
     if (s.pt_minmax_valid) coarse_mm = s.pt_minmax;
 
-    // ---- with the transfer function: bounds, empty bits
+    // ---- with the transfer function: bounds, empty bits (tables = false: a caller that reads the (min, max) alone and
+    // may have no transfer function -- vrhip_render_depth; the tables stay stale and the next caller builds them)
+    // (With tables = false nothing sets cells_have_empty, so the early return above does not hold for the next such
+    // call either: it walks through here again, down to `r->cells = g`.  That is host arithmetic and grow() calls that
+    // find their buffers large enough -- the (min, max) pairs are cached per slot and are not rebuilt.)
     // (the macro cells' bounds -- CellView::cbound -- sit behind the cells' in the same allocation)
     g.ccx = (g.cx + (1 << kLeapShift) - 1) >> kLeapShift;
     g.ccy = (g.cy + (1 << kLeapShift) - 1) >> kLeapShift;
     g.ccz = (g.cz + (1 << kLeapShift) - 1) >> kLeapShift;
     const size_t n_macro = (size_t)g.ccx * g.ccy * g.ccz;
-    if (need_bound && !r->cells_have_bound) {
+    if (tables && need_bound && !r->cells_have_bound) {
         if ((rc = grow(r, r->cell_bound, (n_cells + n_macro) * sizeof(float)))) return rc;
         VR_HIP(r, vr_launch_cell_bounds(coarse_mm, g, inv_max_of(r->format), make_tf_view(r),
                                         r->cell_sparse, r->cell_bound, nullptr, r->stream));
@@ -462,7 +470,7 @@ int ensure_cells(vrhip_renderer *r, bool need_bound, bool need_empty)
     g.bound = r->cells_have_bound ? r->cell_bound : nullptr;
     g.cbound = (r->cells_have_bound && r->pt_leap) ? r->cell_bound + n_cells : nullptr;
     g.cdist = (g.cbound && r->pt_leap_far) ? r->cell_dist_table : nullptr;
-    if (need_empty && !r->cells_have_empty) {
+    if (tables && need_empty && !r->cells_have_empty) {
         if ((rc = grow(r, r->cell_empty, ((n_fine + 63) / 64) * 2 * sizeof(uint32_t)))) return rc;
         VR_HIP(r, vr_launch_cell_bounds(one_grid ? coarse_mm : fine_mm, fine, inv_max_of(r->format),
                                         make_tf_view(r), r->cell_sparse, nullptr, r->cell_empty, r->stream));
@@ -473,6 +481,8 @@ int ensure_cells(vrhip_renderer *r, bool need_bound, bool need_empty)
     r->cells = g;
     return VRHIP_OK;
 }
+
+namespace {
 
 // Build (or reuse) the centre-first queue of 8x8 wave tiles.  tile_ids == nullptr: the whole
 // frame, `out` in frame layout; else the listed tiles, `out` compact [n][tile_h][tile_w].
@@ -556,21 +566,7 @@ void fill_launch(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t ou
     if (getenv("VRHIP_SKIP_GLOBAL")) a->skip.in_lds = 0;   // experiments: bitmap from L2/HBM
     a->skip.near_bits = r->cull_radius ? r->near_bits : nullptr;
     a->skip.near_r = r->cull_radius;
-    a->frame.W = width;
-    a->frame.H = height;
-    // padded NDRange of the reference (volumerendercl.cpp:513-514): a full extra group
-    // when the size is already a multiple of 8; the camera is derived from it.
-    a->frame.gsx = width + (8u - width % 8u);
-    a->frame.gsy = height + (8u - height % 8u);
-    {
-        const float gsx = (float)a->frame.gsx, gsy = (float)a->frame.gsy;
-        float aspect = gsy / gsx;
-        const float other = gsx / gsy;
-        aspect = other < aspect ? other : aspect;   // vmin(aspect, other), vr_device_math.h
-        a->frame.ray_aspect = aspect;
-        a->frame.ray_psx = 2.f / gsx;
-        a->frame.ray_psy = 2.f / gsy;
-    }
+    set_frame_geometry(&a->frame, width, height);
     a->frame.queue = r->queue_dev;
     a->frame.n_wave_tiles = r->queue_n;
     a->frame.out_stride = out_stride;

@@ -365,6 +365,27 @@ def orbit_views(axis, n, rotation=DEFAULT_ROTATION, translation=DEFAULT_TRANSLAT
             for k in range(int(n))]
 
 
+# ---- depth images (include/vrhip.h "depth images and picking"; VolumeRenderCL.render_depth / pick)
+
+def box_to_voxel(pos, res):
+    """Box-space positions ([-1, 1]^3, the last axis x, y, z) as continuous voxel coordinates: (pos * 0.5 + 0.5) * res,
+    in float64 -- the voxel whose cell holds the point is floor() of it."""
+    return (np.asarray(pos, dtype=np.float64) * 0.5 + 0.5) * np.asarray(res, dtype=np.float64)[:3]
+
+
+def depth_grey(xyzt, kind):
+    """A depth image as grey bytes [h, w], the picture `vrhip_render --depth` writes: hits between white (the
+    smallest t) and black (the largest), everything else black."""
+    t = np.asarray(xyzt, dtype=np.float32)[..., 3]
+    hit = np.asarray(kind) == 2
+    out = np.zeros(t.shape, dtype=np.uint8)
+    if hit.any():
+        lo, hi = t[hit].min(), t[hit].max()
+        g = 1.0 - (t[hit] - lo) / (hi - lo) if hi > lo else np.ones(int(hit.sum()), np.float32)
+        out[hit] = np.round(np.clip(g, 0.0, 1.0) * 255.0).astype(np.uint8)
+    return out
+
+
 # ---- slice views (include/vrhip.h "slice views"; VolumeRenderCL.render_slices).  The contract is the 80-byte
 # vrhip_slice_params block; the helpers below compute in float64 and store float32.
 

@@ -431,6 +431,65 @@ class VolumeRenderCL:
             0 if out is not None else 1))
         return out
 
+    # ---- depth images and picking (no reference counterpart; include/vrhip.h "depth images and picking")
+    _DEPTH_MODES = {"iso": _lib.DEPTH_ISO, "max": _lib.DEPTH_MAX, "opacity": _lib.DEPTH_OPACITY}
+
+    def _depth_params(self, mode, threshold, refine, rect):
+        if isinstance(mode, str):
+            if mode not in self._DEPTH_MODES:
+                raise ValueError("depth mode must be 'iso', 'max' or 'opacity'")
+            mode = self._DEPTH_MODES[mode]
+        p = _lib.DepthParams()
+        p.mode, p.threshold, p.refineSteps, p.reserved = int(mode), float(threshold), int(refine), 0
+        if rect is not None:
+            p.x0, p.y0, p.w, p.h = (int(v) for v in rect)
+        return p
+
+    def render_depth(self, width, height, mode, threshold=0.5, refine=4, rect=None, out_dev_ptrs=None):
+        """Where along its ray each pixel's "thing" lies (vrhip_render_depth).  mode "iso" (the first sample at or above
+        `threshold`, refined by `refine` bisections as technique 4 does), "max" (the first sample that attains the ray's
+        maximum) or "opacity" (the sample at which the ray caster's accumulated opacity reaches `threshold`); the
+        DEPTH_* numbers do as well.  rect = (x0, y0, w, h): that rectangle of the width x height frame only.
+        Returns (xyzt float32 [h, w, 4], aux float32 [h, w], kind uint8 [h, w]), row 0 = top: the hit position in
+        box space ([-1, 1]^3) and the ray parameter t, (0, 0, 0, inf) without a hit; the value found (iso: the sample
+        at the hit, max: the maximum, opacity: the opacity reached); DEPTH_MISS / DEPTH_NO_HIT / DEPTH_HIT.
+        With out_dev_ptrs = (xyzt, aux, kind) device addresses (0 or None: not wanted; xyzt 16-byte aligned) the
+        answer is written there without a wait and None is returned.  The rays are the current camera's and seed's;
+        the technique, the iteration and the frame buffer are neither read nor touched."""
+        p = self._depth_params(mode, threshold, refine, rect)
+        self._push_params()
+        if out_dev_ptrs is not None:
+            ptrs = [C.c_void_p(int(a)) if a else None for a in out_dev_ptrs]
+            self._check(self._lib.vrhip_render_depth(self._h, int(width), int(height), C.byref(p), ptrs[0], ptrs[1],
+                                                     ptrs[2], 1))
+            return None
+        w, h = (int(p.w), int(p.h)) if rect is not None else (int(width), int(height))
+        xyzt = np.empty((h, w, 4), dtype=np.float32)
+        aux = np.empty((h, w), dtype=np.float32)
+        kind = np.empty((h, w), dtype=np.uint8)
+        self._check(self._lib.vrhip_render_depth(self._h, int(width), int(height), C.byref(p),
+                                                 xyzt.ctypes.data_as(C.c_void_p), aux.ctypes.data_as(C.c_void_p),
+                                                 kind.ctypes.data_as(C.c_void_p), 0))
+        return xyzt, aux, kind
+
+    def pick(self, width, height, x, y, mode, threshold=0.5, refine=4):
+        """The 3-D point under pixel (x, y) of the width x height frame: render_depth on a 1 x 1 rectangle.  None when
+        the ray finds nothing; else a dict: pos (box space, float32 [3]), t, aux, and voxel = (pos * 0.5 + 0.5) * res,
+        the continuous voxel coordinates (float64 [3], x y z)."""
+        xyzt, aux, kind = self.render_depth(width, height, mode, threshold, refine, rect=(int(x), int(y), 1, 1))
+        if kind[0, 0] != _lib.DEPTH_HIT:
+            return None
+        pos = xyzt[0, 0, :3].copy()
+        voxel = frontend.box_to_voxel(pos, self._res[:3])
+        return {"pos": pos, "t": float(xyzt[0, 0, 3]), "aux": float(aux[0, 0]), "voxel": voxel}
+
+    def lastDepthInfo(self):
+        """What the last render_depth / pick launched (vrhip_last_depth_info): mode, work_items (8 x 8 patches),
+        empty_skip (1: the kernel stepped over samples by the cell grid) -- as a dict."""
+        di = _lib.DepthInfo()
+        self._check(self._lib.vrhip_last_depth_info(self._h, C.byref(di)))
+        return di.as_dict()
+
     # ---- volume
     def loadVolumeData(self, props, ingest="host"):
         """volumerendercl.cpp:765-805. `props` is a datraw.Properties (dat_file_name or
