@@ -210,6 +210,31 @@ public:
     // the 3-D point under pixel (x, y) of the width x height frame: renderDepth on a 1 x 1 rectangle
     pick_result pick(size_t width, size_t height, unsigned int x, unsigned int y, depth_mode mode, float threshold = 0.5f,
                      unsigned int refineSteps = 4);
+    // ---- isosurface extraction (no reference counterpart; vrhip.h "isosurface extraction"): the surface technique 4
+    // draws at `iso`, as a triangle list in box space ([-1, 1]^3), nine floats a triangle, in the contract's order.
+    // Shared vertices are bit-equal, so weldMesh turns the list into an indexed, watertight mesh.  normals: technique
+    // 4's shading normal per vertex.  region: the cubes with lo <= corner and corner + 1 <= hi, in voxels; all zero:
+    // the whole volume.  Camera, technique and frame buffer are neither read nor touched.
+    struct mesh_region {
+        std::array<unsigned int, 3> lo, hi;
+        mesh_region() : lo{{0u, 0u, 0u}}, hi{{0u, 0u, 0u}} {}
+    };
+    struct iso_mesh {
+        std::vector<float> positions, normals;   // [triangles][3][3]; normals empty unless asked for
+    };
+    iso_mesh extractIsosurface(float iso, bool normals = false, const mesh_region &region = mesh_region());
+    // unique vertices by bit-equal position, in order of first occurrence; the first occurrence keeps its normal
+    struct welded_mesh {
+        std::vector<float> vertices, normals;    // [vertices][3]
+        std::vector<uint32_t> indices;           // [triangles][3]
+    };
+    static welded_mesh weldMesh(const std::vector<float> &positions, const std::vector<float> &normals = {});
+    // binary STL: the list as it is, each facet's normal from its winding
+    static void writeStl(const std::string &path, const std::vector<float> &positions);
+    // binary_little_endian PLY of the welded mesh: x y z, nx ny nz when normals are given, uchar-counted uint index
+    // lists; returns the number of vertices written
+    static size_t writePly(const std::string &path, const std::vector<float> &positions,
+                           const std::vector<float> &normals = {});
     // ---- the progressive path tracer (technique 1), many samples per call (vrhip_render_samples): seeds.size()
     // consecutive iterations of the accumulated image -- sample k with jitter seed seeds[k] at iteration
     // (current iteration + k) -- in as few launch sets as possible, bit for bit what seeds.size() runRaycastNoGL calls

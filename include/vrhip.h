@@ -372,6 +372,81 @@ typedef struct vrhip_depth_info {
 } vrhip_depth_info;        /* 32 bytes */
 int vrhip_last_depth_info(const vrhip_renderer *r, vrhip_depth_info *out);
 
+/* ---- isosurface extraction: the surface technique 4 draws, as a triangle list (no reference counterpart; DESIGN.md
+ * "Isosurface extraction").  An entry point of its own, not a technique.  All arithmetic is fp32, every operation
+ * rounded on its own, in the order written.
+ *  Grid: the grid points are the voxel centres of channel 0 of the current time step; a point's value is
+ *   s = (float)raw * inv_max, the normalised value techniques 2 and 4 filter (FLOAT volumes: the raw value).  A point
+ *   is inside when s >= isoValue; a NaN is outside.  A cube is the eight points (x + dx, y + dy, z + dz), its corner
+ *   j = dx + 2 dy + 4 dz; a W x H x D volume has (W-1)(H-1)(D-1) cubes, an axis of length 1 gives none (zero
+ *   triangles, VRHIP_OK).  The surface is open where it leaves the volume or the region: no caps.
+ *  Tetrahedra: every cube is cut into the six tetrahedra of the Kuhn triangulation around the diagonal from corner 0
+ *   to corner 7.  Tetrahedron k = 0..5 belongs to the axis order xyz, xzy, yxz, yzx, zxy, zyx; for the order (a, b, c)
+ *   its vertices are v0 = (0,0,0), v1 = v0 + e_a, v2 = v1 + e_b, v3 = (1,1,1): the cube corners {0,1,3,7}, {0,1,5,7},
+ *   {0,2,3,7}, {0,2,6,7}, {0,4,5,7}, {0,4,6,7}.  The cut is the same in every cube and neighbouring cubes agree on
+ *   their shared faces.
+ *  Triangles of a tetrahedron, from the inside mask m = sum of (v_i inside) << i; an edge vertex is named by the two
+ *   tetrahedron vertices of its edge.  m = 0 or 15: none.  One vertex inside, or one outside: one triangle on the
+ *   three edges at that vertex.  Two inside i0 < i1 and two outside o0 < o1: the quad (i0,o0), (i0,o1), (i1,o1),
+ *   (i1,o0) as the triangles [(i0,o0), (i0,o1), (i1,o1)] and [(i0,o0), (i1,o1), (i1,o0)].  The first edge vertex of a
+ *   triangle is the one named first here (edges at a lone vertex: by ascending other vertex); the other two are
+ *   ordered so that the right-hand normal points to the outside vertices.  The table, masks 0..15 from left to right,
+ *   triangles of a mask separated by |:
+ *   xyz, yzx, zxy (tetrahedra 0, 3, 4):
+ *     -, 01 02 03, 01 13 12, 02 03 13|02 13 12, 02 12 23, 01 23 03|01 12 23, 01 13 23|01 23 02, 03 13 23,
+ *     03 23 13, 01 02 23|01 23 13, 01 23 12|01 03 23, 02 23 12, 02 12 13|02 13 03, 01 12 13, 01 03 02, -
+ *   xzy, yxz, zyx (tetrahedra 1, 2, 5; the mirror images: every triangle above with its last two vertices swapped):
+ *     -, 01 03 02, 01 12 13, 02 13 03|02 12 13, 02 23 12, 01 03 23|01 23 12, 01 23 13|01 02 23, 03 23 13,
+ *     03 13 23, 01 23 02|01 13 23, 01 12 23|01 23 03, 02 12 23, 02 13 12|02 03 13, 01 13 12, 01 02 03, -
+ *  Edge vertex: edge (i, j), i < j, runs from the grid point P = cube corner 0 + v_i to Q = cube corner 0 + v_j, so
+ *   Q - P is in {0,1}^3 and P is the end nearer corner 0.  t = (isoValue - sP) / (sQ - sP); if (!(t >= 0.f)) t = 0.f;
+ *   if (t > 1.f) t = 1.f; per axis g = (float)P + (float)(Q - P) * t and the box-space coordinate is
+ *   (g + 0.5f) / (float)res * 2.f - 1.f -- the volume is [-1, 1]^3, texture coordinate = p * 0.5 + 0.5, as for the
+ *   slice views and depth images.  A vertex depends on its edge's two points alone: every tetrahedron and cube that
+ *   shares the edge writes the same bits, so the list welds by bit-equality into a watertight mesh.  NaN and
+ *   infinite values give finite positions.  Degenerate triangles (a point equal to isoValue) are emitted like any
+ *   other: the count depends on the inside masks alone.
+ *  Normals (VRHIP_MESH_NORMALS_GRADIENT), per vertex: technique 4's shading normal at the vertex's texture coordinate
+ *   (p * 0.5f + 0.5f per axis): the six trilinear taps one texel either side of it, s2 - s1 = g, the normal
+ *   -g * (1.f / sqrtf(g . g)), whatever useLinear says.  g . g == 0 or a non-finite component: (0, 0, 0).
+ *  Order: cubes are grouped into blocks of VRHIP_MESH_BLOCK^3 cubes anchored at voxel (0,0,0) (not at lo); blocks x
+ *   fastest, cubes within a block x fastest, tetrahedra 0..5 within a cube, triangles within a tetrahedron in table
+ *   order.  The output is that list, nine floats a triangle, and nothing else; two calls give the same bytes, and a
+ *   region's list is the whole volume's with the cubes outside the region removed.
+ *  Region: the cubes with lo <= corner 0 and corner 0 + 1 <= hi per axis, in voxels; all six values 0: the whole volume.
+ *  vrhip_isosurface_count: the number of triangles.  vrhip_isosurface_extract: writes them when capacity_triangles
+ *   is at least that number; else it writes nothing, sets *n_triangles to the number needed and returns
+ *   VRHIP_ERR_INVALID.  Host destinations go through staging the renderer owns and the call returns after the copy;
+ *   with out_is_device != 0 they are device memory, 16-byte aligned, and the call returns once the count is known and
+ *   the last kernel is queued on the renderer's stream.
+ *  vrhip_set_object_ess: on, a block whose cell of the cell grid proves every point outside (fl(max * inv_max) <
+ *   isoValue) or every point inside (fl(min * inv_max) >= isoValue) is neither fetched nor classified; no output byte
+ *   changes.  vrhip_last_mesh_info: the blocks of the last call that hold a cube of the region, how many of them
+ *   were skipped so, and whether the cell grid was handed over.
+ *  State: reads the volume, the time step and the object-ESS switch -- not the camera, technique, transfer function,
+ *   seed, iteration, vrhip_iso_params or the environment map -- and writes nothing a render entry point reads later.
+ *  VRHIP_ERR_INVALID: a NULL r, p or n_triangles; normals > 1; reserved != 0; a non-finite isoValue; extract with
+ *   out_positions NULL, with out_normals set and normals == 0 or NULL and normals == 1, or with a device destination
+ *   that is not 16-byte aligned; a region that is not all zero with hi > res, lo > hi or hi == 0 on an axis.
+ *   VRHIP_ERR_UNSUPPORTED: RG / RGBA volumes.  VRHIP_ERR_NODATA: no volume; vrhip_last_mesh_info before the first call. */
+#define VRHIP_MESH_BLOCK 8u
+enum { VRHIP_MESH_NORMALS_NONE = 0, VRHIP_MESH_NORMALS_GRADIENT = 1 };
+typedef struct vrhip_mesh_params {
+    float    isoValue;      /* units of vrhip_iso_params.isoValue */
+    uint32_t normals;       /* VRHIP_MESH_NORMALS_* */
+    uint32_t lo[3], hi[3];  /* region in voxels; all six 0: the whole volume */
+    uint32_t reserved[4];   /* must be 0 */
+} vrhip_mesh_params;        /* 48 bytes */
+int vrhip_isosurface_count(vrhip_renderer *r, const vrhip_mesh_params *p, uint64_t *n_triangles);
+int vrhip_isosurface_extract(vrhip_renderer *r, const vrhip_mesh_params *p, float *out_positions,
+                             float *out_normals, uint64_t capacity_triangles, uint64_t *n_triangles,
+                             int out_is_device);
+typedef struct vrhip_mesh_info {
+    uint64_t triangles, blocks, blocks_skipped;
+    uint32_t empty_skip, reserved;
+} vrhip_mesh_info;          /* 32 bytes */
+int vrhip_last_mesh_info(const vrhip_renderer *r, vrhip_mesh_info *out);
+
 /* createEnvironmentMap (volumerendercl.cpp:1121-1150): float RGBA texels, row-major, width*height*4
  * floats (the host layer decodes the Radiance .hdr file).  The kernel samples it in place of the
  * background colour when it is wider than one texel (volumeraycast.cl:506-510, :655-656);

@@ -81,6 +81,26 @@ class DepthInfo(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
+# vrhip_mesh_params.normals (isosurface extraction, vrhip_isosurface_extract)
+MESH_NORMALS_NONE, MESH_NORMALS_GRADIENT = 0, 1
+MESH_BLOCK = 8
+
+
+class MeshParams(C.Structure):
+    """vrhip_mesh_params: the iso value, the normals wanted and the region of an isosurface extraction."""
+    _fields_ = [("isoValue", C.c_float), ("normals", C.c_uint32), ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class MeshInfo(C.Structure):
+    """vrhip_mesh_info: what the last vrhip_isosurface_count / _extract did."""
+    _fields_ = [("triangles", C.c_uint64), ("blocks", C.c_uint64), ("blocks_skipped", C.c_uint64),
+                ("empty_skip", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 class Stats(C.Structure):
     _fields_ = [("samples_taken", C.c_uint64), ("samples_nominal", C.c_uint64),
                 ("samples_shaded", C.c_uint64), ("bricks_visited", C.c_uint64),
@@ -106,6 +126,7 @@ assert C.sizeof(CameraParams) == 128 and C.sizeof(RenderingParams) == 64
 assert C.sizeof(RaycastParams) == 32 and C.sizeof(PathtraceParams) == 4 and C.sizeof(IsoParams) == 16
 assert C.sizeof(SliceParams) == 80
 assert C.sizeof(DepthParams) == 32 and C.sizeof(DepthInfo) == 32
+assert C.sizeof(MeshParams) == 48 and C.sizeof(MeshInfo) == 32
 
 _H = C.c_void_p
 _U3 = C.POINTER(C.c_uint32)
@@ -180,6 +201,10 @@ SYMBOLS = {
     "vrhip_render_depth": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(DepthParams), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int]),
     "vrhip_last_depth_info": (C.c_int, [_H, C.POINTER(DepthInfo)]),
+    "vrhip_isosurface_count": (C.c_int, [_H, C.POINTER(MeshParams), C.POINTER(C.c_uint64)]),
+    "vrhip_isosurface_extract": (C.c_int, [_H, C.POINTER(MeshParams), C.c_void_p, C.c_void_p, C.c_uint64,
+                                           C.POINTER(C.c_uint64), C.c_int]),
+    "vrhip_last_mesh_info": (C.c_int, [_H, C.POINTER(MeshInfo)]),
     "vrhip_render_tiles": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_void_p, C.c_uint32, C.c_void_p]),
     "vrhip_set_environment_map": (C.c_int, [_H, C.c_void_p, C.c_uint32, C.c_uint32]),

@@ -730,6 +730,27 @@ VolumeRenderCL::pick_result VolumeRenderCL::pick(size_t width, size_t height, un
     return res;
 }
 
+// (weldMesh, writeStl and writePly: meshio.cpp)
+VolumeRenderCL::iso_mesh VolumeRenderCL::extractIsosurface(float iso, bool normals, const mesh_region &region)
+{
+    if (!_volLoaded) throw std::runtime_error("No volume data is loaded.");
+    vrhip_mesh_params p{};
+    p.isoValue = iso;
+    p.normals = normals ? VRHIP_MESH_NORMALS_GRADIENT : VRHIP_MESH_NORMALS_NONE;
+    for (int i = 0; i < 3; ++i) { p.lo[i] = region.lo[i]; p.hi[i] = region.hi[i]; }
+    uint64_t n = 0;
+    check("extractIsosurface", vrhip_isosurface_count(_r, &p, &n));
+    iso_mesh m;
+    m.positions.resize(size_t(n) * 9);
+    if (normals) m.normals.resize(size_t(n) * 9);
+    if (n == 0) return m;
+    uint64_t got = 0;
+    check("extractIsosurface", vrhip_isosurface_extract(_r, &p, m.positions.data(), normals ? m.normals.data() : nullptr, n,
+                                                        &got, 0));
+    if (got != n) throw std::runtime_error("ERROR: extractIsosurface (the volume changed between count and extraction)");
+    return m;
+}
+
 void VolumeRenderCL::renderSlicesRGBA8(size_t width, size_t height, const std::vector<slice_params> &slices,
                                        float *dev_frames, unsigned char *out, bool outIsDevice)
 {

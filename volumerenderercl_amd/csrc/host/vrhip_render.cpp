@@ -486,6 +486,16 @@ void write_rgba8(const std::string &out, const std::vector<unsigned char> &frame
         "                                           with --pathtrace, --mip, --iso, the slice options, --ranks,\n"
         "                                           --frames-per-launch, --orbit, --camera-path, --frames, --rgba8,\n"
         "                                           --img-ess; --depth-refine and --depth-rect need --depth)\n"
+        "         [--mesh V FILE.stl|.ply] [--mesh-normals] [--mesh-region X0 Y0 Z0 X1 Y1 Z1] [--timestep T]\n"
+        "                                          (the isosurface at V as triangles instead of a rendered frame: binary\n"
+        "                                           STL, the triangle list as it is, or binary little-endian PLY, welded by\n"
+        "                                           bit-equal positions; --mesh-normals: technique 4's shading normal per\n"
+        "                                           vertex (PLY: nx ny nz); --mesh-region: the cubes between voxels\n"
+        "                                           (X0, Y0, Z0) and (X1, Y1, Z1) only; --timestep: of that time step;\n"
+        "                                           needs no --size, camera or --out; prints the triangle count, for\n"
+        "                                           .ply the vertex count too; not with a render, slice or depth option,\n"
+        "                                           --ranks, --frames, --rgba8, --downsample; --mesh-normals,\n"
+        "                                           --mesh-region and --timestep need --mesh)\n"
         "writes PREFIX.rgba.f32 (W*H*4 float32, row 0 = top), PREFIX.ppm and prints one JSON line\n";
     std::exit(2);
 }
@@ -532,6 +542,11 @@ int main(int argc, char **argv)
     double depth_threshold = 0.5;
     int depth_refine = 4;
     long depth_rect[4] = {0, 0, 0, 0};
+    // isosurface extraction (--mesh, --mesh-normals, --mesh-region, --timestep)
+    bool mesh = false, mesh_normals = false, have_mesh_region = false, have_timestep = false;
+    double mesh_iso = 0.5;
+    std::string mesh_file;
+    long mesh_region[6] = {0, 0, 0, 0, 0, 0}, timestep = 0;
 
     auto need = [&](int i, int n) { if (i + n >= argc) usage(); };
     for (int i = 1; i < argc; ++i) {
@@ -615,6 +630,10 @@ int main(int argc, char **argv)
         }
         else if (a == "--depth-refine") { need(i, 1); have_depth_refine = true; depth_refine = std::atoi(argv[++i]); }
         else if (a == "--depth-rect") { need(i, 4); for (int k = 0; k < 4; ++k) depth_rect[k] = std::atol(argv[++i]); have_depth_rect = true; }
+        else if (a == "--mesh") { need(i, 2); mesh = true; mesh_iso = std::atof(argv[++i]); mesh_file = argv[++i]; }
+        else if (a == "--mesh-normals") mesh_normals = true;
+        else if (a == "--mesh-region") { need(i, 6); for (int k = 0; k < 6; ++k) mesh_region[k] = std::atol(argv[++i]); have_mesh_region = true; }
+        else if (a == "--timestep") { need(i, 1); timestep = std::atol(argv[++i]); have_timestep = true; }
         else usage();
     }
     if (have_path_arg && (camera_path.empty() || have_orbit)) usage();
@@ -657,6 +676,21 @@ int main(int argc, char **argv)
                 depth_rect[1] + depth_rect[3] > long(H))
                 usage();
         }
+    }
+    if ((mesh_normals || have_mesh_region || have_timestep) && !mesh) usage();
+    bool mesh_ply = false;
+    if (mesh) {
+        const size_t dot = mesh_file.rfind('.');
+        const std::string ext = dot == std::string::npos ? "" : mesh_file.substr(dot);
+        if (ext != ".stl" && ext != ".ply") usage();
+        mesh_ply = ext == ".ply";
+        // triangles of the volume, not a picture of it: what selects, shapes or multiplies frames has nothing to act on
+        if (pathtrace || mip || iso || have_iso_refine || slicing || have_slab || have_stack || slice_value || depth || ranks > 0 ||
+            frames_per_launch > 0 || have_orbit || have_path_arg || frames != 1 || rgba8 || img_ess || downsample ||
+            !dump_tf.empty() || bench || independent)
+            usage();
+        if (!std::isfinite(mesh_iso) || timestep < 0) usage();
+        for (long c : mesh_region) if (c < 0 || c > 8192) usage();
     }
     if (have_orbit && (orbit_n < 1 || orbit_n > 1 << 20 ||
                        orbit_axis[0] * orbit_axis[0] + orbit_axis[1] * orbit_axis[1] + orbit_axis[2] * orbit_axis[2] == 0.0))
@@ -719,7 +753,7 @@ int main(int argc, char **argv)
             return 1;
         }
     }
-    if ((dat.empty() && synth_kind.empty()) || (out.empty() && !downsample)) usage();
+    if ((dat.empty() && synth_kind.empty()) || (out.empty() && !downsample && !mesh)) usage();
 
     try {
         // everything the front end sets on a renderer; returns false when there is no frame to render
@@ -819,6 +853,38 @@ int main(int argc, char **argv)
             return sets;
         };
 
+        if (mesh) {
+            // ---- the isosurface as a file (VolumeRenderCL::extractIsosurface): the volume, the ESS switch, nothing else
+            VolumeRenderCL vr;
+            vr.initialize(false, false, VENDOR_ANY, std::to_string(device));
+            if (!dat.empty()) {
+                DatRawReader::Properties p;
+                p.dat_file_name = dat;
+                vr.setDeviceIngest(device_ingest);
+                vr.loadVolumeData(p);
+            } else {
+                DatRawReader::data_format f = synth_fmt == "USHORT" ? DatRawReader::USHORT
+                                              : synth_fmt == "FLOAT" ? DatRawReader::FLOAT : DatRawReader::UCHAR;
+                vr.loadSyntheticVolume(synth_kind, synth_n, f);
+            }
+            vr.setObjEss(ess);
+            if (have_timestep) vr.setTimestep(size_t(timestep));
+            VolumeRenderCL::mesh_region region;
+            if (have_mesh_region)
+                for (size_t k = 0; k < 3; ++k) { region.lo[k] = unsigned(mesh_region[k]); region.hi[k] = unsigned(mesh_region[3 + k]); }
+            const VolumeRenderCL::iso_mesh m = vr.extractIsosurface(float(mesh_iso), mesh_normals, region);
+            const size_t triangles = m.positions.size() / 9;
+            if (mesh_ply) {
+                const size_t vertices = VolumeRenderCL::writePly(mesh_file, m.positions, m.normals);
+                std::printf("{\"device\": \"%s\", \"mesh\": \"%s\", \"iso\": %.9g, \"triangles\": %zu, \"vertices\": %zu}\n",
+                            vr.getCurrentDeviceName().c_str(), mesh_file.c_str(), mesh_iso, triangles, vertices);
+            } else {
+                VolumeRenderCL::writeStl(mesh_file, m.positions);
+                std::printf("{\"device\": \"%s\", \"mesh\": \"%s\", \"iso\": %.9g, \"triangles\": %zu}\n",
+                            vr.getCurrentDeviceName().c_str(), mesh_file.c_str(), mesh_iso, triangles);
+            }
+            return 0;
+        }
         if (ranks > 0) {
             // image-tile decomposition over `ranks` GPUs: one renderer per rank, every
             // one with the whole volume and the same settings; jitter seeds follow the same

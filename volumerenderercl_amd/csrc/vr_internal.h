@@ -448,6 +448,32 @@ struct DepthLaunch {
     uint8_t *out_kind;
 };
 hipError_t vr_launch_depth(const DepthLaunch &a, hipStream_t stream);
+// isosurface extraction (vrhip_isosurface_count / _extract): the blocks of 8^3 cubes b0 + (0 .. nb - 1) per axis,
+// x fastest, of which the cubes lo <= corner 0 < hi are classified (lo < hi <= res - 1, every block holds one).
+// cell_minmax: the (min, max) pairs of the cell grid of 2^cell_shift >= 8 voxels, cell_cx x cell_cy x .. cells, or
+// nullptr: every block is fetched.  vr_mesh.hip
+struct MeshLaunch {
+    VolView vol;
+    int format;            // vrhip_format
+    float iso;
+    uint32_t lo[3], hi[3];
+    uint32_t b0[3], nb[3];
+    const float2 *cell_minmax;
+    int cell_shift, cell_cx, cell_cy;
+};
+constexpr uint32_t kMeshSkipped = 0x80000000u;   // a block's count word: skipped by the cell grid (its count is 0)
+constexpr uint32_t kMeshScanChunk = 4096;        // block counts per workgroup of the scan
+inline size_t vr_mesh_scan_partials(size_t n_blocks) { return (n_blocks + kMeshScanChunk - 1) / kMeshScanChunk; }
+// pass 1: counts[n_blocks], one word per block (its triangles, or kMeshSkipped)
+hipError_t vr_launch_mesh_count(const MeshLaunch &a, uint32_t *counts, hipStream_t stream);
+// the exclusive 64-bit prefix sum of the counts, reduce-then-scan in separate launches: partials holds
+// 2 * vr_mesh_scan_partials(n_blocks) + 2 words and ends with the totals (triangles, skipped blocks); offsets
+// (n_blocks words) may be nullptr: the totals alone
+hipError_t vr_launch_mesh_scan(const uint32_t *counts, size_t n_blocks, unsigned long long *partials,
+                               unsigned long long *offsets, hipStream_t stream);
+// pass 2: every triangle to its place, nine floats each; normals may be nullptr
+hipError_t vr_launch_mesh_emit(const MeshLaunch &a, const uint32_t *counts, const unsigned long long *offsets,
+                               float *positions, float *normals, hipStream_t stream);
 // the frame launch for a.render.technique
 inline hipError_t vr_launch_frame(const RaycastLaunch &a, hipStream_t stream)
 {

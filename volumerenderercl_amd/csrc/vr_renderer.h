@@ -1,5 +1,6 @@
 // vr_renderer.h -- the host state of one renderer (vrhip_renderer, include/vrhip.h), shared by the units that
-// implement the C ABI: vrhip_api.hip, vrhip_gather.hip, vrhip_ingest_api.hip, vrhip_slice_api.hip, vrhip_depth_api.hip.  Host only.
+// implement the C ABI: vrhip_api.hip, vrhip_gather.hip, vrhip_ingest_api.hip, vrhip_slice_api.hip, vrhip_depth_api.hip,
+// vrhip_mesh_api.hip.  Host only.
 //  * DevBuf / Handle: device memory, events and the stream, freed with the object that holds them;
 //  * grow(): the one place that (re)allocates a renderer's buffer;
 //  * the invalidation functions: one per cause, next to the table of what depends on what.
@@ -229,6 +230,18 @@ struct vrhip_renderer {
     PinnedBuf depth_host;
     vrhip_depth_info depth_info;
     bool have_depth_info = false;
+
+    // isosurface extraction (vrhip_isosurface_count / _extract, vrhip_mesh_api.hip): the per-block counts, their
+    // prefix sum and its partial sums; for host destinations the triangles on the device and the pinned block they
+    // are copied through (the totals always travel through mesh_totals_host); what the last call did
+    // (vrhip_last_mesh_info).  Nothing is kept from one call to the next but the allocations: every call counts
+    // anew.  Grown on demand, freed with the renderer.  No render entry point reads them.
+    DevBuf<uint32_t> mesh_counts;
+    DevBuf<unsigned long long> mesh_offsets, mesh_partials;
+    DevBuf<float> mesh_out_dev;
+    PinnedBuf mesh_host, mesh_totals_host;
+    vrhip_mesh_info mesh_info;
+    bool have_mesh_info = false;
 
     // device-side ingest (vrhip_ingest_raw, vrhip_volume_histogram): the running maximum and the 256 64-bit
     // histogram counters in device memory, the events around its kernels (all created on first use)

@@ -386,6 +386,104 @@ def depth_grey(xyzt, kind):
     return out
 
 
+# ---- meshes (include/vrhip.h "isosurface extraction"; VolumeRenderCL.extract_isosurface)
+
+def weld_mesh(positions, normals=None):
+    """A triangle list [n, 3, 3] as an indexed mesh: (vertices float32 [m, 3], normals float32 [m, 3] or None, indices
+    uint32 [n, 3]).  Vertices are unique by bit-equal position; the first occurrence keeps its index order and its
+    normal."""
+    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+    keys = pos.view(np.uint32).reshape(-1, 3)
+    _, first, inverse = np.unique(keys, axis=0, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")          # unique vertices by first occurrence
+    rank = np.empty(order.size, dtype=np.int64)
+    rank[order] = np.arange(order.size)
+    idx = rank[np.asarray(inverse).reshape(-1)].astype(np.uint32).reshape(-1, 3)
+    sel = first[order]
+    nrm = None
+    if normals is not None:
+        nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)[sel].copy()
+    return pos[sel].copy(), nrm, idx
+
+
+def facet_normals(positions):
+    """The unit right-hand normal of every triangle of a list [n, 3, 3], float32 [n, 3]; (0, 0, 0) for a degenerate one."""
+    p = np.asarray(positions, dtype=np.float64).reshape(-1, 3, 3)
+    n = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+    ln = np.linalg.norm(n, axis=1)
+    out = np.zeros_like(n)
+    ok = ln > 0
+    out[ok] = n[ok] / ln[ok, None]
+    return out.astype(np.float32)
+
+
+def write_stl(path, positions):
+    """A triangle list [n, 3, 3] as binary STL: the soup as it is, each facet's normal from its winding."""
+    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3, 3)
+    rec = np.zeros(pos.shape[0], dtype=np.dtype([("n", "<f4", 3), ("v", "<f4", (3, 3)), ("attr", "<u2")]))
+    rec["n"] = facet_normals(pos)
+    rec["v"] = pos
+    with open(path, "wb") as f:
+        f.write(b"vrhip isosurface".ljust(80, b" "))
+        f.write(np.uint32(pos.shape[0]).astype("<u4").tobytes())
+        f.write(rec.tobytes())
+
+
+def read_stl(path):
+    """A binary STL as (facet normals float32 [n, 3], positions float32 [n, 3, 3])."""
+    raw = open(path, "rb").read()
+    n = int(np.frombuffer(raw, dtype="<u4", count=1, offset=80)[0])
+    rec = np.frombuffer(raw, dtype=np.dtype([("n", "<f4", 3), ("v", "<f4", (3, 3)), ("attr", "<u2")]), count=n, offset=84)
+    return rec["n"].copy(), rec["v"].copy()
+
+
+def write_ply(path, positions, normals=None):
+    """A triangle list as binary_little_endian PLY, welded (weld_mesh): x y z, nx ny nz when normals are given, and
+    the faces as uchar-counted lists of uint indices.  Returns (vertices, faces) written."""
+    v, nrm, idx = weld_mesh(positions, normals)
+    head = ["ply", "format binary_little_endian 1.0", "comment vrhip isosurface", "element vertex %d" % v.shape[0],
+            "property float x", "property float y", "property float z"]
+    if nrm is not None:
+        head += ["property float nx", "property float ny", "property float nz"]
+    head += ["element face %d" % idx.shape[0], "property list uchar uint vertex_indices", "end_header"]
+    vert = np.hstack([v, nrm]) if nrm is not None else v
+    face = np.zeros(idx.shape[0], dtype=np.dtype([("n", "u1"), ("i", "<u4", 3)]))
+    face["n"] = 3
+    face["i"] = idx
+    with open(path, "wb") as f:
+        f.write(("\n".join(head) + "\n").encode("ascii"))
+        f.write(np.ascontiguousarray(vert, dtype="<f4").tobytes())
+        f.write(face.tobytes())
+    return v.shape[0], idx.shape[0]
+
+
+def read_ply(path):
+    """A PLY as write_ply (or `vrhip_render --mesh`) writes it: (vertices float32 [m, 3], normals float32 [m, 3] or
+    None, indices uint32 [n, 3])."""
+    raw = open(path, "rb").read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    lines = raw[:end].decode("ascii").split("\n")
+    if lines[0] != "ply" or "format binary_little_endian 1.0" not in lines:
+        raise ValueError("read_ply: not a binary little-endian PLY")
+    nv = nf = 0
+    props = []
+    for ln in lines:
+        w = ln.split()
+        if w[:2] == ["element", "vertex"]:
+            nv = int(w[2])
+        elif w[:2] == ["element", "face"]:
+            nf = int(w[2])
+        elif w[:2] == ["property", "float"]:
+            props.append(w[2])
+    if props not in (["x", "y", "z"], ["x", "y", "z", "nx", "ny", "nz"]):
+        raise ValueError("read_ply: unexpected vertex properties %r" % (props,))
+    vert = np.frombuffer(raw, dtype="<f4", count=nv * len(props), offset=end).reshape(nv, len(props))
+    face = np.frombuffer(raw, dtype=np.dtype([("n", "u1"), ("i", "<u4", 3)]), count=nf, offset=end + vert.nbytes)
+    if nf and not np.all(face["n"] == 3):
+        raise ValueError("read_ply: not a triangle mesh")
+    return (vert[:, :3].copy(), vert[:, 3:].copy() if len(props) == 6 else None, face["i"].astype(np.uint32))
+
+
 # ---- slice views (include/vrhip.h "slice views"; VolumeRenderCL.render_slices).  The contract is the 80-byte
 # vrhip_slice_params block; the helpers below compute in float64 and store float32.
 

@@ -490,6 +490,63 @@ class VolumeRenderCL:
         self._check(self._lib.vrhip_last_depth_info(self._h, C.byref(di)))
         return di.as_dict()
 
+    # ---- isosurface extraction (no reference counterpart; include/vrhip.h "isosurface extraction")
+    @staticmethod
+    def _mesh_params(iso, normals, region):
+        p = _lib.MeshParams()
+        p.isoValue = float(iso)
+        p.normals = _lib.MESH_NORMALS_GRADIENT if normals else _lib.MESH_NORMALS_NONE
+        if region is not None:
+            lo, hi = region
+            p.lo[:] = [int(v) for v in lo]
+            p.hi[:] = [int(v) for v in hi]
+        return p
+
+    def isosurface_count(self, iso, region=None):
+        """The number of triangles of the isosurface at `iso` (units of isoValue of setIsoParams) of the current time
+        step (vrhip_isosurface_count).  region = ((x0, y0, z0), (x1, y1, z1)) in voxels: the cubes with lo <= corner
+        and corner + 1 <= hi only; None: the whole volume."""
+        p = self._mesh_params(iso, False, region)
+        n = C.c_uint64(0)
+        self._check(self._lib.vrhip_isosurface_count(self._h, C.byref(p), C.byref(n)))
+        return int(n.value)
+
+    def extract_isosurface(self, iso, normals=False, region=None, out_dev_ptrs=None):
+        """The isosurface at `iso` as a triangle list (vrhip_isosurface_extract): (positions float32 [n, 3, 3] in box
+        space -- the volume is [-1, 1]^3 --, normals float32 [n, 3, 3] or None).  The list is deterministic and
+        ordered (blocks of 8^3 cubes, cubes, tetrahedra); shared vertices are bit-equal, so frontend.weld_mesh turns it
+        into an indexed, watertight mesh.  normals: technique 4's shading normal per vertex.
+        With out_dev_ptrs = (positions, normals or None, capacity in triangles) -- device addresses, 16-byte aligned --
+        the triangles are written there and their number is returned; a capacity that is too small raises, and
+        isosurface_count tells what is needed.  The camera, the technique and the frame buffer are neither read nor
+        touched."""
+        p = self._mesh_params(iso, normals, region)
+        n = C.c_uint64(0)
+        if out_dev_ptrs is not None:
+            pos, nrm, cap = out_dev_ptrs
+            self._check(self._lib.vrhip_isosurface_extract(self._h, C.byref(p), C.c_void_p(int(pos)),
+                                                           C.c_void_p(int(nrm)) if nrm else None, int(cap), C.byref(n), 1))
+            return int(n.value)
+        self._check(self._lib.vrhip_isosurface_count(self._h, C.byref(p), C.byref(n)))
+        count = int(n.value)
+        pos = np.empty((count, 3, 3), dtype=np.float32)
+        nrm = np.empty((count, 3, 3), dtype=np.float32) if normals else None
+        if count:
+            self._check(self._lib.vrhip_isosurface_extract(
+                self._h, C.byref(p), pos.ctypes.data_as(C.c_void_p),
+                nrm.ctypes.data_as(C.c_void_p) if normals else None, count, C.byref(n), 0))
+            if int(n.value) != count:
+                raise RuntimeError("extract_isosurface: the volume changed between the count and the extraction")
+        return pos, nrm
+
+    def lastMeshInfo(self):
+        """What the last isosurface_count / extract_isosurface did (vrhip_last_mesh_info): triangles, blocks (of 8^3
+        cubes that hold a cube of the region), blocks_skipped (by the cell grid, object-order ESS on), empty_skip (1:
+        the cell grid was handed to the kernel) -- as a dict."""
+        mi = _lib.MeshInfo()
+        self._check(self._lib.vrhip_last_mesh_info(self._h, C.byref(mi)))
+        return mi.as_dict()
+
     # ---- volume
     def loadVolumeData(self, props, ingest="host"):
         """volumerendercl.cpp:765-805. `props` is a datraw.Properties (dat_file_name or
