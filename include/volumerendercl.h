@@ -235,6 +235,12 @@ public:
     // lists; returns the number of vertices written
     static size_t writePly(const std::string &path, const std::vector<float> &positions,
                            const std::vector<float> &normals = {});
+    // ... of an indexed mesh as it is
+    static size_t writePly(const std::string &path, const welded_mesh &mesh);
+    // the same surface as an indexed mesh made on the device (vrhip.h "indexed isosurface extraction"): one vertex
+    // per crossed lattice edge, vertices[indices] = extractIsosurface's list bit for bit.  Where a grid point equals
+    // `iso` several vertices share a position, which weldMesh would merge; no host weld happens here.
+    welded_mesh extractIsosurfaceIndexed(float iso, bool normals = false, const mesh_region &region = mesh_region());
     // ---- the progressive path tracer (technique 1), many samples per call (vrhip_render_samples): seeds.size()
     // consecutive iterations of the accumulated image -- sample k with jitter seed seeds[k] at iteration
     // (current iteration + k) -- in as few launch sets as possible, bit for bit what seeds.size() runRaycastNoGL calls

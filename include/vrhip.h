@@ -447,6 +447,60 @@ typedef struct vrhip_mesh_info {
 } vrhip_mesh_info;          /* 32 bytes */
 int vrhip_last_mesh_info(const vrhip_renderer *r, vrhip_mesh_info *out);
 
+/* ---- indexed isosurface extraction: the same surface as unique vertices and an index list (DESIGN.md "Indexed
+ * isosurface extraction").  vrhip_mesh_params means what it means above -- grid, inside test, tetrahedra, table, edge
+ * vertex, normals, region, skipping -- and is checked and refused as there.  fp32, every operation rounded on its own.
+ *  Edges: the lattice edges are (P, d), P a grid point and d = dx + 2 dy + 4 dz in 1..7, from P to Q = P + (dx, dy, dz),
+ *   Q a point of the volume: exactly the edges of the Kuhn tetrahedra (any two cube corners u, v with u's bits among
+ *   v's are an edge of some tetrahedron of that cube), P the end nearer corner 0 as in the edge vertex formula.
+ *  Eligible: edge (P, d) is eligible when a cube of the effective region contains it.  The effective region is lo, hi
+ *   of the calls above after hi = min(hi, res - 1); on an axis whose bit of d is set lo <= P < hi, on one whose bit
+ *   is clear lo <= P <= hi.  A region that holds no cube has no eligible edge.
+ *  Crossed: inside(P) != inside(Q), inside being s >= isoValue (a NaN is outside).
+ *  Vertices: one per eligible crossed edge and nothing else; its position is the edge vertex formula on (P, Q), its
+ *   normal the normals formula at that position.  Identity is the edge, not the float: two edges whose positions are
+ *   bit-equal (a grid point equal to isoValue: t = 0 on all of its edges) stay two vertices, where a weld by
+ *   bit-equality makes them one.
+ *  Vertex order: ascending by the owning point P's block -- blocks of VRHIP_MESH_BLOCK^3 grid points anchored at voxel
+ *   (0,0,0), x fastest; per axis there may be one more of them than of the cube blocks (9 points: one cube block, two
+ *   point blocks) --, then by the point within the block, x fastest, then by d.
+ *  Triangles: the list of vrhip_isosurface_extract, in its order, each triangle's three vertices in its order, each
+ *   entry the number of the vertex of the edge that vertex lies on.  out_vertices[out_indices] is that call's
+ *   out_positions byte for byte, out_normals[out_indices] its out_normals, and *n_triangles is vrhip_isosurface_count's.
+ *  vrhip_isosurface_count_indexed: both numbers.  vrhip_isosurface_extract_indexed: writes three floats a vertex
+ *   (and a normal), three 32-bit words a triangle, when both capacities suffice; else it writes nothing to any
+ *   destination, sets both counts to the numbers needed and returns VRHIP_ERR_INVALID.  More than 2^32 - 1 vertices:
+ *   VRHIP_ERR_UNSUPPORTED from the extraction, the counts set, nothing written.  Host destinations go through
+ *   staging the renderer owns and the call returns after the copy; with out_is_device != 0 all of them are device
+ *   memory, 16-byte aligned, and the call returns once the counts are known and the last kernel is queued on the
+ *   renderer's stream.
+ *  vrhip_set_object_ess: on, a point block whose cell of the cell grid proves its points 8 b .. 8 b + 8 all outside or
+ *   all inside -- the test and the argument of a cube block, which covers those nine points per axis -- is neither
+ *   fetched nor classified; cube blocks are skipped as above; no output byte changes.
+ *  vrhip_last_indexed_mesh_info: the last indexed call's counts; the point blocks that own an eligible edge and how
+ *   many of them were skipped; the cube blocks as vrhip_mesh_info; scratch_bytes, the device memory an extraction of
+ *   that surface holds beyond the destinations (for a count: what the count held; the staging of host destinations
+ *   is not in it); whether the cell grid was handed over.
+ *  State: two calls give the same bytes.  Reads what the calls above read; writes nothing a render entry point, a
+ *   slice, a depth call or vrhip_last_mesh_info reads later.
+ *  VRHIP_ERR_INVALID: as above, n_vertices and out_vertices / out_indices in the places of n_triangles and
+ *   out_positions.  VRHIP_ERR_UNSUPPORTED: RG / RGBA volumes.  VRHIP_ERR_NODATA: no volume;
+ *   vrhip_last_indexed_mesh_info before the first indexed call. */
+int vrhip_isosurface_count_indexed(vrhip_renderer *r, const vrhip_mesh_params *p, uint64_t *n_vertices,
+                                   uint64_t *n_triangles);
+int vrhip_isosurface_extract_indexed(vrhip_renderer *r, const vrhip_mesh_params *p, float *out_vertices,
+                                     float *out_normals, uint32_t *out_indices, uint64_t capacity_vertices,
+                                     uint64_t capacity_triangles, uint64_t *n_vertices, uint64_t *n_triangles,
+                                     int out_is_device);
+typedef struct vrhip_indexed_mesh_info {
+    uint64_t vertices, triangles;
+    uint64_t point_blocks, point_blocks_skipped;
+    uint64_t blocks, blocks_skipped;
+    uint64_t scratch_bytes;
+    uint32_t empty_skip, reserved;
+} vrhip_indexed_mesh_info;  /* 64 bytes */
+int vrhip_last_indexed_mesh_info(const vrhip_renderer *r, vrhip_indexed_mesh_info *out);
+
 /* createEnvironmentMap (volumerendercl.cpp:1121-1150): float RGBA texels, row-major, width*height*4
  * floats (the host layer decodes the Radiance .hdr file).  The kernel samples it in place of the
  * background colour when it is wider than one texel (volumeraycast.cl:506-510, :655-656);

@@ -3,10 +3,10 @@ ray-cast hot path of vbruder/VolumeRendererCL, behind the reference's VolumeRend
 interface.  The product is `libvrhip.so` (csrc/, C ABI in include/vrhip.h); this package is
 the thin host-side mirror used by tests, bench.py and the multi-GPU tile driver."""
 from . import _lib, frontend
-from ._lib import (CameraParams, DepthInfo, DepthParams, IsoParams, MeshInfo, MeshParams, PathtraceParams, RaycastParams, RenderingParams, SliceParams, Stats,
+from ._lib import (CameraParams, DepthInfo, DepthParams, IndexedMeshInfo, IsoParams, MeshInfo, MeshParams, PathtraceParams, RaycastParams, RenderingParams, SliceParams, Stats,
                    UCHAR, USHORT, FLOAT, TECH_RAYCAST, TECH_PATHTRACE, TECH_MIP, TECH_ISO)
 from .renderer import VolumeRenderCL
 
 __all__ = ["VolumeRenderCL", "frontend", "_lib", "CameraParams", "RenderingParams",
-           "RaycastParams", "PathtraceParams", "IsoParams", "SliceParams", "DepthParams", "DepthInfo", "MeshParams", "MeshInfo", "Stats", "UCHAR", "USHORT", "FLOAT",
+           "RaycastParams", "PathtraceParams", "IsoParams", "SliceParams", "DepthParams", "DepthInfo", "MeshParams", "MeshInfo", "IndexedMeshInfo", "Stats", "UCHAR", "USHORT", "FLOAT",
            "TECH_RAYCAST", "TECH_PATHTRACE", "TECH_MIP", "TECH_ISO"]

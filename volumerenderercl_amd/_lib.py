@@ -101,6 +101,16 @@ class MeshInfo(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
+class IndexedMeshInfo(C.Structure):
+    """vrhip_indexed_mesh_info: what the last vrhip_isosurface_count_indexed / _extract_indexed did."""
+    _fields_ = [("vertices", C.c_uint64), ("triangles", C.c_uint64), ("point_blocks", C.c_uint64),
+                ("point_blocks_skipped", C.c_uint64), ("blocks", C.c_uint64), ("blocks_skipped", C.c_uint64),
+                ("scratch_bytes", C.c_uint64), ("empty_skip", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 class Stats(C.Structure):
     _fields_ = [("samples_taken", C.c_uint64), ("samples_nominal", C.c_uint64),
                 ("samples_shaded", C.c_uint64), ("bricks_visited", C.c_uint64),
@@ -126,7 +136,7 @@ assert C.sizeof(CameraParams) == 128 and C.sizeof(RenderingParams) == 64
 assert C.sizeof(RaycastParams) == 32 and C.sizeof(PathtraceParams) == 4 and C.sizeof(IsoParams) == 16
 assert C.sizeof(SliceParams) == 80
 assert C.sizeof(DepthParams) == 32 and C.sizeof(DepthInfo) == 32
-assert C.sizeof(MeshParams) == 48 and C.sizeof(MeshInfo) == 32
+assert C.sizeof(MeshParams) == 48 and C.sizeof(MeshInfo) == 32 and C.sizeof(IndexedMeshInfo) == 64
 
 _H = C.c_void_p
 _U3 = C.POINTER(C.c_uint32)
@@ -205,6 +215,10 @@ SYMBOLS = {
     "vrhip_isosurface_extract": (C.c_int, [_H, C.POINTER(MeshParams), C.c_void_p, C.c_void_p, C.c_uint64,
                                            C.POINTER(C.c_uint64), C.c_int]),
     "vrhip_last_mesh_info": (C.c_int, [_H, C.POINTER(MeshInfo)]),
+    "vrhip_isosurface_count_indexed": (C.c_int, [_H, C.POINTER(MeshParams), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "vrhip_isosurface_extract_indexed": (C.c_int, [_H, C.POINTER(MeshParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                   C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
+    "vrhip_last_indexed_mesh_info": (C.c_int, [_H, C.POINTER(IndexedMeshInfo)]),
     "vrhip_render_tiles": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_void_p, C.c_uint32, C.c_void_p]),
     "vrhip_set_environment_map": (C.c_int, [_H, C.c_void_p, C.c_uint32, C.c_uint32]),

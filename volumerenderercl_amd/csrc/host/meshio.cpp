@@ -99,17 +99,25 @@ void VolumeRenderCL::writeStl(const std::string &path, const std::vector<float> 
 
 size_t VolumeRenderCL::writePly(const std::string &path, const std::vector<float> &positions, const std::vector<float> &normals)
 {
-    const welded_mesh m = weldMesh(positions, normals);
+    return writePly(path, weldMesh(positions, normals));
+}
+
+size_t VolumeRenderCL::writePly(const std::string &path, const welded_mesh &m)
+{
+    if (m.vertices.size() % 3 != 0 || m.indices.size() % 3 != 0 || (!m.normals.empty() && m.normals.size() != m.vertices.size()))
+        throw std::invalid_argument("an indexed mesh holds three floats a vertex and three indices a triangle");
     const size_t nv = m.vertices.size() / 3, nf = m.indices.size() / 3;
+    for (uint32_t i : m.indices)
+        if (i >= nv) throw std::invalid_argument("writePly: an index names no vertex");
     std::ofstream f(path, std::ios::binary);
     if (!f) throw std::runtime_error("ERROR: cannot write " + path);
     f << "ply\nformat binary_little_endian 1.0\ncomment vrhip isosurface\nelement vertex " << nv
       << "\nproperty float x\nproperty float y\nproperty float z\n";
-    if (!normals.empty()) f << "property float nx\nproperty float ny\nproperty float nz\n";
+    if (!m.normals.empty()) f << "property float nx\nproperty float ny\nproperty float nz\n";
     f << "element face " << nf << "\nproperty list uchar uint vertex_indices\nend_header\n";
     for (size_t v = 0; v < nv; ++v) {
         for (int i = 0; i < 3; ++i) put_f32(f, m.vertices[3 * v + i]);
-        if (!normals.empty())
+        if (!m.normals.empty())
             for (int i = 0; i < 3; ++i) put_f32(f, m.normals[3 * v + i]);
     }
     for (size_t t = 0; t < nf; ++t) {

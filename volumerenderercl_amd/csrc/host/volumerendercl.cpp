@@ -751,6 +751,28 @@ VolumeRenderCL::iso_mesh VolumeRenderCL::extractIsosurface(float iso, bool norma
     return m;
 }
 
+VolumeRenderCL::welded_mesh VolumeRenderCL::extractIsosurfaceIndexed(float iso, bool normals, const mesh_region &region)
+{
+    if (!_volLoaded) throw std::runtime_error("No volume data is loaded.");
+    vrhip_mesh_params p{};
+    p.isoValue = iso;
+    p.normals = normals ? VRHIP_MESH_NORMALS_GRADIENT : VRHIP_MESH_NORMALS_NONE;
+    for (int i = 0; i < 3; ++i) { p.lo[i] = region.lo[i]; p.hi[i] = region.hi[i]; }
+    uint64_t nv = 0, nt = 0;
+    check("extractIsosurfaceIndexed", vrhip_isosurface_count_indexed(_r, &p, &nv, &nt));
+    welded_mesh m;
+    m.vertices.resize(size_t(nv) * 3);
+    if (normals) m.normals.resize(size_t(nv) * 3);
+    m.indices.resize(size_t(nt) * 3);
+    if (nt == 0) return m;
+    uint64_t got_v = 0, got_t = 0;
+    check("extractIsosurfaceIndexed", vrhip_isosurface_extract_indexed(_r, &p, m.vertices.data(), normals ? m.normals.data() : nullptr,
+                                                                       m.indices.data(), nv, nt, &got_v, &got_t, 0));
+    if (got_v != nv || got_t != nt)
+        throw std::runtime_error("ERROR: extractIsosurfaceIndexed (the volume changed between count and extraction)");
+    return m;
+}
+
 void VolumeRenderCL::renderSlicesRGBA8(size_t width, size_t height, const std::vector<slice_params> &slices,
                                        float *dev_frames, unsigned char *out, bool outIsDevice)
 {

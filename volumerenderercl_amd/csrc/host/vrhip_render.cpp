@@ -487,6 +487,7 @@ void write_rgba8(const std::string &out, const std::vector<unsigned char> &frame
         "                                           --frames-per-launch, --orbit, --camera-path, --frames, --rgba8,\n"
         "                                           --img-ess; --depth-refine and --depth-rect need --depth)\n"
         "         [--mesh V FILE.stl|.ply] [--mesh-normals] [--mesh-region X0 Y0 Z0 X1 Y1 Z1] [--timestep T]\n"
+        "         [--mesh-indexed]\n"
         "                                          (the isosurface at V as triangles instead of a rendered frame: binary\n"
         "                                           STL, the triangle list as it is, or binary little-endian PLY, welded by\n"
         "                                           bit-equal positions; --mesh-normals: technique 4's shading normal per\n"
@@ -495,7 +496,9 @@ void write_rgba8(const std::string &out, const std::vector<unsigned char> &frame
         "                                           needs no --size, camera or --out; prints the triangle count, for\n"
         "                                           .ply the vertex count too; not with a render, slice or depth option,\n"
         "                                           --ranks, --frames, --rgba8, --downsample; --mesh-normals,\n"
-        "                                           --mesh-region and --timestep need --mesh)\n"
+        "                                           --mesh-region and --timestep need --mesh; --mesh-indexed, with a\n"
+        "                                           .ply only: the indexed mesh as the device makes it, one vertex per\n"
+        "                                           crossed lattice edge, no weld on the host)\n"
         "writes PREFIX.rgba.f32 (W*H*4 float32, row 0 = top), PREFIX.ppm and prints one JSON line\n";
     std::exit(2);
 }
@@ -543,7 +546,7 @@ int main(int argc, char **argv)
     int depth_refine = 4;
     long depth_rect[4] = {0, 0, 0, 0};
     // isosurface extraction (--mesh, --mesh-normals, --mesh-region, --timestep)
-    bool mesh = false, mesh_normals = false, have_mesh_region = false, have_timestep = false;
+    bool mesh = false, mesh_normals = false, have_mesh_region = false, have_timestep = false, mesh_indexed = false;
     double mesh_iso = 0.5;
     std::string mesh_file;
     long mesh_region[6] = {0, 0, 0, 0, 0, 0}, timestep = 0;
@@ -632,6 +635,7 @@ int main(int argc, char **argv)
         else if (a == "--depth-rect") { need(i, 4); for (int k = 0; k < 4; ++k) depth_rect[k] = std::atol(argv[++i]); have_depth_rect = true; }
         else if (a == "--mesh") { need(i, 2); mesh = true; mesh_iso = std::atof(argv[++i]); mesh_file = argv[++i]; }
         else if (a == "--mesh-normals") mesh_normals = true;
+        else if (a == "--mesh-indexed") mesh_indexed = true;
         else if (a == "--mesh-region") { need(i, 6); for (int k = 0; k < 6; ++k) mesh_region[k] = std::atol(argv[++i]); have_mesh_region = true; }
         else if (a == "--timestep") { need(i, 1); timestep = std::atol(argv[++i]); have_timestep = true; }
         else usage();
@@ -677,13 +681,14 @@ int main(int argc, char **argv)
                 usage();
         }
     }
-    if ((mesh_normals || have_mesh_region || have_timestep) && !mesh) usage();
+    if ((mesh_normals || have_mesh_region || have_timestep || mesh_indexed) && !mesh) usage();
     bool mesh_ply = false;
     if (mesh) {
         const size_t dot = mesh_file.rfind('.');
         const std::string ext = dot == std::string::npos ? "" : mesh_file.substr(dot);
         if (ext != ".stl" && ext != ".ply") usage();
         mesh_ply = ext == ".ply";
+        if (mesh_indexed && !mesh_ply) usage();   // (STL is a triangle list)
         // triangles of the volume, not a picture of it: what selects, shapes or multiplies frames has nothing to act on
         if (pathtrace || mip || iso || have_iso_refine || slicing || have_slab || have_stack || slice_value || depth || ranks > 0 ||
             frames_per_launch > 0 || have_orbit || have_path_arg || frames != 1 || rgba8 || img_ess || downsample ||
@@ -872,6 +877,14 @@ int main(int argc, char **argv)
             VolumeRenderCL::mesh_region region;
             if (have_mesh_region)
                 for (size_t k = 0; k < 3; ++k) { region.lo[k] = unsigned(mesh_region[k]); region.hi[k] = unsigned(mesh_region[3 + k]); }
+            if (mesh_indexed) {
+                const VolumeRenderCL::welded_mesh im = vr.extractIsosurfaceIndexed(float(mesh_iso), mesh_normals, region);
+                const size_t vertices = VolumeRenderCL::writePly(mesh_file, im);
+                std::printf("{\"device\": \"%s\", \"mesh\": \"%s\", \"iso\": %.9g, \"triangles\": %zu, \"vertices\": %zu, "
+                            "\"indexed\": true}\n",
+                            vr.getCurrentDeviceName().c_str(), mesh_file.c_str(), mesh_iso, im.indices.size() / 3, vertices);
+                return 0;
+            }
             const VolumeRenderCL::iso_mesh m = vr.extractIsosurface(float(mesh_iso), mesh_normals, region);
             const size_t triangles = m.positions.size() / 9;
             if (mesh_ply) {

@@ -474,6 +474,27 @@ hipError_t vr_launch_mesh_scan(const uint32_t *counts, size_t n_blocks, unsigned
 // pass 2: every triangle to its place, nine floats each; normals may be nullptr
 hipError_t vr_launch_mesh_emit(const MeshLaunch &a, const uint32_t *counts, const unsigned long long *offsets,
                                float *positions, float *normals, hipStream_t stream);
+// the indexed extraction (vrhip_isosurface_count_indexed / _extract_indexed): the blocks of 8^3 grid points
+// b0 + (0 .. pnb - 1) per axis, x fastest, that own a point lo <= P <= hi of the launch
+inline void vr_mesh_point_blocks(const MeshLaunch &a, uint32_t pnb[3])
+{
+    for (int i = 0; i < 3; ++i) pnb[i] = a.hi[i] / VRHIP_MESH_BLOCK - a.b0[i] + 1u;
+}
+// the rank table of a point block that holds a vertex: per row of eight points (row = y + 8 z) the points' 7-bit
+// edge masks as the bytes of a 64-bit word, x ascending, and the number of the row's first vertex
+constexpr uint32_t kMeshTableRows = 64;
+constexpr size_t kMeshTableBytes = kMeshTableRows * (sizeof(unsigned long long) + sizeof(uint32_t));   // 768
+// vcounts[n_point_blocks]: a block's vertices, or kMeshSkipped; vflags: 1 where it holds a vertex, else 0
+hipError_t vr_launch_mesh_vertex_count(const MeshLaunch &a, uint32_t *vcounts, uint32_t *vflags, hipStream_t stream);
+// every vertex to its place (voffsets: the scan of vcounts), three floats each, normals may be nullptr; the table
+// of a block that holds a vertex to its slot (slots: the scan of vflags) in row_masks / row_bases
+hipError_t vr_launch_mesh_vertex_emit(const MeshLaunch &a, const uint32_t *vcounts, const unsigned long long *voffsets,
+                                      const unsigned long long *slots, float *vertices, float *normals,
+                                      unsigned long long *row_masks, uint32_t *row_bases, hipStream_t stream);
+// pass 2's triangles (counts, offsets: pass 1's and their scan) as three vertex numbers each
+hipError_t vr_launch_mesh_index_emit(const MeshLaunch &a, const uint32_t *counts, const unsigned long long *offsets,
+                                     const unsigned long long *slots, const unsigned long long *row_masks,
+                                     const uint32_t *row_bases, uint32_t *indices, hipStream_t stream);
 // the frame launch for a.render.technique
 inline hipError_t vr_launch_frame(const RaycastLaunch &a, hipStream_t stream)
 {

@@ -1,6 +1,8 @@
 // vr_mesh.hip -- isosurface extraction (vrhip_isosurface_count / vrhip_isosurface_extract, include/vrhip.h
 // "isosurface extraction"): the count and emit kernels, instantiated per voxel type, the three kernels of the prefix
 // sum between them, and their launch entries.  Not a technique: it writes buffers of its own and the caller's.
+// Behind them the kernels of the indexed extraction (vrhip_isosurface_extract_indexed), which share the staging,
+// the table and the scan: see "the indexed extraction" below.
 //
 // Definition (tests/ref/mesh_ref.c restates it on the CPU): the volume's cubes, each cut into the six
 // Kuhn tetrahedra, each tetrahedron's zero, one or two triangles from its inside mask by the table below (the
@@ -320,6 +322,199 @@ __global__ __launch_bounds__(kScanThreads) void vr_mesh_scan_apply_kernel(const 
         }
 }
 
+// ---- the indexed extraction (vrhip_isosurface_count_indexed / _extract_indexed): one vertex per
+// eligible crossed lattice edge (P, d), numbered by point block, point and d, and the soup's triangles as indices.
+// One wave per block of 8^3 grid points, which owns the edges that start at them; all seven reach no further than
+// the 9^3 points mesh_stage_block stages.
+//  * vr_mesh_vertex_count_kernel: the cell test of pass 1 (the cell answers for the very points 8 b .. 8 b + 8), then
+//    lane (x, y) walks z and sums the popcounts of its points' edge masks; the block's count word and a word that
+//    says whether it holds a vertex.  Both are scanned by vr_mesh_scan_*: a vertex offset and a table slot per block.
+//  * vr_mesh_vertex_emit_kernel: the layer loop of pass 2 over points; every vertex (and normal) is written once.
+//    A block that holds a vertex also leaves its rank table at its slot: per row of eight points (row = y + 8 z)
+//    the eight 7-bit masks as the bytes of one 64-bit word and the number of the row's first vertex, 32 bits,
+//    the block's offset included: kMeshTableBytes = 64 * (8 + 4) = 768 bytes a block.
+//  * vr_mesh_index_emit_kernel: pass 2 once more, with its counts and offsets, so every triangle lands at the soup's
+//    place; a triangle vertex on (P, d) is row base + popcount(row masks below bit 8 x + d - 1) of P's block and row.
+
+// the eligible crossed edges that start at point (lx, ly, lz) of the staged block: bit d - 1 for edge d = dx + 2 dy + 4 dz
+VR_DEV uint32_t mesh_point_edges(const MeshArgs &a, const float *s_val, uint32_t bx, uint32_t by, uint32_t bz, uint32_t lx,
+                                 uint32_t ly, uint32_t lz)
+{
+    const uint32_t g[3] = {bx * kMB + lx, by * kMB + ly, bz * kMB + lz};
+    uint32_t closed = 0, open = 0;   // per axis: lo <= P <= hi, lo <= P < hi
+#pragma unroll
+    for (uint32_t ax = 0; ax < 3u; ++ax) {
+        closed |= (g[ax] >= a.lo[ax] && g[ax] <= a.hi[ax] ? 1u : 0u) << ax;
+        open |= (g[ax] >= a.lo[ax] && g[ax] < a.hi[ax] ? 1u : 0u) << ax;
+    }
+    if (closed != 7u) return 0u;
+    const float *c0 = s_val + (lx + kMP * (ly + kMP * lz));
+    const bool in0 = c0[0] >= a.iso;
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t d = 1; d < 8u; ++d)
+        m |= ((d & ~open) == 0u && (c0[mesh_point_offset(d)] >= a.iso) != in0 ? 1u : 0u) << (d - 1u);
+    return m;
+}
+
+template <typename VT>
+__global__ __launch_bounds__(64) void vr_mesh_vertex_count_kernel(VolView vv, MeshArgs a, const float2 *__restrict__ cell_mm,
+                                                                  uint32_t *__restrict__ vcounts, uint32_t *__restrict__ vflags)
+{
+    __shared__ float s_val[kMeshPoints];
+    uint32_t bx, by, bz;
+    mesh_block_of(a, bx, by, bz);
+    // the one block of the launch that owns no eligible edge -- its only point of the region is (hi, hi, hi) -- is
+    // not one of the contract's point blocks: no vertex, and not skipped either
+    if (bx * kMB == a.hi[0] && by * kMB == a.hi[1] && bz * kMB == a.hi[2]) {   // (uniform)
+        if (threadIdx.x == 0) vcounts[blockIdx.x] = vflags[blockIdx.x] = 0u;
+        return;
+    }
+    if (cell_mm) {   // (uniform: one block, one cell)
+        const uint32_t cx = (bx * kMB) >> a.cell_shift, cy = (by * kMB) >> a.cell_shift, cz = (bz * kMB) >> a.cell_shift;
+        const float2 mm = cell_mm[((size_t)cz * (uint32_t)a.cell_cy + cy) * (uint32_t)a.cell_cx + cx];
+        if (mm.y * vv.inv_max < a.iso || mm.x * vv.inv_max >= a.iso) {
+            if (threadIdx.x == 0) {
+                vcounts[blockIdx.x] = kMeshSkipped;
+                vflags[blockIdx.x] = 0u;
+            }
+            return;
+        }
+    }
+    const Vol<VT, 0, false> vol = make_vol<VT, 0, false>(vv, nullptr);
+    mesh_stage_block(vol, bx, by, bz, s_val);
+    const uint32_t lx = threadIdx.x & 7u, ly = threadIdx.x >> 3;
+    uint32_t n = 0;
+#pragma unroll 1
+    for (uint32_t lz = 0; lz < kMB; ++lz) n += (uint32_t)__popc(mesh_point_edges(a, s_val, bx, by, bz, lx, ly, lz));
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_down(n, off, 64);
+    if (threadIdx.x == 0) {
+        vcounts[blockIdx.x] = n;
+        vflags[blockIdx.x] = n != 0u ? 1u : 0u;
+    }
+}
+
+template <typename VT, bool NORMALS>
+__global__ __launch_bounds__(64) void vr_mesh_vertex_emit_kernel(VolView vv, MeshArgs a, const uint32_t *__restrict__ vcounts,
+                                                                 const unsigned long long *__restrict__ voffsets,
+                                                                 const unsigned long long *__restrict__ slots,
+                                                                 float *__restrict__ vertices, float *__restrict__ normals,
+                                                                 unsigned long long *__restrict__ row_masks,
+                                                                 uint32_t *__restrict__ row_bases)
+{
+    __shared__ float s_val[kMeshPoints];
+    const uint32_t cw = vcounts[blockIdx.x];
+    if (cw == 0u || cw == kMeshSkipped) return;   // (uniform)
+    uint32_t bx, by, bz;
+    mesh_block_of(a, bx, by, bz);
+    const Vol<VT, 0, false> vol = make_vol<VT, 0, false>(vv, nullptr);
+    mesh_stage_block(vol, bx, by, bz, s_val);
+    const uint32_t lane = threadIdx.x, lx = lane & 7u, ly = lane >> 3;
+    const float res[3] = {vol.fw, vol.fh, vol.fd};
+    const size_t table = (size_t)slots[blockIdx.x] * kMeshTableRows;
+    uint8_t *mask_bytes = reinterpret_cast<uint8_t *>(row_masks + table);   // byte x of row y + 8 z: at 64 z + lane
+    uint32_t layer_base = (uint32_t)voffsets[blockIdx.x];   // (the host refuses more than 2^32 - 1 vertices)
+#pragma unroll 1
+    for (uint32_t lz = 0; lz < kMB; ++lz) {
+        const uint32_t m = mesh_point_edges(a, s_val, bx, by, bz, lx, ly, lz);
+        const uint32_t n = (uint32_t)__popc(m);
+        uint32_t incl = n;   // the layer's inclusive sum over the lanes: lane = x + 8 y is the points' order
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t below = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += below;
+        }
+        uint32_t vtx = layer_base + (incl - n);
+        layer_base += __shfl(incl, 63, 64);
+        mask_bytes[64u * lz + lane] = (uint8_t)m;
+        if (lx == 0u) row_bases[table + ly + kMB * lz] = vtx;
+        if (m != 0u) {   // (the shuffles above are the whole wave's)
+            const float *c0 = s_val + (lx + kMP * (ly + kMP * lz));
+            const uint32_t p0[3] = {bx * kMB + lx, by * kMB + ly, bz * kMB + lz};
+            const float sp = c0[0];
+#pragma unroll 1
+            for (uint32_t rest = m; rest != 0u; rest &= rest - 1u, ++vtx) {
+                const uint32_t d = (uint32_t)__ffs((int)rest);   // (bit d - 1)
+                const float sq = c0[mesh_point_offset(d)];
+                float t = (a.iso - sp) / (sq - sp);
+                if (!(t >= 0.f)) t = 0.f;
+                if (t > 1.f) t = 1.f;
+                float p[3];
+#pragma unroll
+                for (uint32_t ax = 0; ax < 3u; ++ax) {
+                    const float g = (float)p0[ax] + (float)((d >> ax) & 1u) * t;
+                    p[ax] = (g + 0.5f) / res[ax] * 2.f - 1.f;
+                }
+                const size_t o = (size_t)vtx * 3u;
+                vertices[o] = p[0];
+                vertices[o + 1] = p[1];
+                vertices[o + 2] = p[2];
+                if constexpr (NORMALS) {
+                    const f3 nrm = mesh_normal(vol, p[0] * 0.5f + 0.5f, p[1] * 0.5f + 0.5f, p[2] * 0.5f + 0.5f);
+                    normals[o] = nrm.x;
+                    normals[o + 1] = nrm.y;
+                    normals[o + 2] = nrm.z;
+                }
+            }
+        }
+    }
+}
+
+// pnx, pny: the point blocks per row and column of the launch (the grid of slots)
+template <typename VT>
+__global__ __launch_bounds__(64) void vr_mesh_index_emit_kernel(VolView vv, MeshArgs a, uint32_t pnx, uint32_t pny,
+                                                                const uint32_t *__restrict__ counts,
+                                                                const unsigned long long *__restrict__ offsets,
+                                                                const unsigned long long *__restrict__ slots,
+                                                                const unsigned long long *__restrict__ row_masks,
+                                                                const uint32_t *__restrict__ row_bases,
+                                                                uint32_t *__restrict__ indices)
+{
+    __shared__ float s_val[kMeshPoints];
+    const uint32_t cw = counts[blockIdx.x];
+    if (cw == 0u || cw == kMeshSkipped) return;   // (uniform)
+    uint32_t bx, by, bz;
+    mesh_block_of(a, bx, by, bz);
+    const Vol<VT, 0, false> vol = make_vol<VT, 0, false>(vv, nullptr);
+    mesh_stage_block(vol, bx, by, bz, s_val);
+    const uint32_t lane = threadIdx.x, lx = lane & 7u, ly = lane >> 3;
+    unsigned long long layer_base = offsets[blockIdx.x];
+#pragma unroll 1
+    for (uint32_t lz = 0; lz < kMB; ++lz) {
+        const uint32_t cm = mesh_cube_mask(a, s_val, bx, by, bz, lx, ly, lz);
+        const uint32_t n = mesh_cube_count(cm);
+        uint32_t incl = n;   // as pass 2
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t below = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += below;
+        }
+        unsigned long long tri = layer_base + (unsigned long long)(incl - n);
+        layer_base += (unsigned long long)__shfl(incl, 63, 64);
+        if (n != 0u) {
+            const uint32_t corner0[3] = {bx * kMB + lx, by * kMB + ly, bz * kMB + lz};
+#pragma unroll 1
+            for (uint32_t k = 0; k < 6u; ++k) {
+                const uint32_t w = kTetTriangles[(kTetMirror >> k) & 1u][mesh_tet_mask(cm, k)];
+                const uint32_t tc = (((kTetV1 >> (4u * k)) & 15u) << 4) | (((kTetV2 >> (4u * k)) & 15u) << 8) | (7u << 12);
+                const uint32_t nv = 3u * (w & 15u);
+#pragma unroll 1
+                for (uint32_t v = 0; v < nv; ++v) {
+                    const uint32_t e = (w >> (4u + 4u * v)) & 15u;
+                    const uint32_t cp = (tc >> (4u * ((kEdgeLo >> (4u * e)) & 15u))) & 15u;
+                    const uint32_t cq = (tc >> (4u * ((kEdgeHi >> (4u * e)) & 15u))) & 15u;
+                    // the edge (P, d): P = corner 0 + cp, d = cq - cp (cp's bits are among cq's)
+                    const uint32_t px = corner0[0] + (cp & 1u), py = corner0[1] + ((cp >> 1) & 1u), pz = corner0[2] + (cp >> 2);
+                    const uint32_t d = cq ^ cp;
+                    const size_t pb = ((size_t)(pz / kMB - a.b0[2]) * pny + (py / kMB - a.b0[1])) * pnx + (px / kMB - a.b0[0]);
+                    const size_t row = (size_t)slots[pb] * kMeshTableRows + ((py & 7u) + kMB * (pz & 7u));
+                    const unsigned long long before = (1ull << (8u * (px & 7u) + d - 1u)) - 1ull;
+                    indices[(size_t)(tri + v / 3u) * 3u + (size_t)(v % 3u)] = row_bases[row] + (uint32_t)__popcll(row_masks[row] & before);
+                }
+                tri += (unsigned long long)(w & 15u);
+            }
+        }
+    }
+}
+
 MeshArgs mesh_args(const MeshLaunch &a)
 {
     MeshArgs m;
@@ -379,6 +574,70 @@ hipError_t vr_launch_mesh_emit(const MeshLaunch &a, const uint32_t *counts, cons
         else
             hipLaunchKernelGGL((vr_mesh_emit_kernel<VT, false>), dim3(grid), dim3(64), 0, stream, a.vol, mesh_args(a), counts,
                                offsets, positions, normals);
+        return hipGetLastError();
+    });
+}
+
+// ---- the indexed extraction's launches
+
+namespace {
+
+// the launch over the point blocks: b0 as the cubes', one block more on an axis whose hi is a multiple of the block
+MeshArgs mesh_point_args(const MeshLaunch &a, uint32_t *grid)
+{
+    MeshArgs m = mesh_args(a);
+    vr_mesh_point_blocks(a, m.nb);
+    const unsigned long long n = (unsigned long long)m.nb[0] * m.nb[1] * m.nb[2];
+    *grid = n < 0x7fffffffull ? (uint32_t)n : 0u;
+    return m;
+}
+
+} // namespace
+
+hipError_t vr_launch_mesh_vertex_count(const MeshLaunch &a, uint32_t *vcounts, uint32_t *vflags, hipStream_t stream)
+{
+    uint32_t grid;
+    const MeshArgs m = mesh_point_args(a, &grid);
+    if (grid == 0) return hipErrorInvalidValue;
+    return vr_for_format(a.format, [&](auto vt) {
+        using VT = typename decltype(vt)::type;
+        hipLaunchKernelGGL((vr_mesh_vertex_count_kernel<VT>), dim3(grid), dim3(64), 0, stream, a.vol, m, a.cell_minmax, vcounts,
+                           vflags);
+        return hipGetLastError();
+    });
+}
+
+hipError_t vr_launch_mesh_vertex_emit(const MeshLaunch &a, const uint32_t *vcounts, const unsigned long long *voffsets,
+                                      const unsigned long long *slots, float *vertices, float *normals,
+                                      unsigned long long *row_masks, uint32_t *row_bases, hipStream_t stream)
+{
+    uint32_t grid;
+    const MeshArgs m = mesh_point_args(a, &grid);
+    if (grid == 0 || !vertices || !row_masks || !row_bases) return hipErrorInvalidValue;
+    return vr_for_format(a.format, [&](auto vt) {
+        using VT = typename decltype(vt)::type;
+        if (normals)
+            hipLaunchKernelGGL((vr_mesh_vertex_emit_kernel<VT, true>), dim3(grid), dim3(64), 0, stream, a.vol, m, vcounts,
+                               voffsets, slots, vertices, normals, row_masks, row_bases);
+        else
+            hipLaunchKernelGGL((vr_mesh_vertex_emit_kernel<VT, false>), dim3(grid), dim3(64), 0, stream, a.vol, m, vcounts,
+                               voffsets, slots, vertices, normals, row_masks, row_bases);
+        return hipGetLastError();
+    });
+}
+
+hipError_t vr_launch_mesh_index_emit(const MeshLaunch &a, const uint32_t *counts, const unsigned long long *offsets,
+                                     const unsigned long long *slots, const unsigned long long *row_masks,
+                                     const uint32_t *row_bases, uint32_t *indices, hipStream_t stream)
+{
+    const uint32_t grid = mesh_grid(a);
+    if (grid == 0 || !indices) return hipErrorInvalidValue;
+    uint32_t pnb[3];
+    vr_mesh_point_blocks(a, pnb);
+    return vr_for_format(a.format, [&](auto vt) {
+        using VT = typename decltype(vt)::type;
+        hipLaunchKernelGGL((vr_mesh_index_emit_kernel<VT>), dim3(grid), dim3(64), 0, stream, a.vol, mesh_args(a), pnb[0], pnb[1],
+                           counts, offsets, slots, row_masks, row_bases, indices);
         return hipGetLastError();
     });
 }

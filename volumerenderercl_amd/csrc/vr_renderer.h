@@ -242,6 +242,16 @@ struct vrhip_renderer {
     PinnedBuf mesh_host, mesh_totals_host;
     vrhip_mesh_info mesh_info;
     bool have_mesh_info = false;
+    // ... and its indexed form (vrhip_isosurface_count_indexed / _extract_indexed): per point block the vertex count,
+    // the holds-a-vertex flag and their two prefix sums, the partial sums of both scans, the rank tables of the
+    // blocks that hold a vertex (vr_internal.h kMeshTableBytes each); the cube blocks' words are the ones above,
+    // counted anew like them, and so is the staging of host destinations.  imesh_info: vrhip_last_indexed_mesh_info;
+    // mesh_info is not touched.
+    DevBuf<uint32_t> imesh_vcounts, imesh_vflags, imesh_row_bases;
+    DevBuf<unsigned long long> imesh_voffsets, imesh_slots, imesh_partials, imesh_row_masks;
+    PinnedBuf imesh_totals_host;
+    vrhip_indexed_mesh_info imesh_info;
+    bool have_imesh_info = false;
 
     // device-side ingest (vrhip_ingest_raw, vrhip_volume_histogram): the running maximum and the 256 64-bit
     // histogram counters in device memory, the events around its kernels (all created on first use)

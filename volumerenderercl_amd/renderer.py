@@ -547,6 +547,53 @@ class VolumeRenderCL:
         self._check(self._lib.vrhip_last_mesh_info(self._h, C.byref(mi)))
         return mi.as_dict()
 
+    # ---- indexed isosurface extraction (include/vrhip.h "indexed isosurface extraction")
+    def isosurface_count_indexed(self, iso, region=None):
+        """(vertices, triangles) of the indexed isosurface at `iso` (vrhip_isosurface_count_indexed): one vertex per
+        crossed lattice edge of the region, the triangles of isosurface_count."""
+        p = self._mesh_params(iso, False, region)
+        nv, nt = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.vrhip_isosurface_count_indexed(self._h, C.byref(p), C.byref(nv), C.byref(nt)))
+        return int(nv.value), int(nt.value)
+
+    def extract_isosurface_indexed(self, iso, normals=False, region=None, out_dev_ptrs=None):
+        """The isosurface at `iso` as an indexed mesh made on the device (vrhip_isosurface_extract_indexed): (vertices
+        float32 [m, 3] in box space, normals float32 [m, 3] or None, indices uint32 [n, 3]).  vertices[indices] is
+        extract_isosurface's list bit for bit; a vertex is a lattice edge, so edges that meet in a grid point equal to
+        `iso` stay separate vertices with equal positions, which frontend.weld_mesh would merge.
+        With out_dev_ptrs = (vertices, normals or None, indices, capacity in vertices, capacity in triangles) --
+        device addresses, 16-byte aligned -- the mesh is written there and (m, n) is returned; a capacity that is too
+        small raises, and isosurface_count_indexed tells what is needed."""
+        p = self._mesh_params(iso, normals, region)
+        nv, nt = C.c_uint64(0), C.c_uint64(0)
+        if out_dev_ptrs is not None:
+            vtx, nrm, idx, cap_v, cap_t = out_dev_ptrs
+            self._check(self._lib.vrhip_isosurface_extract_indexed(
+                self._h, C.byref(p), C.c_void_p(int(vtx)), C.c_void_p(int(nrm)) if nrm else None, C.c_void_p(int(idx)),
+                int(cap_v), int(cap_t), C.byref(nv), C.byref(nt), 1))
+            return int(nv.value), int(nt.value)
+        self._check(self._lib.vrhip_isosurface_count_indexed(self._h, C.byref(p), C.byref(nv), C.byref(nt)))
+        m, n = int(nv.value), int(nt.value)
+        vtx = np.empty((m, 3), dtype=np.float32)
+        nrm = np.empty((m, 3), dtype=np.float32) if normals else None
+        idx = np.empty((n, 3), dtype=np.uint32)
+        if n:
+            self._check(self._lib.vrhip_isosurface_extract_indexed(
+                self._h, C.byref(p), vtx.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p) if normals else None,
+                idx.ctypes.data_as(C.c_void_p), m, n, C.byref(nv), C.byref(nt), 0))
+            if (int(nv.value), int(nt.value)) != (m, n):
+                raise RuntimeError("extract_isosurface_indexed: the volume changed between the count and the extraction")
+        return vtx, nrm, idx
+
+    def lastIndexedMeshInfo(self):
+        """What the last isosurface_count_indexed / extract_isosurface_indexed did (vrhip_last_indexed_mesh_info):
+        vertices, triangles, point_blocks (of 8^3 grid points that own an edge of the region), point_blocks_skipped,
+        blocks, blocks_skipped (the cube blocks, as lastMeshInfo), scratch_bytes (device memory beyond the
+        destinations), empty_skip -- as a dict."""
+        mi = _lib.IndexedMeshInfo()
+        self._check(self._lib.vrhip_last_indexed_mesh_info(self._h, C.byref(mi)))
+        return mi.as_dict()
+
     # ---- volume
     def loadVolumeData(self, props, ingest="host"):
         """volumerendercl.cpp:765-805. `props` is a datraw.Properties (dat_file_name or
