@@ -369,7 +369,8 @@ VR_DEV void after_segment(const RayCtx &c, RayDyn &d)
 
 // LDS staging of the gathered sample evaluation (eval_batch): one slot per sample of a wave's
 // round (64 lanes x kBatch samples), for each of the 4 waves of a workgroup
-constexpr int kSlotFloats = 5;   // in: pos.xyz, opacity, owner|flags   out: ndl, spec, contour, op
+constexpr int kSlotFloats = 5;   // eval_batch: in: pos.xyz, opacity, owner|flags   out: ndl, spec, contour, op
+                                 // eval_front / eval_dense / eval_back: in: pos.xyz, density, owner|flags   out: colour.rgb, op
 constexpr int kStageFloatsPerWave = 64 * kBatch * kSlotFloats;
 // Dynamic LDS of the marching kernels: [a stage per wave][the transfer function, tff_n float4][the skip bitmap, n_words
 // + 1 words, if it is kept there].  The host sizes a launch with march_lds_bytes; the workgroup (WAVES waves) takes its
@@ -597,13 +598,23 @@ VR_DEV void eval_batch(const V &vol, const float4 *s_tff, int tffn, float *s_sta
 // opacity on the headline: inside the divergent call that was two passes of the gradient / shading code
 // more often than not; the wave's idle and empty-run-skipping lanes take the second half now.  The same
 // operations per sample, in another lane (as before).
+//
+// The COLOUR of a sample is the dense pass's work too.  Only the TF's alpha decides `lit` and `need`; a sample
+// without `need` composites to nothing whatever its colour is (op == 0: colour * op is a zero whose sign alone is the
+// colour's doing, and r - (+-0) * oma is r for every r but -0, which the accumulator -- the environment colour less
+// such products -- holds only where the background itself is -0), and two thirds of the headline's evaluated
+// samples are such.  So eval_front reads the two table entries' alpha only (tff_linear_alpha: the index, entries and
+// lerp of tff_linear's .w) and stages the DENSITY in the slot; eval_dense runs tff_linear on it -- the same fp32
+// operations on the same operands, so the same alpha, now with the colour --, applies the shading terms to the
+// colour right where it has computed them, and hands back colour and opacity: a slot stays 5 floats.  The colour
+// that is no longer computed was finite (0 * colour cannot have been a NaN): the table holds bytes / 255 (TfView),
+// and tff_coord's clamp keeps a FLOAT volume's inf and NaN voxels on its edge entries -- in both lookups.
 struct EvalFront {
-    float4 tfc[kBatch];
     bool lit[kBatch], need[kBatch];
     uint32_t slot[kBatch];
 };
 
-// divergent part 1: density, transfer function, slots of the samples with an opacity, staged to LDS.
+// divergent part 1: density, the transfer function's alpha, slots of the samples with an opacity, staged to LDS.
 // Returns the number of slots (the same in every lane that calls).
 template <typename VT, bool FP, typename V>
 VR_DEV uint32_t eval_front(const V &vol, const float4 *s_tff, int tffn, float *s_stage, const RayCtx &c,
@@ -625,16 +636,17 @@ VR_DEV uint32_t eval_front(const V &vol, const float4 *s_tff, int tffn, float *s
 #pragma unroll
         for (int k = 0; k < kBatch; ++k) dens[k] = vol.linear(pk[k].x, pk[k].y, pk[k].z);
     }
+    float al[kBatch];
 #pragma unroll
-    for (int k = 0; k < kBatch; ++k) ef.tfc[k] = tff_linear<kRawDensity<VT>>(s_tff, tffn, dens[k]);
+    for (int k = 0; k < kBatch; ++k) al[k] = tff_linear_alpha<kRawDensity<VT>>(s_tff, tffn, dens[k]);
     const bool shade_mode = rp.illumType == 1;   // :809
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t n_slots = 0;
 #pragma unroll
     for (int k = 0; k < kBatch; ++k) {
-        ef.lit[k] = vk[k] && ef.tfc[k].w > 0.1f;   // :809/:832
+        ef.lit[k] = vk[k] && al[k] > 0.1f;   // :809/:832
         // opacity 0 gives op = 1 - powr(1, y) = 0 exactly: nothing of the sample survives
-        ef.need[k] = vk[k] && ef.tfc[k].w != 0.f;
+        ef.need[k] = vk[k] && al[k] != 0.f;
         const unsigned long long m = __ballot(ef.need[k]);
         ef.slot[k] = n_slots + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
         n_slots += (uint32_t)__builtin_popcountll(m);
@@ -645,7 +657,7 @@ VR_DEV uint32_t eval_front(const V &vol, const float4 *s_tff, int tffn, float *s
             if (ef.need[k]) {
                 float *q = s_stage + kSlotFloats * ef.slot[k];
                 q[0] = pk[k].x; q[1] = pk[k].y; q[2] = pk[k].z;
-                q[3] = ef.tfc[k].w;
+                q[3] = dens[k];
                 q[4] = __uint_as_float(lane | ((ef.lit[k] && shade_mode) ? 64u : 0u));
             }
         }
@@ -655,7 +667,8 @@ VR_DEV uint32_t eval_front(const V &vol, const float4 *s_tff, int tffn, float *s
 
 // wave-uniform part: every lane of the wave takes slots (n_slots > 0, the same in all 64 lanes)
 template <typename VT, bool FP, typename V>
-VR_DEV void eval_dense(const V &vol, float *s_stage, const RayCtx &c, float refInterval, uint32_t n_slots)
+VR_DEV void eval_dense(const V &vol, const float4 *s_tff, int tffn, float *s_stage, const RayCtx &c, float refInterval,
+                       uint32_t n_slots)
 {
     const uint32_t lane = threadIdx.x & 63u;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -664,7 +677,8 @@ VR_DEV void eval_dense(const V &vol, float *s_stage, const RayCtx &c, float refI
         const uint32_t sidx = base + lane;
         const bool mine = sidx < n_slots;
         float *q = s_stage + kSlotFloats * (mine ? sidx : 0u);
-        const float qx = q[0], qy = q[1], qz = q[2], qw = q[3];
+        const float qx = q[0], qy = q[1], qz = q[2];
+        const float qd = mine ? q[3] : 0.f;   // (slot 0 holds a result from the second pass on: not a density)
         const uint32_t tag = mine ? __float_as_uint(q[4]) : lane;
         const int owner = (int)(tag & 63u);
         const bool shade = mine && (tag & 64u);
@@ -672,57 +686,51 @@ VR_DEV void eval_dense(const V &vol, float *s_stage, const RayCtx &c, float refI
         const f3 lgt = mk3(__shfl(c.lgt.x, owner, 64), __shfl(c.lgt.y, owner, 64), __shfl(c.lgt.z, owner, 64));
         const f3 hv = mk3(__shfl(c.hv.x, owner, 64), __shfl(c.hv.y, owner, 64), __shfl(c.hv.z, owner, 64));
         const int hvalid = __shfl(c.hvalid ? 1 : 0, owner, 64);
-        float o_ndl = 0.f, o_sp = 0.f, o_op = 0.f;
+        // colour and alpha of the sample: eval_front's lookup again, all four channels (its alpha bit for bit)
+        float4 t = tff_linear<kRawDensity<VT>>(s_tff, tffn, qd);
         if (__ballot(shade)) {
             if (shade) {
                 const f3 g = vol.neg_gradient(qx, qy, qz);
                 // illumination (:294-303) with specularBlinnPhong (:280-291)
-                o_ndl = vmax(0.f, dot3(g, lgt));
-                o_sp = hvalid ? vr_powr(vmax(dot3(g, hv), 0.f), 40.f) : 0.0f;
+                const float o_ndl = vmax(0.f, dot3(g, lgt));
+                float o_sp = hvalid ? vr_powr(vmax(dot3(g, hv), 0.f), 40.f) : 0.0f;
                 o_sp = o_sp * 0.15f;
+                t.x = ((t.x * 0.15f) + ((t.x * o_ndl) * 0.7f)) + o_sp;
+                t.y = ((t.y * 0.15f) + ((t.y * o_ndl) * 0.7f)) + o_sp;
+                t.z = ((t.z * 0.15f) + ((t.z * o_ndl) * 0.7f)) + o_sp;
             }
         }
         if (mine) {
-            o_op = 1.f - vr_powr(1.f - qw, refInterval);  // opacity correction (:864)
-            q[0] = o_ndl; q[1] = o_sp; q[2] = 0.f; q[3] = o_op;
+            const float o_op = 1.f - vr_powr(1.f - t.w, refInterval);  // opacity correction (:864)
+            q[0] = t.x; q[1] = t.y; q[2] = t.z; q[3] = o_op;
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
 
-// divergent part 2: the samples' scalars back from their slots, shading combined, colour x opacity
-VR_DEV void eval_back(const float *s_stage, const RayCtx &c, const vrhip_rendering_params &rp, EvalFront &ef,
-                      uint32_t n_slots, float (&p0)[kBatch], float (&p1)[kBatch], float (&p2)[kBatch],
-                      float (&op)[kBatch])
+// divergent part 2: the samples' (shaded) colour and opacity back from their slots, colour x opacity.  A sample without
+// a slot has opacity 0 and any colour: 0.
+VR_DEV void eval_back(const float *s_stage, const RayCtx &c, const EvalFront &ef, uint32_t n_slots,
+                      float (&p0)[kBatch], float (&p1)[kBatch], float (&p2)[kBatch], float (&op)[kBatch])
 {
-    const bool shade_mode = rp.illumType == 1;
-    float ndl[kBatch], spc[kBatch];
+    float t0[kBatch], t1[kBatch], t2[kBatch];
 #pragma unroll
-    for (int k = 0; k < kBatch; ++k) { ndl[k] = 0.f; spc[k] = 0.f; op[k] = 0.f; }
+    for (int k = 0; k < kBatch; ++k) { t0[k] = 0.f; t1[k] = 0.f; t2[k] = 0.f; op[k] = 0.f; }
     if (n_slots) {
 #pragma unroll
         for (int k = 0; k < kBatch; ++k) {
             if (ef.need[k]) {
                 const float *q = s_stage + kSlotFloats * ef.slot[k];
-                ndl[k] = q[0]; spc[k] = q[1]; op[k] = q[3];
+                t0[k] = q[0]; t1[k] = q[1]; t2[k] = q[2]; op[k] = q[3];
             }
         }
     }
 #pragma unroll
     for (int k = 0; k < kBatch; ++k) {
-        float4 t = ef.tfc[k];
-        if (ef.lit[k] && shade_mode) {
-            t.x = ((t.x * 0.15f) + ((t.x * ndl[k]) * 0.7f)) + spc[k];
-            t.y = ((t.y * 0.15f) + ((t.y * ndl[k]) * 0.7f)) + spc[k];
-            t.z = ((t.z * 0.15f) + ((t.z * ndl[k]) * 0.7f)) + spc[k];
-        }
-        t.x = c.env0 - t.x;
-        t.y = c.env1 - t.y;
-        t.z = c.env2 - t.z;
-        p0[k] = t.x * op[k];
-        p1[k] = t.y * op[k];
-        p2[k] = t.z * op[k];
+        p0[k] = (c.env0 - t0[k]) * op[k];
+        p1[k] = (c.env1 - t1[k]) * op[k];
+        p2[k] = (c.env2 - t2[k]) * op[k];
     }
 }
 
@@ -1460,10 +1468,10 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_rays_kernel(
 #endif
             EvalFront ef;
             const uint32_t ns = eval_front<VT, FP>(vol, s_tff, tffn, s_stage, c, rp, tk, vk, ev, ef);
-            if (ns) eval_dense<VT, FP>(vol, s_stage, c, refInterval, ns);
+            if (ns) eval_dense<VT, FP>(vol, s_tff, tffn, s_stage, c, refInterval, ns);
             VR_MARK("R_comp");
             float p0[kBatch], p1[kBatch], p2[kBatch], opk[kBatch];
-            eval_back(s_stage, c, rp, ef, ns, p0, p1, p2, opk);
+            eval_back(s_stage, c, ef, ns, p0, p1, p2, opk);
 #pragma unroll
             for (int k = 0; k < kBatch; ++k)
                 if (vk[k] && d.state == S_SAMPLE) composite(c, d, p0[k], p1[k], p2[k], opk[k], tk[k]);
@@ -1812,9 +1820,9 @@ __global__ __launch_bounds__(WAVES * 64) void vr_raycast_split_kernel(
                     VR_BATCH_PARAMS_SPLIT(ev2 && d.t < d.t_exit);
                     EvalFront ef;
                     const uint32_t ns = eval_front<VT, FP>(vol, s_tff, tffn, s_stage, c, rp, tk, vk, ev2, ef);
-                    if (ns) eval_dense<VT, FP>(vol, s_stage, c, refInterval, ns);
+                    if (ns) eval_dense<VT, FP>(vol, s_tff, tffn, s_stage, c, refInterval, ns);
                     float p0[kBatch], p1[kBatch], p2[kBatch], opk[kBatch];
-                    eval_back(s_stage, c, rp, ef, ns, p0, p1, p2, opk);
+                    eval_back(s_stage, c, ef, ns, p0, p1, p2, opk);
                     VR_STAMP(3);
                     int fl[kBatch];
 #pragma unroll
