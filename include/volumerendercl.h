@@ -241,6 +241,24 @@ public:
     // per crossed lattice edge, vertices[indices] = extractIsosurface's list bit for bit.  Where a grid point equals
     // `iso` several vertices share a position, which weldMesh would merge; no host weld happens here.
     welded_mesh extractIsosurfaceIndexed(float iso, bool normals = false, const mesh_region &region = mesh_region());
+    // ---- volume statistics (no reference counterpart; vrhip.h "volume statistics"): the counts, the moments and the
+    // value x gradient-magnitude histogram of a region of the current time step, computed on the device.  s is the
+    // normalised value isoValue is compared against; bins: vBins over [vLo, vHi] and gBins over [0, gHi), the top
+    // gradient bin open-ended; region: the voxels lo <= v < hi, all zero: the whole volume; moments: min, max, sum and
+    // sumSq of s as well (0 without).  hist is [gBins][vBins], value fastest.  Nothing a render call reads changes.
+    struct stats_params {
+        unsigned int vBins = 256, gBins = 1;
+        float vLo = 0.f, vHi = 1.f, gHi = 1.f;
+        mesh_region region;
+        bool moments = false;
+    };
+    struct volume_stats {
+        uint64_t voxels = 0, nan = 0, below = 0, above = 0, gradientNan = 0, binned = 0;
+        float min = 0.f, max = 0.f;
+        double sum = 0., sumSq = 0.;
+        std::vector<uint64_t> hist;
+    };
+    volume_stats volumeStatistics(const stats_params &params);
     // ---- the progressive path tracer (technique 1), many samples per call (vrhip_render_samples): seeds.size()
     // consecutive iterations of the accumulated image -- sample k with jitter seed seeds[k] at iteration
     // (current iteration + k) -- in as few launch sets as possible, bit for bit what seeds.size() runRaycastNoGL calls

@@ -501,6 +501,81 @@ typedef struct vrhip_indexed_mesh_info {
 } vrhip_indexed_mesh_info;  /* 64 bytes */
 int vrhip_last_indexed_mesh_info(const vrhip_renderer *r, vrhip_indexed_mesh_info *out);
 
+/* ---- volume statistics: counts, moments and the value x gradient-magnitude histogram of a region (DESIGN.md "Volume
+ * statistics").  Not a technique: it reads the volume and writes the caller's destinations.  fp32, every operation
+ * rounded on its own, no contraction; tests/ref/stats_ref.c restates it on the CPU.
+ *  Value: s = (float)raw * inv_max of channel 0 of the current time step (FLOAT: the raw value) -- the grid-point
+ *   value of the isosurface extraction, the s techniques 2 and 4 and the slices compare against.
+ *  Region: the voxels lo <= v < hi per axis; all six values 0: the whole volume.  lo == hi on an axis: no voxel.
+ *  A voxel of the region is classified in this order: a NaN s counts in `nan`; s < v_lo in `below`; s > v_hi in
+ *   `above`; else it has the value bin i: k_v = (float)bins_v / (v_hi - v_lo) once, u = (s - v_lo) * k_v,
+ *   i = u >= (float)bins_v ? bins_v - 1 : (uint32_t)u (s == v_hi lies in the last bin).
+ *  Gradient, for voxels with a value bin and bins_g > 1 (else j = 0): per axis g_a = s(p + e_a) - s(p - e_a), the
+ *   neighbour's coordinate clamped to the VOLUME (not the region: histograms of disjoint regions add up), in index
+ *   space (slice thickness is ignored); m = 0.5f * sqrtf((gx * gx + gy * gy) + gz * gz).  A NaN m counts in
+ *   `gradient_nan` and the voxel is not binned; else k_g = (float)bins_g / g_hi once, w = m * k_g,
+ *   j = w >= (float)bins_g ? bins_g - 1 : (uint32_t)w: the top gradient bin is open-ended.
+ *  hist[j * bins_v + i] += 1: bins_g * bins_v 64-bit counts, value fastest, written whole (zeros included).
+ *   voxels == nan + below + above + gradient_nan + binned, binned == the sum of hist.
+ *  Moments (VRHIP_STATS_MOMENTS; without it min, max, sum and sum_sq are 0): min and max over the non-NaN s of the
+ *   region, compared with < and >, +inf and -inf where there is none, a zero of either sign reported as +0; sum and
+ *   sum_sq of (double)s and (double)s * (double)s over the same voxels, in this order, which is part of the contract:
+ *   blocks of VRHIP_MESH_BLOCK^3 voxels anchored at voxel (0,0,0); lane x + 8 y of a block adds the voxels of its
+ *   column z = 0..7 ascending, from 0.0 (voxels outside the region and NaNs add nothing); then over the 64 lanes
+ *   v += v[lane ^ k] for k = 1, 2, 4, 8, 16, 32; the block sums of the call's block grid (the blocks that hold a
+ *   voxel of the region, x fastest) are added from 0.0 in ascending order within chunks of VRHIP_STATS_SUM_CHUNK
+ *   consecutive blocks, and the chunk sums from 0.0 in ascending order.  No floating-point atomic anywhere: two calls
+ *   give the same bits, whatever the object-ESS switch says.
+ *  vrhip_set_object_ess: on, a block whose cell of the cell grid proves the outcome is not fetched.  Constant block
+ *   (min == max, finite): every voxel of it in the region has the value bin (or below / above) of fl(min * inv_max)
+ *   and gradient bin 0.  Out of window (without VRHIP_STATS_MOMENTS only): fl(max * inv_max) < v_lo or
+ *   fl(min * inv_max) > v_hi, every voxel below or above.  With VRHIP_STATS_MOMENTS a constant block is skipped only
+ *   where min == max == 0: its block sums are +0.0 and its min and max 0 on either path (n * c is exact in double
+ *   for n <= 512, n * c * c is not in general, so other constants are fetched).  A cell with a NaN holds
+ *   (-inf, +inf) and proves nothing.  No count and no bit of the output changes with the switch.
+ *  hist: host memory, or with hist_is_device != 0 device memory, 16-byte aligned; either way the call returns after
+ *   the counts have reached *out, so the histogram is complete then.
+ *  vrhip_last_stats_info: the blocks of the last call that hold a voxel of the region, how many were fetched, skipped
+ *   as constant and skipped as out of window, whether the cell grid was handed over, which histogram path ran
+ *   (VRHIP_STATS_PATH_*: per-workgroup tables in LDS flushed with 64-bit integer atomics, or atomics straight to the
+ *   global table) and the scratch the call held in device memory beyond the histogram.
+ *  State: reads the volume, the time step and the object-ESS switch; writes nothing a render, slice, depth or mesh
+ *   call or their last_*_info reads later.
+ *  VRHIP_ERR_INVALID: a NULL r, p, out or hist; bins_v outside 1..4096, bins_g outside 1..256 or their product above
+ *   65536; v_lo or v_hi not finite, v_hi <= v_lo, or k_v not finite; bins_g > 1 with g_hi not finite, g_hi <= 0 or
+ *   k_g not finite; flags other than VRHIP_STATS_MOMENTS; reserved != 0; a region that is not all zero with hi > res,
+ *   lo > hi or hi == 0 on an axis; a device hist that is not 16-byte aligned.  VRHIP_ERR_UNSUPPORTED: RG / RGBA
+ *   volumes.  VRHIP_ERR_NODATA: no volume; vrhip_last_stats_info before the first call. */
+#define VRHIP_STATS_MOMENTS 1u
+#define VRHIP_STATS_SUM_CHUNK 256u
+#define VRHIP_STATS_MAX_BINS_V 4096u
+#define VRHIP_STATS_MAX_BINS_G 256u
+#define VRHIP_STATS_MAX_BINS 65536u
+enum { VRHIP_STATS_PATH_LDS = 0, VRHIP_STATS_PATH_GLOBAL = 1 };
+typedef struct vrhip_stats_params {
+    uint32_t lo[3], hi[3];  /* region in voxels; all six 0: the whole volume */
+    uint32_t bins_v, bins_g;
+    float    v_lo, v_hi, g_hi;
+    uint32_t flags;         /* VRHIP_STATS_MOMENTS */
+    uint32_t reserved[4];   /* must be 0 */
+} vrhip_stats_params;       /* 64 bytes */
+typedef struct vrhip_volume_stats {
+    uint64_t voxels, nan, below, above, gradient_nan, binned;
+    float    min, max;
+    double   sum, sum_sq;
+} vrhip_volume_stats;       /* 72 bytes */
+int vrhip_volume_statistics(vrhip_renderer *r, const vrhip_stats_params *p, vrhip_volume_stats *out, uint64_t *hist,
+                            int hist_is_device);
+typedef struct vrhip_stats_info {
+    uint64_t blocks, blocks_fetched, blocks_skipped_constant, blocks_skipped_window;
+    uint64_t scratch_bytes;
+    uint32_t empty_skip, hist_path;
+} vrhip_stats_info;         /* 48 bytes */
+int vrhip_last_stats_info(const vrhip_renderer *r, vrhip_stats_info *out);
+/* the checks of vrhip_volume_statistics that need neither a renderer nor a volume -- bins, window, g_hi, flags,
+ * reserved -- for callers that validate before they have a device: VRHIP_OK or VRHIP_ERR_INVALID (a NULL p too) */
+int vrhip_stats_params_check(const vrhip_stats_params *p);
+
 /* createEnvironmentMap (volumerendercl.cpp:1121-1150): float RGBA texels, row-major, width*height*4
  * floats (the host layer decodes the Radiance .hdr file).  The kernel samples it in place of the
  * background colour when it is wider than one texel (volumeraycast.cl:506-510, :655-656);

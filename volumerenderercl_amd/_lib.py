@@ -111,6 +111,40 @@ class IndexedMeshInfo(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
+# vrhip_stats_params.flags, the chunk of the moments' sum and vrhip_stats_info.hist_path (volume statistics,
+# vrhip_volume_statistics)
+STATS_MOMENTS = 1
+STATS_SUM_CHUNK = 256
+STATS_PATH_LDS, STATS_PATH_GLOBAL = 0, 1
+
+
+class StatsParams(C.Structure):
+    """vrhip_stats_params: the region, the bins, the window and the flags of a vrhip_volume_statistics call."""
+    _fields_ = [("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("bins_v", C.c_uint32), ("bins_g", C.c_uint32),
+                ("v_lo", C.c_float), ("v_hi", C.c_float), ("g_hi", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class VolumeStats(C.Structure):
+    """vrhip_volume_stats: the counts and the moments of a region."""
+    _fields_ = [("voxels", C.c_uint64), ("nan", C.c_uint64), ("below", C.c_uint64), ("above", C.c_uint64),
+                ("gradient_nan", C.c_uint64), ("binned", C.c_uint64), ("min", C.c_float), ("max", C.c_float),
+                ("sum", C.c_double), ("sum_sq", C.c_double)]
+
+    def as_dict(self):
+        return {n: (float if t in (C.c_float, C.c_double) else int)(getattr(self, n)) for n, t in self._fields_}
+
+
+class StatsInfo(C.Structure):
+    """vrhip_stats_info: what the last vrhip_volume_statistics did."""
+    _fields_ = [("blocks", C.c_uint64), ("blocks_fetched", C.c_uint64), ("blocks_skipped_constant", C.c_uint64),
+                ("blocks_skipped_window", C.c_uint64), ("scratch_bytes", C.c_uint64), ("empty_skip", C.c_uint32),
+                ("hist_path", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class Stats(C.Structure):
     _fields_ = [("samples_taken", C.c_uint64), ("samples_nominal", C.c_uint64),
                 ("samples_shaded", C.c_uint64), ("bricks_visited", C.c_uint64),
@@ -137,6 +171,7 @@ assert C.sizeof(RaycastParams) == 32 and C.sizeof(PathtraceParams) == 4 and C.si
 assert C.sizeof(SliceParams) == 80
 assert C.sizeof(DepthParams) == 32 and C.sizeof(DepthInfo) == 32
 assert C.sizeof(MeshParams) == 48 and C.sizeof(MeshInfo) == 32 and C.sizeof(IndexedMeshInfo) == 64
+assert C.sizeof(StatsParams) == 64 and C.sizeof(VolumeStats) == 72 and C.sizeof(StatsInfo) == 48
 
 _H = C.c_void_p
 _U3 = C.POINTER(C.c_uint32)
@@ -219,6 +254,9 @@ SYMBOLS = {
     "vrhip_isosurface_extract_indexed": (C.c_int, [_H, C.POINTER(MeshParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                    C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
     "vrhip_last_indexed_mesh_info": (C.c_int, [_H, C.POINTER(IndexedMeshInfo)]),
+    "vrhip_volume_statistics": (C.c_int, [_H, C.POINTER(StatsParams), C.POINTER(VolumeStats), C.c_void_p, C.c_int]),
+    "vrhip_last_stats_info": (C.c_int, [_H, C.POINTER(StatsInfo)]),
+    "vrhip_stats_params_check": (C.c_int, [C.POINTER(StatsParams)]),
     "vrhip_render_tiles": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_void_p, C.c_uint32, C.c_void_p]),
     "vrhip_set_environment_map": (C.c_int, [_H, C.c_void_p, C.c_uint32, C.c_uint32]),

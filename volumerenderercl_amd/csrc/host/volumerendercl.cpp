@@ -773,6 +773,36 @@ VolumeRenderCL::welded_mesh VolumeRenderCL::extractIsosurfaceIndexed(float iso, 
     return m;
 }
 
+VolumeRenderCL::volume_stats VolumeRenderCL::volumeStatistics(const stats_params &params)
+{
+    if (!_volLoaded) throw std::runtime_error("No volume data is loaded.");
+    vrhip_stats_params p{};
+    for (int i = 0; i < 3; ++i) { p.lo[i] = params.region.lo[i]; p.hi[i] = params.region.hi[i]; }
+    p.bins_v = params.vBins;
+    p.bins_g = params.gBins;
+    p.v_lo = params.vLo;
+    p.v_hi = params.vHi;
+    p.g_hi = params.gHi;
+    p.flags = params.moments ? VRHIP_STATS_MOMENTS : 0u;
+    if (vrhip_stats_params_check(&p) != VRHIP_OK)   // (before the table is sized by the bins)
+        throw std::invalid_argument("volumeStatistics: bins, window or gradient range out of range");
+    volume_stats out;
+    out.hist.resize(size_t(p.bins_v) * p.bins_g);
+    vrhip_volume_stats st{};
+    check("volumeStatistics", vrhip_volume_statistics(_r, &p, &st, out.hist.data(), 0));
+    out.voxels = st.voxels;
+    out.nan = st.nan;
+    out.below = st.below;
+    out.above = st.above;
+    out.gradientNan = st.gradient_nan;
+    out.binned = st.binned;
+    out.min = st.min;
+    out.max = st.max;
+    out.sum = st.sum;
+    out.sumSq = st.sum_sq;
+    return out;
+}
+
 void VolumeRenderCL::renderSlicesRGBA8(size_t width, size_t height, const std::vector<slice_params> &slices,
                                        float *dev_frames, unsigned char *out, bool outIsDevice)
 {

@@ -499,8 +499,54 @@ void write_rgba8(const std::string &out, const std::vector<unsigned char> &frame
         "                                           --mesh-region and --timestep need --mesh; --mesh-indexed, with a\n"
         "                                           .ply only: the indexed mesh as the device makes it, one vertex per\n"
         "                                           crossed lattice edge, no weld on the host)\n"
+        "         [--stats FILE.json] [--stats-bins V G] [--stats-window LO HI GHI] [--stats-region X0 Y0 Z0 X1 Y1 Z1]\n"
+        "         [--stats-moments] [--stats-hist FILE.u64] [--timestep T]\n"
+        "                                          (what is in the volume instead of a rendered frame: the counts of the\n"
+        "                                           normalised values of channel 0 -- voxels, nan, below, above,\n"
+        "                                           gradient_nan, binned -- and the value x gradient-magnitude histogram,\n"
+        "                                           V (1-4096, default 256) value bins over [LO, HI] (default 0 1) by G\n"
+        "                                           (1-256, default 1) gradient bins over [0, GHI) (default 1), the top\n"
+        "                                           one open-ended, V * G <= 65536, computed on the device, as JSON with\n"
+        "                                           the table as rows of V counts; --stats-region: the voxels from\n"
+        "                                           (X0, Y0, Z0) up to but not including (X1, Y1, Z1); --stats-moments:\n"
+        "                                           min, max, sum, sum_sq, mean and std too; --stats-hist: the table as\n"
+        "                                           G * V little-endian 64-bit counts; --timestep: of that time step;\n"
+        "                                           needs no --size, camera or --out; not with a render, slice, depth or\n"
+        "                                           mesh option, --ranks, --frames, --rgba8, --downsample; the other\n"
+        "                                           --stats-* options need --stats)\n"
         "writes PREFIX.rgba.f32 (W*H*4 float32, row 0 = top), PREFIX.ppm and prints one JSON line\n";
     std::exit(2);
+}
+
+// --stats: the counts, the moments when they were asked for (mean and std: population, in double, from sum and
+// sum_sq over the non-NaN voxels) and the table, rows of vBins counts by ascending gradient bin
+bool write_stats_json(const std::string &path, const VolumeRenderCL::stats_params &sp, const VolumeRenderCL::volume_stats &st)
+{
+    std::ofstream f(path);
+    char num[64];
+    auto real = [&](double v) -> std::string {   // (JSON has no inf or nan: as strings)
+        if (!std::isfinite(v)) return v != v ? "\"nan\"" : v > 0 ? "\"inf\"" : "\"-inf\"";
+        std::snprintf(num, sizeof num, "%.17g", v);
+        return num;
+    };
+    f << "{\"bins\": [" << sp.vBins << ", " << sp.gBins << "], \"window\": [" << real(sp.vLo) << ", " << real(sp.vHi) << ", "
+      << real(sp.gHi) << "],\n \"voxels\": " << st.voxels << ", \"nan\": " << st.nan << ", \"below\": " << st.below
+      << ", \"above\": " << st.above << ", \"gradient_nan\": " << st.gradientNan << ", \"binned\": " << st.binned;
+    if (sp.moments) {
+        const double n = double(st.voxels - st.nan), mean = n > 0 ? st.sum / n : 0.0;
+        const double var = n > 0 ? std::max(0.0, st.sumSq / n - mean * mean) : 0.0;
+        f << ",\n \"min\": " << real(st.min) << ", \"max\": " << real(st.max) << ", \"sum\": " << real(st.sum)
+          << ", \"sum_sq\": " << real(st.sumSq) << ", \"mean\": " << real(mean) << ", \"std\": " << real(std::sqrt(var));
+    }
+    f << ",\n \"hist\": [";
+    for (unsigned j = 0; j < sp.gBins; ++j) {
+        f << (j ? ",\n  [" : "[");
+        for (unsigned i = 0; i < sp.vBins; ++i) f << (i ? ", " : "") << st.hist[size_t(j) * sp.vBins + i];
+        f << "]";
+    }
+    f << "]}\n";
+    f.flush();
+    return bool(f);
 }
 
 } // namespace
@@ -550,6 +596,11 @@ int main(int argc, char **argv)
     double mesh_iso = 0.5;
     std::string mesh_file;
     long mesh_region[6] = {0, 0, 0, 0, 0, 0}, timestep = 0;
+    // volume statistics (--stats, --stats-bins, --stats-window, --stats-region, --stats-moments, --stats-hist)
+    bool stats = false, have_stats_opt = false, have_stats_region = false, stats_moments = false;
+    std::string stats_file, stats_hist_file;
+    long stats_bins[2] = {256, 1}, stats_region[6] = {0, 0, 0, 0, 0, 0};
+    double stats_window[3] = {0.0, 1.0, 1.0};
 
     auto need = [&](int i, int n) { if (i + n >= argc) usage(); };
     for (int i = 1; i < argc; ++i) {
@@ -637,6 +688,16 @@ int main(int argc, char **argv)
         else if (a == "--mesh-normals") mesh_normals = true;
         else if (a == "--mesh-indexed") mesh_indexed = true;
         else if (a == "--mesh-region") { need(i, 6); for (int k = 0; k < 6; ++k) mesh_region[k] = std::atol(argv[++i]); have_mesh_region = true; }
+        else if (a == "--stats") { need(i, 1); stats = true; stats_file = argv[++i]; }
+        else if (a == "--stats-bins") { need(i, 2); for (int k = 0; k < 2; ++k) stats_bins[k] = std::atol(argv[++i]); have_stats_opt = true; }
+        else if (a == "--stats-window") { need(i, 3); for (int k = 0; k < 3; ++k) stats_window[k] = std::atof(argv[++i]); have_stats_opt = true; }
+        else if (a == "--stats-region") {
+            need(i, 6);
+            for (int k = 0; k < 6; ++k) stats_region[k] = std::atol(argv[++i]);
+            have_stats_opt = have_stats_region = true;
+        }
+        else if (a == "--stats-moments") have_stats_opt = stats_moments = true;
+        else if (a == "--stats-hist") { need(i, 1); stats_hist_file = argv[++i]; have_stats_opt = true; }
         else if (a == "--timestep") { need(i, 1); timestep = std::atol(argv[++i]); have_timestep = true; }
         else usage();
     }
@@ -681,7 +742,24 @@ int main(int argc, char **argv)
                 usage();
         }
     }
-    if ((mesh_normals || have_mesh_region || have_timestep || mesh_indexed) && !mesh) usage();
+    if ((mesh_normals || have_mesh_region || mesh_indexed) && !mesh) usage();
+    if (have_timestep && !mesh && !stats) usage();
+    if (have_stats_opt && !stats) usage();
+    if (stats) {
+        // numbers about the volume, not a picture of it: as for --mesh, and not with it
+        if (mesh || pathtrace || mip || iso || have_iso_refine || slicing || have_slab || have_stack || slice_value || depth ||
+            ranks > 0 || frames_per_launch > 0 || have_orbit || have_path_arg || frames != 1 || rgba8 || img_ess || downsample ||
+            !dump_tf.empty() || bench || independent)
+            usage();
+        if (stats_file.empty() || timestep < 0) usage();
+        if (stats_bins[0] < 1 || stats_bins[0] > 4096 || stats_bins[1] < 1 || stats_bins[1] > 256 ||
+            stats_bins[0] * stats_bins[1] > 65536)
+            usage();
+        if (!std::isfinite(stats_window[0]) || !std::isfinite(stats_window[1]) || !(float(stats_window[1]) > float(stats_window[0])))
+            usage();
+        if (stats_bins[1] > 1 && (!std::isfinite(stats_window[2]) || !(float(stats_window[2]) > 0.f))) usage();
+        for (long c : stats_region) if (c < 0 || c > 8192) usage();
+    }
     bool mesh_ply = false;
     if (mesh) {
         const size_t dot = mesh_file.rfind('.');
@@ -758,7 +836,7 @@ int main(int argc, char **argv)
             return 1;
         }
     }
-    if ((dat.empty() && synth_kind.empty()) || (out.empty() && !downsample && !mesh)) usage();
+    if ((dat.empty() && synth_kind.empty()) || (out.empty() && !downsample && !mesh && !stats)) usage();
 
     try {
         // everything the front end sets on a renderer; returns false when there is no frame to render
@@ -896,6 +974,43 @@ int main(int argc, char **argv)
                 std::printf("{\"device\": \"%s\", \"mesh\": \"%s\", \"iso\": %.9g, \"triangles\": %zu}\n",
                             vr.getCurrentDeviceName().c_str(), mesh_file.c_str(), mesh_iso, triangles);
             }
+            return 0;
+        }
+        if (stats) {
+            // ---- what is in the volume (VolumeRenderCL::volumeStatistics): the volume, the ESS switch, nothing else
+            VolumeRenderCL vr;
+            vr.initialize(false, false, VENDOR_ANY, std::to_string(device));
+            if (!dat.empty()) {
+                DatRawReader::Properties p;
+                p.dat_file_name = dat;
+                vr.setDeviceIngest(device_ingest);
+                vr.loadVolumeData(p);
+            } else {
+                DatRawReader::data_format f = synth_fmt == "USHORT" ? DatRawReader::USHORT
+                                              : synth_fmt == "FLOAT" ? DatRawReader::FLOAT : DatRawReader::UCHAR;
+                vr.loadSyntheticVolume(synth_kind, synth_n, f);
+            }
+            vr.setObjEss(ess);
+            if (have_timestep) vr.setTimestep(size_t(timestep));
+            VolumeRenderCL::stats_params sp;
+            sp.vBins = unsigned(stats_bins[0]);
+            sp.gBins = unsigned(stats_bins[1]);
+            sp.vLo = float(stats_window[0]);
+            sp.vHi = float(stats_window[1]);
+            sp.gHi = float(stats_window[2]);
+            sp.moments = stats_moments;
+            if (have_stats_region)
+                for (size_t k = 0; k < 3; ++k) { sp.region.lo[k] = unsigned(stats_region[k]); sp.region.hi[k] = unsigned(stats_region[3 + k]); }
+            const VolumeRenderCL::volume_stats st = vr.volumeStatistics(sp);
+            if (!write_stats_json(stats_file, sp, st)) throw std::runtime_error("cannot write " + stats_file);
+            if (!stats_hist_file.empty()) {
+                std::ofstream f(stats_hist_file, std::ios::binary);
+                f.write(reinterpret_cast<const char *>(st.hist.data()), std::streamsize(st.hist.size() * sizeof(uint64_t)));
+                if (!f) throw std::runtime_error("cannot write " + stats_hist_file);
+            }
+            std::printf("{\"device\": \"%s\", \"stats\": \"%s\", \"voxels\": %llu, \"binned\": %llu}\n",
+                        vr.getCurrentDeviceName().c_str(), stats_file.c_str(), (unsigned long long)st.voxels,
+                        (unsigned long long)st.binned);
             return 0;
         }
         if (ranks > 0) {

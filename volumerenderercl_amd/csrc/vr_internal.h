@@ -495,6 +495,39 @@ hipError_t vr_launch_mesh_vertex_emit(const MeshLaunch &a, const uint32_t *vcoun
 hipError_t vr_launch_mesh_index_emit(const MeshLaunch &a, const uint32_t *counts, const unsigned long long *offsets,
                                      const unsigned long long *slots, const unsigned long long *row_masks,
                                      const uint32_t *row_bases, uint32_t *indices, hipStream_t stream);
+// volume statistics (vrhip_volume_statistics): the blocks of 8^3 voxels b0 + (0 .. nb - 1) per axis, x fastest, of
+// which the voxels lo <= v < hi are classified (lo < hi <= res, every block holds one).  cell_minmax as for MeshLaunch.
+// lds_hist: the workgroups keep the table in (dynamic) LDS and flush it; else every count goes to `hist` at once.
+// vr_stats.hip
+struct StatsLaunch {
+    VolView vol;
+    int format;            // vrhip_format
+    uint32_t lo[3], hi[3];
+    uint32_t b0[3], nb[3];
+    uint32_t bins_v, bins_g;
+    float v_lo, v_hi, k_v, k_g;
+    bool moments, lds_hist;
+    const float2 *cell_minmax;
+    int cell_shift, cell_cx, cell_cy;
+    int num_cus;
+};
+// a block's, a chunk's or the call's moments
+struct StatsRec {
+    double sum, sum_sq;
+    float mn, mx;
+};
+// counters[]: 64-bit words the launch adds to
+enum { kStatsNan = 0, kStatsBelow, kStatsAbove, kStatsGradNan, kStatsBinned, kStatsFetched, kStatsSkipConst, kStatsSkipWindow,
+       kStatsCounters };
+constexpr uint32_t kStatsChunk = VRHIP_STATS_SUM_CHUNK;   // blocks per workgroup = per chunk of the moments' sum
+constexpr uint32_t kStatsLdsBins = 16384;                 // the largest table a workgroup keeps in LDS (64 KiB)
+inline size_t vr_stats_chunks(size_t n_blocks) { return (n_blocks + kStatsChunk - 1) / kStatsChunk; }
+// hist (bins_g * bins_v words) and counters are zero before the launch; chunk_recs: vr_stats_chunks(n_blocks)
+// records, written with a.moments only
+hipError_t vr_launch_stats(const StatsLaunch &a, unsigned long long *hist, unsigned long long *counters,
+                           StatsRec *chunk_recs, hipStream_t stream);
+// the chunk records added in ascending order into *total
+hipError_t vr_launch_stats_total(const StatsRec *chunk_recs, size_t n_chunks, StatsRec *total, hipStream_t stream);
 // the frame launch for a.render.technique
 inline hipError_t vr_launch_frame(const RaycastLaunch &a, hipStream_t stream)
 {

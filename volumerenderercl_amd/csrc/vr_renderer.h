@@ -1,6 +1,6 @@
 // vr_renderer.h -- the host state of one renderer (vrhip_renderer, include/vrhip.h), shared by the units that
 // implement the C ABI: vrhip_api.hip, vrhip_gather.hip, vrhip_ingest_api.hip, vrhip_slice_api.hip, vrhip_depth_api.hip,
-// vrhip_mesh_api.hip.  Host only.
+// vrhip_mesh_api.hip, vrhip_stats_api.hip.  Host only.
 //  * DevBuf / Handle: device memory, events and the stream, freed with the object that holds them;
 //  * grow(): the one place that (re)allocates a renderer's buffer;
 //  * the invalidation functions: one per cause, next to the table of what depends on what.
@@ -252,6 +252,17 @@ struct vrhip_renderer {
     PinnedBuf imesh_totals_host;
     vrhip_indexed_mesh_info imesh_info;
     bool have_imesh_info = false;
+
+    // volume statistics (vrhip_volume_statistics, vrhip_stats_api.hip): the counters and the call's moments in one
+    // device block, the chunks' moment records, for a host destination the table on the device, and the pinned block
+    // all of it is copied through; what the last call did (vrhip_last_stats_info).  Nothing but the allocations is
+    // kept from one call to the next.  Grown on demand, freed with the renderer.  No render, slice, depth or mesh
+    // entry point reads them.
+    DevBuf<unsigned long long> stats_ws, stats_hist_dev;
+    DevBuf<StatsRec> stats_chunks;
+    PinnedBuf stats_host;
+    vrhip_stats_info stats_info;
+    bool have_stats_info = false;
 
     // device-side ingest (vrhip_ingest_raw, vrhip_volume_histogram): the running maximum and the 256 64-bit
     // histogram counters in device memory, the events around its kernels (all created on first use)

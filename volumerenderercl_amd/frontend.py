@@ -484,6 +484,44 @@ def read_ply(path):
     return (vert[:, :3].copy(), vert[:, 3:].copy() if len(props) == 6 else None, face["i"].astype(np.uint32))
 
 
+# ---- volume statistics (include/vrhip.h "volume statistics"; VolumeRenderCL.volume_statistics): from its result to a
+# mean and an isoValue.  Host arithmetic in float64.
+
+def mean_std(stats):
+    """(mean, standard deviation) of the normalised value over the non-NaN voxels of a volume_statistics(...,
+    moments=True) result: sum / n and sqrt(sum_sq / n - mean^2) (population, clamped at 0), n = voxels - nan.
+    No such voxel: (nan, nan)."""
+    n = int(stats["voxels"]) - int(stats["nan"])
+    if n <= 0:
+        return float("nan"), float("nan")
+    mean = float(stats["sum"]) / n
+    return mean, float(np.sqrt(max(float(stats["sum_sq"]) / n - mean * mean, 0.0)))
+
+
+def otsu_threshold(hist_row, v_lo, v_hi):
+    """Otsu's threshold of a 1-D histogram over [v_lo, v_hi] (a row of volume_statistics' table, or its column sum
+    hist.sum(axis=0)): the bin boundary v_lo + k * (v_hi - v_lo) / bins, 1 <= k < bins, that maximises the
+    between-class variance w0 * w1 * (mu0 - mu1)^2 of the bins below and from k on, every bin at its centre; of equal
+    maxima the middle one (a plateau between two separated modes).  An isoValue for setIsoParams / extract_isosurface.
+    Fewer than two occupied bins: the window's centre."""
+    h = np.asarray(hist_row, dtype=np.float64).ravel()
+    bins = h.size
+    width = (float(v_hi) - float(v_lo)) / bins
+    if bins < 2 or np.count_nonzero(h) < 2:
+        return 0.5 * (float(v_lo) + float(v_hi))
+    centres = float(v_lo) + (np.arange(bins) + 0.5) * width
+    w0 = np.cumsum(h)[:-1]                 # the bins below boundary k = 1 .. bins - 1
+    w1 = h.sum() - w0
+    m0 = np.cumsum(h * centres)[:-1]
+    m1 = (h * centres).sum() - m0
+    ok = (w0 > 0) & (w1 > 0)
+    var = np.zeros(bins - 1)
+    var[ok] = w0[ok] * w1[ok] * (m0[ok] / w0[ok] - m1[ok] / w1[ok]) ** 2
+    best = np.flatnonzero(var >= var.max() * (1.0 - 1e-12))
+    k = int(best[(best.size - 1) // 2]) + 1
+    return float(v_lo) + k * width
+
+
 # ---- slice views (include/vrhip.h "slice views"; VolumeRenderCL.render_slices).  The contract is the 80-byte
 # vrhip_slice_params block; the helpers below compute in float64 and store float32.
 

@@ -594,6 +594,49 @@ class VolumeRenderCL:
         self._check(self._lib.vrhip_last_indexed_mesh_info(self._h, C.byref(mi)))
         return mi.as_dict()
 
+    # ---- volume statistics (include/vrhip.h "volume statistics")
+    @staticmethod
+    def _stats_params(bins, window, region, moments):
+        p = _lib.StatsParams()
+        p.bins_v, p.bins_g = int(bins[0]), int(bins[1])
+        p.v_lo, p.v_hi, p.g_hi = float(window[0]), float(window[1]), float(window[2])
+        p.flags = _lib.STATS_MOMENTS if moments else 0
+        if region is not None:
+            lo, hi = region
+            p.lo[:] = [int(v) for v in lo]
+            p.hi[:] = [int(v) for v in hi]
+        return p
+
+    def volume_statistics(self, bins=(256, 1), window=(0.0, 1.0, 1.0), region=None, moments=False, out_dev_ptr=None):
+        """What is in the current time step (vrhip_volume_statistics), computed on the device: (stats, hist).  stats is
+        a dict -- voxels, nan, below, above, gradient_nan, binned, and with moments min, max, sum, sum_sq of the
+        normalised value s (0 without) --, hist a uint64 ndarray [bins_g, bins_v]: value bins over window[0] <= s <=
+        window[1], gradient-magnitude bins (central differences in index space) over [0, window[2]), the top one
+        open-ended.  region = ((x0, y0, z0), (x1, y1, z1)) in voxels, lo <= v < hi; None: the whole volume.
+        frontend.mean_std and frontend.otsu_threshold turn the result into a mean and an isoValue.
+        With out_dev_ptr -- a device address, 16-byte aligned, of bins_g * bins_v 64-bit words -- the table is
+        written there and only stats is returned.  The camera, the technique and the frame buffer are neither read
+        nor touched."""
+        p = self._stats_params(bins, window, region, moments)
+        if self._lib.vrhip_stats_params_check(C.byref(p)) != _lib.OK:   # (before the table is sized by the bins)
+            raise ValueError("volume_statistics: bins, window or gradient range out of range")
+        st = _lib.VolumeStats()
+        if out_dev_ptr is not None:
+            self._check(self._lib.vrhip_volume_statistics(self._h, C.byref(p), C.byref(st), C.c_void_p(int(out_dev_ptr)), 1))
+            return st.as_dict()
+        hist = np.empty((p.bins_g, p.bins_v), dtype=np.uint64)
+        self._check(self._lib.vrhip_volume_statistics(self._h, C.byref(p), C.byref(st), hist.ctypes.data_as(C.c_void_p), 0))
+        return st.as_dict(), hist
+
+    def lastStatsInfo(self):
+        """What the last volume_statistics did (vrhip_last_stats_info): blocks (of 8^3 voxels that hold a voxel of the
+        region), blocks_fetched, blocks_skipped_constant, blocks_skipped_window (by the cell grid, object-order ESS
+        on), scratch_bytes, empty_skip (1: the cell grid was handed to the kernel), hist_path (_lib.STATS_PATH_LDS or
+        _lib.STATS_PATH_GLOBAL) -- as a dict."""
+        si = _lib.StatsInfo()
+        self._check(self._lib.vrhip_last_stats_info(self._h, C.byref(si)))
+        return si.as_dict()
+
     # ---- volume
     def loadVolumeData(self, props, ingest="host"):
         """volumerendercl.cpp:765-805. `props` is a datraw.Properties (dat_file_name or
