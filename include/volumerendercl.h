@@ -259,6 +259,28 @@ public:
         std::vector<uint64_t> hist;
     };
     volume_stats volumeStatistics(const stats_params &params);
+    // ---- volume filters (no reference counterpart; vrhip.h "volume filters"): channel 0 of the current time step
+    // filtered on the device into time step dstTimestep -- the current one: in place; the number of steps: a new one
+    // (which getResolution() does not count).  Separable: per axis (x, y, z) the radius 0..8 and the weights
+    // taps[axis][k] at distance k, three fp32 passes with neighbours clamped to the volume; median: the median of
+    // the 3x3x3 neighbourhood.  The ESS bricks are rebuilt when a transfer function is set, as after a load.
+    struct FilterParams {
+        bool median = false;
+        std::array<unsigned int, 3> radius = {{0, 0, 0}};
+        std::array<std::array<float, 9>, 3> taps = {};
+    };
+    struct filter_info {
+        uint64_t blocks = 0, blocksFetched = 0, blocksSkipped = 0, scratchBytes = 0;
+        bool emptySkip = false, inPlace = false;
+    };
+    void filterVolume(const FilterParams &params, size_t dstTimestep);
+    // the current step smoothed in place with a normalised Gaussian of `sigma` voxels along x; the other axes are
+    // scaled by the slice thickness (sigma * thickness[0] / thickness[a]): isotropic in box space.  radius 0:
+    // ceil(3 sigma) per axis, at most 8.
+    void gaussianFilter(double sigma, unsigned int radius = 0);
+    void medianFilter();   // the current step, in place
+    size_t getTimestep() const { return _timestep; }   // the step setTimestep last selected
+    filter_info lastFilterInfo();
     // ---- the progressive path tracer (technique 1), many samples per call (vrhip_render_samples): seeds.size()
     // consecutive iterations of the accumulated image -- sample k with jitter seed seeds[k] at iteration
     // (current iteration + k) -- in as few launch sets as possible, bit for bit what seeds.size() runRaycastNoGL calls

@@ -576,6 +576,67 @@ int vrhip_last_stats_info(const vrhip_renderer *r, vrhip_stats_info *out);
  * reserved -- for callers that validate before they have a device: VRHIP_OK or VRHIP_ERR_INVALID (a NULL p too) */
 int vrhip_stats_params_check(const vrhip_stats_params *p);
 
+/* ---- volume filters: separable smoothing and the 3x3x3 median, computed on the device (DESIGN.md "Volume filters").
+ * Not a technique: vrhip_filter_volume reads channel 0 of the CURRENT time step and writes the whole of time step
+ * dst_timestep, in the volume's own format and resolution.  fp32, every operation rounded on its own, no contraction;
+ * tests/ref/filter_ref.c restates it on the CPU.
+ *  Value: s = (float)raw * inv_max (FLOAT: the raw value) -- the s of the statistics and the isosurface extraction.
+ *  Neighbours: a neighbour's coordinate is clamped to the volume on each axis.
+ *  VRHIP_FILTER_SEPARABLE: three passes on full fp32 fields, x on s gives A, y on A gives B, z on B gives C.  A pass
+ *   along axis a with radius R = radius[a] and taps w = taps[a] computes at point p: acc = w[0] * f(p); then for
+ *   k = 1 .. R ascending acc = acc + w[k] * (f(p - k e_a) + f(p + k e_a)).  A radius-0 axis still multiplies by w[0].
+ *   The taps within the radius must be finite and need not sum to 1; those beyond it are not read.
+ *  VRHIP_FILTER_MEDIAN3: the 14th smallest of the 27 clamped neighbours (the voxel included).  UCHAR and USHORT: of
+ *   the raw integers, stored as it is.  FLOAT: of the order-preserving 32-bit keys of the raw words -- the sign bit
+ *   flipped for words with a clear sign bit, all bits for the others, every NaN mapped to 0xffffffff, above +inf --
+ *   and the word of that key is stored.
+ *  Store.  FLOAT: C (or the median); a zero of either sign is stored as +0, a NaN as 0x7fc00000.  UCHAR / USHORT,
+ *   SEPARABLE: q = C * 255.f (65535.f); q = q > 0.f ? q : 0.f; q = q < 255.f ? q : 255.f (65535.f) -- a NaN, which
+ *   only overflowing taps can make, becomes 0 --; the voxel is (integer)rintf(q), round half to even.
+ *  Destination: dst_timestep is an existing step (the current one: in place) or the number of steps, which appends
+ *   one.  Afterwards it is a step like an uploaded one: its bricks, cells and footprint are stale and
+ *   vrhip_build_bricks is due as after an upload; renderers that share this one's volumes are treated as by an upload
+ *   (an overwritten step: they drop what they derived; an appended step: they are detached).  In place the result is
+ *   written to a scratch of the volume's size and type and then takes the slot's place (swapped in; copied where
+ *   other renderers hold the slot's address); it is the only full-size scratch, and it is freed before the call
+ *   returns.  No full-size fp32 intermediate exists: the passes run on tiles in LDS.
+ *  vrhip_set_object_ess: work goes by blocks of VRHIP_MESH_BLOCK^3 voxels anchored at voxel (0,0,0).  On, a block is
+ *   not fetched where the coarse cells that cover the block dilated by radius[a] voxels per axis (by 1 for the median)
+ *   and clamped to the volume all hold the same finite min == max == c.  SEPARABLE skips only c == 0: every product
+ *   and sum is a zero and a zero is stored as +0 (other constants are fetched: sum(w) * c is not c in fp32).  MEDIAN3
+ *   skips any c and stores it (c == 0: +0).  A cell with a NaN holds (-inf, +inf) and proves nothing.  No byte of the
+ *   destination changes with the switch.
+ *  vrhip_last_filter_info: the blocks of the last call, how many were fetched and skipped, the device scratch the
+ *   call held (the in-place copy; 16 bytes of counters), whether the cell grid was handed over, whether it ran in place.
+ *  vrhip_filter_gaussian_taps, in double: t_k = exp(-(k * k) / (2 sigma^2)), S = t_0 + 2 * (t_1 + ... + t_R) added in
+ *   ascending order, taps[k] = (float)(t_k / S) for k <= radius and 0 above.  A convenience: taps are inputs.
+ *  State: reads the volume, the time step and the object-ESS switch.  Nothing that a render, slice, depth, mesh or
+ *   statistics call of ANOTHER step reads later changes, beyond what an upload into dst_timestep changes.
+ *  VRHIP_ERR_INVALID: a NULL r or p (the tap helper: NULL taps, sigma not finite or <= 0, radius > 8); an unknown
+ *   kind; a radius above VRHIP_FILTER_MAX_RADIUS, or a non-zero radius with MEDIAN3; a non-finite tap within the
+ *   radius (SEPARABLE); reserved != 0; dst_timestep above the number of steps.  VRHIP_ERR_UNSUPPORTED: RG / RGBA
+ *   volumes; a renderer whose volumes are borrowed (vrhip_share_volumes) -- checked before anything is touched.
+ *   VRHIP_ERR_NODATA: no volume; vrhip_last_filter_info before the first call. */
+#define VRHIP_FILTER_MAX_RADIUS 8u
+enum { VRHIP_FILTER_SEPARABLE = 0, VRHIP_FILTER_MEDIAN3 = 1 };
+typedef struct vrhip_filter_params {
+    uint32_t kind;                                   /* VRHIP_FILTER_* */
+    uint32_t radius[3];                              /* SEPARABLE: 0..8 per axis (x, y, z); MEDIAN3: must be 0 */
+    float    taps[3][VRHIP_FILTER_MAX_RADIUS + 1];   /* taps[a][k] = weight at distance k on axis a, symmetric */
+    uint32_t reserved[4];                            /* must be 0 */
+} vrhip_filter_params;                               /* 140 bytes */
+int vrhip_filter_volume(vrhip_renderer *r, const vrhip_filter_params *p, uint32_t dst_timestep);
+/* the checks of vrhip_filter_volume that need neither a renderer nor a volume -- kind, radii, taps, reserved:
+ * VRHIP_OK or VRHIP_ERR_INVALID (a NULL p too) */
+int vrhip_filter_params_check(const vrhip_filter_params *p);
+int vrhip_filter_gaussian_taps(double sigma, uint32_t radius, float taps[VRHIP_FILTER_MAX_RADIUS + 1]);
+typedef struct vrhip_filter_info {
+    uint64_t blocks, blocks_fetched, blocks_skipped;
+    uint64_t scratch_bytes;
+    uint32_t empty_skip, in_place;
+} vrhip_filter_info;                                 /* 40 bytes */
+int vrhip_last_filter_info(const vrhip_renderer *r, vrhip_filter_info *out);
+
 /* createEnvironmentMap (volumerendercl.cpp:1121-1150): float RGBA texels, row-major, width*height*4
  * floats (the host layer decodes the Radiance .hdr file).  The kernel samples it in place of the
  * background colour when it is wider than one texel (volumeraycast.cl:506-510, :655-656);

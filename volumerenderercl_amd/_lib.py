@@ -145,6 +145,26 @@ class StatsInfo(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+# vrhip_filter_params.kind and the largest radius (volume filters, vrhip_filter_volume)
+FILTER_SEPARABLE, FILTER_MEDIAN3 = 0, 1
+FILTER_MAX_RADIUS = 8
+
+
+class FilterParams(C.Structure):
+    """vrhip_filter_params: the kind, the radii and the taps of a vrhip_filter_volume call."""
+    _fields_ = [("kind", C.c_uint32), ("radius", C.c_uint32 * 3), ("taps", (C.c_float * (FILTER_MAX_RADIUS + 1)) * 3),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class FilterInfo(C.Structure):
+    """vrhip_filter_info: what the last vrhip_filter_volume did."""
+    _fields_ = [("blocks", C.c_uint64), ("blocks_fetched", C.c_uint64), ("blocks_skipped", C.c_uint64),
+                ("scratch_bytes", C.c_uint64), ("empty_skip", C.c_uint32), ("in_place", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class Stats(C.Structure):
     _fields_ = [("samples_taken", C.c_uint64), ("samples_nominal", C.c_uint64),
                 ("samples_shaded", C.c_uint64), ("bricks_visited", C.c_uint64),
@@ -172,6 +192,7 @@ assert C.sizeof(SliceParams) == 80
 assert C.sizeof(DepthParams) == 32 and C.sizeof(DepthInfo) == 32
 assert C.sizeof(MeshParams) == 48 and C.sizeof(MeshInfo) == 32 and C.sizeof(IndexedMeshInfo) == 64
 assert C.sizeof(StatsParams) == 64 and C.sizeof(VolumeStats) == 72 and C.sizeof(StatsInfo) == 48
+assert C.sizeof(FilterParams) == 140 and C.sizeof(FilterInfo) == 40
 
 _H = C.c_void_p
 _U3 = C.POINTER(C.c_uint32)
@@ -257,6 +278,10 @@ SYMBOLS = {
     "vrhip_volume_statistics": (C.c_int, [_H, C.POINTER(StatsParams), C.POINTER(VolumeStats), C.c_void_p, C.c_int]),
     "vrhip_last_stats_info": (C.c_int, [_H, C.POINTER(StatsInfo)]),
     "vrhip_stats_params_check": (C.c_int, [C.POINTER(StatsParams)]),
+    "vrhip_filter_volume": (C.c_int, [_H, C.POINTER(FilterParams), C.c_uint32]),
+    "vrhip_filter_params_check": (C.c_int, [C.POINTER(FilterParams)]),
+    "vrhip_filter_gaussian_taps": (C.c_int, [C.c_double, C.c_uint32, C.POINTER(C.c_float)]),
+    "vrhip_last_filter_info": (C.c_int, [_H, C.POINTER(FilterInfo)]),
     "vrhip_render_tiles": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_void_p, C.c_uint32, C.c_void_p]),
     "vrhip_set_environment_map": (C.c_int, [_H, C.c_void_p, C.c_uint32, C.c_uint32]),

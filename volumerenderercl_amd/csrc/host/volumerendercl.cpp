@@ -803,6 +803,61 @@ VolumeRenderCL::volume_stats VolumeRenderCL::volumeStatistics(const stats_params
     return out;
 }
 
+void VolumeRenderCL::filterVolume(const FilterParams &params, size_t dstTimestep)
+{
+    if (!_volLoaded) throw std::runtime_error("No volume data is loaded.");
+    vrhip_filter_params p{};
+    p.kind = params.median ? VRHIP_FILTER_MEDIAN3 : VRHIP_FILTER_SEPARABLE;
+    for (size_t a = 0; a < 3; ++a) {
+        p.radius[a] = params.radius[a];
+        for (size_t k = 0; k <= VRHIP_FILTER_MAX_RADIUS; ++k) p.taps[a][k] = params.taps[a][k];
+    }
+    if (vrhip_filter_params_check(&p) != VRHIP_OK) throw std::invalid_argument("filterVolume: radius or taps out of range");
+    check("filterVolume", vrhip_filter_volume(_r, &p, uint32_t(dstTimestep)));
+    if (!_tff.empty()) generateBricks();
+    if (dstTimestep == _timestep) _rendering_params.iteration = 0;
+}
+
+void VolumeRenderCL::gaussianFilter(double sigma, unsigned int radius)
+{
+    if (!(std::isfinite(sigma) && sigma > 0.0) || radius > VRHIP_FILTER_MAX_RADIUS)
+        throw std::invalid_argument("gaussianFilter: sigma must be finite and positive, radius at most 8");
+    double thickness[3] = {1.0, 1.0, 1.0};
+    if (!_synthetic && _dr.has_data())
+        for (size_t a = 0; a < 3; ++a) thickness[a] = _dr.properties().slice_thickness.at(a);
+    FilterParams fp;
+    for (size_t a = 0; a < 3; ++a) {
+        const double s = thickness[a] > 0.0 ? sigma * thickness[0] / thickness[a] : sigma;
+        const unsigned int r = radius ? radius : unsigned(std::min(std::ceil(3.0 * s), double(VRHIP_FILTER_MAX_RADIUS)));
+        float w[VRHIP_FILTER_MAX_RADIUS + 1];
+        if (vrhip_filter_gaussian_taps(s, r, w) != VRHIP_OK) throw std::invalid_argument("gaussianFilter: sigma out of range");
+        fp.radius[a] = r;
+        for (size_t k = 0; k <= VRHIP_FILTER_MAX_RADIUS; ++k) fp.taps[a][k] = w[k];
+    }
+    filterVolume(fp, _timestep);
+}
+
+void VolumeRenderCL::medianFilter()
+{
+    FilterParams fp;
+    fp.median = true;
+    filterVolume(fp, _timestep);
+}
+
+VolumeRenderCL::filter_info VolumeRenderCL::lastFilterInfo()
+{
+    vrhip_filter_info fi{};
+    check("lastFilterInfo", vrhip_last_filter_info(_r, &fi));
+    filter_info out;
+    out.blocks = fi.blocks;
+    out.blocksFetched = fi.blocks_fetched;
+    out.blocksSkipped = fi.blocks_skipped;
+    out.scratchBytes = fi.scratch_bytes;
+    out.emptySkip = fi.empty_skip != 0;
+    out.inPlace = fi.in_place != 0;
+    return out;
+}
+
 void VolumeRenderCL::renderSlicesRGBA8(size_t width, size_t height, const std::vector<slice_params> &slices,
                                        float *dev_frames, unsigned char *out, bool outIsDevice)
 {

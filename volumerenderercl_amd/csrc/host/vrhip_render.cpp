@@ -514,6 +514,15 @@ void write_rgba8(const std::string &out, const std::vector<unsigned char> &frame
         "                                           needs no --size, camera or --out; not with a render, slice, depth or\n"
         "                                           mesh option, --ranks, --frames, --rgba8, --downsample; the other\n"
         "                                           --stats-* options need --stats)\n"
+        "         [--filter gauss SIGMA [RADIUS]] [--filter median] [--filter taps FILE]\n"
+        "                                          (filter the loaded time step on the device, in place, before whatever\n"
+        "                                           else the command does -- a render, --mesh, --stats, slices, depth --\n"
+        "                                           and rebuild the ESS bricks; repeatable, applied in order; gauss: a\n"
+        "                                           normalised Gaussian of SIGMA voxels along x, scaled per axis by the\n"
+        "                                           slice thickness, RADIUS 1-8 (default ceil(3 sigma), at most 8);\n"
+        "                                           median: the 3x3x3 median; taps: FILE holds three lines, for x, y and\n"
+        "                                           z, of 1 to 9 weights each, the weight at distance 0 first; honours\n"
+        "                                           --timestep where that is allowed; not with --ranks, --downsample)\n"
         "writes PREFIX.rgba.f32 (W*H*4 float32, row 0 = top), PREFIX.ppm and prints one JSON line\n";
     std::exit(2);
 }
@@ -547,6 +556,48 @@ bool write_stats_json(const std::string &path, const VolumeRenderCL::stats_param
     f << "]}\n";
     f.flush();
     return bool(f);
+}
+
+// --filter: one entry per occurrence, in the order given
+struct FilterSpec {
+    enum { GAUSS, MEDIAN, TAPS } kind = GAUSS;
+    double sigma = 1.0;
+    unsigned radius = 0;                    // GAUSS: 0 = by sigma
+    VolumeRenderCL::FilterParams taps;      // TAPS
+};
+
+// --filter taps FILE: three lines (x, y, z) of 1 to 9 finite weights, distance 0 first; '#' starts a comment line
+bool read_filter_taps(const std::string &path, VolumeRenderCL::FilterParams &fp)
+{
+    std::ifstream f(path);
+    if (!f) return false;
+    std::string line;
+    size_t axis = 0;
+    while (std::getline(f, line)) {
+        const size_t first = line.find_first_not_of(" \t\r");
+        if (first == std::string::npos || line[first] == '#') continue;
+        if (axis == 3) return false;
+        std::istringstream in(line);
+        double w;
+        size_t n = 0;
+        while (in >> w) {
+            if (n == 9 || !std::isfinite(float(w))) return false;
+            fp.taps[axis][n++] = float(w);
+        }
+        if (!in.eof() || n == 0) return false;
+        fp.radius[axis] = unsigned(n - 1);
+        ++axis;
+    }
+    return axis == 3;
+}
+
+void apply_filters(VolumeRenderCL &vr, const std::vector<FilterSpec> &filters)
+{
+    for (const FilterSpec &fs : filters) {
+        if (fs.kind == FilterSpec::GAUSS) vr.gaussianFilter(fs.sigma, fs.radius);
+        else if (fs.kind == FilterSpec::MEDIAN) vr.medianFilter();
+        else vr.filterVolume(fs.taps, vr.getTimestep());
+    }
 }
 
 } // namespace
@@ -601,6 +652,7 @@ int main(int argc, char **argv)
     std::string stats_file, stats_hist_file;
     long stats_bins[2] = {256, 1}, stats_region[6] = {0, 0, 0, 0, 0, 0};
     double stats_window[3] = {0.0, 1.0, 1.0};
+    std::vector<FilterSpec> filters;   // --filter
 
     auto need = [&](int i, int n) { if (i + n >= argc) usage(); };
     for (int i = 1; i < argc; ++i) {
@@ -698,6 +750,31 @@ int main(int argc, char **argv)
         }
         else if (a == "--stats-moments") have_stats_opt = stats_moments = true;
         else if (a == "--stats-hist") { need(i, 1); stats_hist_file = argv[++i]; have_stats_opt = true; }
+        else if (a == "--filter") {
+            need(i, 1);
+            const std::string what = argv[++i];
+            FilterSpec fs;
+            if (what == "gauss") {
+                need(i, 1);
+                fs.kind = FilterSpec::GAUSS;
+                fs.sigma = std::atof(argv[++i]);
+                if (!(std::isfinite(fs.sigma) && fs.sigma > 0.0)) usage();
+                if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {   // (an option starts with '-')
+                    const long rad = std::atol(argv[++i]);
+                    if (rad < 1 || rad > 8) usage();
+                    fs.radius = unsigned(rad);
+                }
+            } else if (what == "median") fs.kind = FilterSpec::MEDIAN;
+            else if (what == "taps") {
+                need(i, 1);
+                fs.kind = FilterSpec::TAPS;
+                if (!read_filter_taps(argv[++i], fs.taps)) {
+                    std::fprintf(stderr, "--filter taps: %s does not hold three lines of 1 to 9 finite weights\n", argv[i]);
+                    return 2;
+                }
+            } else usage();
+            filters.push_back(fs);
+        }
         else if (a == "--timestep") { need(i, 1); timestep = std::atol(argv[++i]); have_timestep = true; }
         else usage();
     }
@@ -745,6 +822,7 @@ int main(int argc, char **argv)
     if ((mesh_normals || have_mesh_region || mesh_indexed) && !mesh) usage();
     if (have_timestep && !mesh && !stats) usage();
     if (have_stats_opt && !stats) usage();
+    if (!filters.empty() && (ranks > 0 || downsample)) usage();
     if (stats) {
         // numbers about the volume, not a picture of it: as for --mesh, and not with it
         if (mesh || pathtrace || mip || iso || have_iso_refine || slicing || have_slab || have_stack || slice_value || depth ||
@@ -852,6 +930,10 @@ int main(int argc, char **argv)
                                           : synth_fmt == "FLOAT" ? DatRawReader::FLOAT : DatRawReader::UCHAR;
             vr.loadSyntheticVolume(synth_kind, synth_n, f);
         }
+        if (!filters.empty()) {
+            vr.setObjEss(ess);
+            apply_filters(vr, filters);
+        }
         if (downsample) {   // volumeDownsampling (volumerendercl.cpp:238-341) and nothing else
             const std::string base = vr.volumeDownsampling(0, downsample);
             std::printf("{\"downsampled\": \"%s\"}\n", base.c_str());
@@ -952,6 +1034,7 @@ int main(int argc, char **argv)
             }
             vr.setObjEss(ess);
             if (have_timestep) vr.setTimestep(size_t(timestep));
+            apply_filters(vr, filters);
             VolumeRenderCL::mesh_region region;
             if (have_mesh_region)
                 for (size_t k = 0; k < 3; ++k) { region.lo[k] = unsigned(mesh_region[k]); region.hi[k] = unsigned(mesh_region[3 + k]); }
@@ -992,6 +1075,7 @@ int main(int argc, char **argv)
             }
             vr.setObjEss(ess);
             if (have_timestep) vr.setTimestep(size_t(timestep));
+            apply_filters(vr, filters);
             VolumeRenderCL::stats_params sp;
             sp.vBins = unsigned(stats_bins[0]);
             sp.gBins = unsigned(stats_bins[1]);

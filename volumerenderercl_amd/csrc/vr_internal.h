@@ -528,6 +528,27 @@ hipError_t vr_launch_stats(const StatsLaunch &a, unsigned long long *hist, unsig
                            StatsRec *chunk_recs, hipStream_t stream);
 // the chunk records added in ascending order into *total
 hipError_t vr_launch_stats_total(const StatsRec *chunk_recs, size_t n_chunks, StatsRec *total, hipStream_t stream);
+// volume filters (vrhip_filter_volume): every block of 8^3 voxels of `vol` (x fastest) filtered into `dst`, a
+// micro-bricked volume of the same layout and type that is not `vol.data`.  cell_minmax as for MeshLaunch: the
+// (min, max) of vol's coarse cells, or nullptr: every block is fetched.  vr_filter.hip
+struct FilterLaunch {
+    VolView vol;
+    int format;            // vrhip_format
+    uint32_t kind;         // VRHIP_FILTER_*
+    uint32_t radius[3];
+    float taps[3][VRHIP_FILTER_MAX_RADIUS + 1];
+    const float2 *cell_minmax;
+    int cell_shift, cell_cx, cell_cy, cell_cz;
+    int num_cus;
+};
+// counters[]: 64-bit words the launch adds to
+enum { kFilterFetched = 0, kFilterSkipped, kFilterCounters };
+inline size_t vr_filter_blocks(const VolView &v)
+{
+    return (size_t)((v.w + 7) / 8) * (size_t)((v.h + 7) / 8) * (size_t)((v.d + 7) / 8);
+}
+// counters are zero before the launch
+hipError_t vr_launch_filter(const FilterLaunch &a, void *dst, unsigned long long *counters, hipStream_t stream);
 // the frame launch for a.render.technique
 inline hipError_t vr_launch_frame(const RaycastLaunch &a, hipStream_t stream)
 {

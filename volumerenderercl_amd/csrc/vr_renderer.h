@@ -1,6 +1,6 @@
 // vr_renderer.h -- the host state of one renderer (vrhip_renderer, include/vrhip.h), shared by the units that
 // implement the C ABI: vrhip_api.hip, vrhip_gather.hip, vrhip_ingest_api.hip, vrhip_slice_api.hip, vrhip_depth_api.hip,
-// vrhip_mesh_api.hip, vrhip_stats_api.hip.  Host only.
+// vrhip_mesh_api.hip, vrhip_stats_api.hip, vrhip_filter_api.hip.  Host only.
 //  * DevBuf / Handle: device memory, events and the stream, freed with the object that holds them;
 //  * grow(): the one place that (re)allocates a renderer's buffer;
 //  * the invalidation functions: one per cause, next to the table of what depends on what.
@@ -263,6 +263,13 @@ struct vrhip_renderer {
     PinnedBuf stats_host;
     vrhip_stats_info stats_info;
     bool have_stats_info = false;
+
+    // volume filters (vrhip_filter_volume, vrhip_filter_api.hip): the counters of a call in device memory, and what
+    // the last call did (vrhip_last_filter_info).  The in-place scratch lives only inside a call.  No render, slice,
+    // depth, mesh or statistics entry point reads them.
+    DevBuf<unsigned long long> filter_ws;
+    vrhip_filter_info filter_info;
+    bool have_filter_info = false;
 
     // device-side ingest (vrhip_ingest_raw, vrhip_volume_histogram): the running maximum and the 256 64-bit
     // histogram counters in device memory, the events around its kernels (all created on first use)

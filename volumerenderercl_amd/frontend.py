@@ -522,6 +522,28 @@ def otsu_threshold(hist_row, v_lo, v_hi):
     return float(v_lo) + k * width
 
 
+# ---- volume filters (include/vrhip.h "volume filters"; VolumeRenderCL.filter_volume)
+
+def gaussian_taps(sigma, radius=None):
+    """The weights w[0 .. radius] of a normalised Gaussian for filter_volume(kind="separable"), float32, as
+    vrhip_filter_gaussian_taps computes them, in float64: t_k = exp(-k^2 / (2 sigma^2)), S = t_0 + 2 (t_1 + ... +
+    t_R) added in ascending order, w_k = t_k / S.  radius None: ceil(3 sigma), at most 8."""
+    sigma = float(sigma)
+    if not (math.isfinite(sigma) and sigma > 0.0):
+        raise ValueError("gaussian_taps: sigma must be finite and positive")
+    if radius is None:
+        radius = min(int(math.ceil(3.0 * sigma)), 8)
+    radius = int(radius)
+    if not 0 <= radius <= 8:
+        raise ValueError("gaussian_taps: radius must be 0..8")
+    t = [math.exp(-(float(k) * float(k)) / (2.0 * sigma * sigma)) for k in range(radius + 1)]
+    tail = 0.0
+    for k in range(1, radius + 1):
+        tail = tail + t[k]
+    total = t[0] + 2.0 * tail
+    return np.array([v / total for v in t], dtype=np.float32)
+
+
 # ---- slice views (include/vrhip.h "slice views"; VolumeRenderCL.render_slices).  The contract is the 80-byte
 # vrhip_slice_params block; the helpers below compute in float64 and store float32.
 

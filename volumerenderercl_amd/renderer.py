@@ -637,6 +637,77 @@ class VolumeRenderCL:
         self._check(self._lib.vrhip_last_stats_info(self._h, C.byref(si)))
         return si.as_dict()
 
+    # ---- volume filters (include/vrhip.h "volume filters")
+    @staticmethod
+    def _filter_params(kind, taps, radius):
+        p = _lib.FilterParams()
+        kinds = {"separable": _lib.FILTER_SEPARABLE, "median3": _lib.FILTER_MEDIAN3}
+        if kind not in kinds:
+            raise ValueError("filter_volume: kind must be 'separable' or 'median3'")
+        p.kind = kinds[kind]
+        if kind == "median3":
+            if taps is not None or (radius is not None and any(int(v) for v in np.atleast_1d(radius))):
+                raise ValueError("filter_volume: the median takes neither taps nor a radius")
+            return p
+        if taps is None:
+            raise ValueError("filter_volume: separable needs taps")
+        taps = list(taps)
+        if len(taps) and np.isscalar(taps[0]):   # one tap vector: the same on every axis
+            taps = [taps, taps, taps]
+        if len(taps) != 3:
+            raise ValueError("filter_volume: taps is one sequence of weights, or one per axis")
+        taps = [np.asarray(t, dtype=np.float32).ravel() for t in taps]
+        if radius is None:
+            radius = [max(t.size - 1, 0) for t in taps]
+        elif np.isscalar(radius):
+            radius = [radius] * 3
+        radius = [int(v) for v in radius]
+        for a in range(3):
+            if not 0 <= radius[a] <= _lib.FILTER_MAX_RADIUS or taps[a].size < radius[a] + 1:
+                raise ValueError("filter_volume: a radius is 0..8 and needs radius + 1 taps")
+            p.radius[a] = radius[a]
+            for k in range(radius[a] + 1):
+                p.taps[a][k] = float(taps[a][k])
+        return p
+
+    def filter_volume(self, kind="separable", taps=None, radius=None, dst=None):
+        """Filter channel 0 of the current time step on the device (vrhip_filter_volume) into time step dst -- None:
+        the current one, in place; the number of steps: a new one.  kind "separable": taps is one sequence of weights
+        w[0 .. R] (the weight at distance k, used on both sides) for all axes or one per axis (x, y, z), radius the
+        R per axis (None: len(taps) - 1); three fp32 passes x, y, z with neighbours clamped to the volume
+        (frontend.gaussian_taps makes Gaussian weights).  kind "median3": the median of the 3x3x3 neighbourhood.
+        The destination is a step like an uploaded one: the ESS bricks are rebuilt here, as loadVolumeData does,
+        when a transfer function is set.  Returns dst."""
+        if not self._vol_loaded:
+            raise RuntimeError("No volume data is loaded.")
+        p = self._filter_params(kind, taps, radius)
+        if self._lib.vrhip_filter_params_check(C.byref(p)) != _lib.OK:
+            raise ValueError("filter_volume: radius or taps out of range")
+        dst = self._timestep if dst is None else int(dst)
+        self._check(self._lib.vrhip_filter_volume(self._h, C.byref(p), dst))
+        if dst >= self._res[3]:
+            self._res[3] = dst + 1
+        if self._histograms:
+            h = self.volumeHistogram(dst)
+            if dst < len(self._histograms):
+                self._histograms[dst] = h
+            else:
+                self._histograms.append(h)
+        if getattr(self, "_tff", None) is not None:
+            self._generate_bricks()
+        if dst == self._timestep:
+            self._rendering.iteration = 0
+        return dst
+
+    def lastFilterInfo(self):
+        """What the last filter_volume did (vrhip_last_filter_info): blocks (of 8^3 voxels), blocks_fetched,
+        blocks_skipped (constant by the cell grid, object-order ESS on), scratch_bytes (device memory the call held:
+        the in-place copy and the counters), empty_skip (1: the cell grid was handed to the kernel), in_place -- as a
+        dict."""
+        fi = _lib.FilterInfo()
+        self._check(self._lib.vrhip_last_filter_info(self._h, C.byref(fi)))
+        return fi.as_dict()
+
     # ---- volume
     def loadVolumeData(self, props, ingest="host"):
         """volumerendercl.cpp:765-805. `props` is a datraw.Properties (dat_file_name or
