@@ -44,7 +44,9 @@ public:
     enum scaling_metric { MIN = 0, MAX, AVG, DENSITY };
     // TECH_MIP: maximum intensity projection (VRHIP_TECHNIQUE_MIP, vrhip.h; no reference counterpart)
     // TECH_ISO: first-hit isosurface (VRHIP_TECHNIQUE_ISO, vrhip.h; no reference counterpart; 3 is unassigned)
-    enum technique { TECH_RAYCAST = 0, TECH_PATHTRACE = 1, TECH_MIP = 2, TECH_ISO = 4 };
+    // TECH_TF2D: ray casting through a 2-D transfer function (VRHIP_TECHNIQUE_TF2D, vrhip.h; no reference counterpart;
+    //   5 is unassigned)
+    enum technique { TECH_RAYCAST = 0, TECH_PATHTRACE = 1, TECH_MIP = 2, TECH_ISO = 4, TECH_TF2D = 6 };
 
     VolumeRenderCL();
     ~VolumeRenderCL();
@@ -91,6 +93,14 @@ public:
     // 0.5), and the bisection rounds that refine the hit (0-16, default 4); vrhip_iso_params
     void setIsoValue(float isoValue);
     void setIsoRefinement(unsigned int refineSteps);
+    // TECH_TF2D (no reference counterpart): the n_v x n_g RGBA8 table, value fastest, and the gradient magnitude of
+    // its upper edge (vrhip_set_transfer_function_2d; the gHi of volumeStatistics' histogram).  Throws on a table of
+    // another size than 4 * nV * nG bytes.
+    void setTransferFunction2D(const std::vector<unsigned char> &table, unsigned int nV, unsigned int nG, float gHi);
+    // ... and the one such table to be had without an editor: the rows are `tff` (4 * nV bytes), their alpha scaled by
+    // a ramp over the gradient magnitude that is 0 up to g0 and 1 from g1 on (vrhip_tf2d_build_ramp).  Host only.
+    static std::vector<unsigned char> rampTransferFunction2D(const std::vector<unsigned char> &tff, unsigned int nG,
+                                                             float gHi, float g0, float g1);
     void setBBox(float bl_x, float bl_y, float bl_z, float tr_x, float tr_y, float tr_z);
     void setTimestep(const size_t t);
 
@@ -336,6 +346,9 @@ private:
     int _channels = 1;          // 1 = R, 2 = RG, 4 = RGBA (volDataToCLmem, :697-705)
     std::vector<unsigned char> _tff;          // what setTransferFunction / setTffPrefixSum were last given
     std::vector<unsigned int> _tffPrefixSum;  // (shareVolumes hands them to the twin)
+    std::vector<unsigned char> _tf2d;         // what setTransferFunction2D was last given (likewise)
+    unsigned int _tf2dNV = 0, _tf2dNG = 0;
+    float _tf2dGHi = 0.f;
     bool _objEss = true;
     int _device = 0;
     unsigned int _roundBudget = 0;            // 0 = the library's default

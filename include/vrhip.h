@@ -55,7 +55,8 @@ typedef struct vrhip_rendering_params {
     uint32_t useLinear;
     uint32_t useGradient;
     uint32_t technique;  /* 0 ray cast, 1 path tracing, 2 maximum intensity projection (VRHIP_TECHNIQUE_MIP),
-                            4 first-hit isosurface (VRHIP_TECHNIQUE_ISO); 3 is unassigned and rejected */
+                            4 first-hit isosurface (VRHIP_TECHNIQUE_ISO), 6 two-dimensional transfer function
+                            (VRHIP_TECHNIQUE_TF2D); 3 and 5 are unassigned and rejected */
     uint32_t seed;
     uint32_t iteration;
 } vrhip_rendering_params; /* 64 bytes */
@@ -108,6 +109,51 @@ typedef struct vrhip_iso_params {
     uint32_t refineSteps;
     uint32_t reserved[2];
 } vrhip_iso_params; /* 16 bytes */
+
+/* rendering_params.technique == 6: emission-absorption ray casting through a TWO-DIMENSIONAL transfer function,
+ * TF2(value, gradient magnitude) (Kniss et al.; no reference counterpart).  The values 3 and 5 are
+ * unassigned: they answer "Unknown rendering technique." like every other value.
+ *  Table (vrhip_set_transfer_function_2d): n_v x n_g RGBA8 entries, value fastest: T[j * n_v + i].  1 <= n_v <= 4096,
+ *   1 <= n_g <= 256, n_v * n_g <= 65536 -- the limits of the statistics histogram; g_hi finite and > 0: the gradient
+ *   magnitude that maps to the upper edge of the table, the same axis as vrhip_stats_params.g_hi.  Texel (i, j) is
+ *   the colour at the CENTRE of histogram bin (i, j) of vrhip_volume_statistics called with the window [0, 1],
+ *   bins_v = n_v, bins_g = n_g and the same g_hi: a lookup there returns the entry exactly.
+ *  Ray: exactly technique 0's with object-order ESS off, as for techniques 2 and 4: t_0 = max(0, tnear), sample k at
+ *   cam + dir * (t_k - offset), and the reference's loop: composite sample k; stop when the accumulated alpha, as a
+ *   double, exceeds 0.98; t_{k+1} = t_k + stepSize; go on while t_{k+1} < tfar (a step that no longer changes t ends
+ *   the sequence).
+ *  Sample: s = the filtered, normalised channel-0 value (useLinear: trilinear or nearest; FLOAT: the raw value);
+ *   G = s2 - s1, the ray caster's six-tap central difference (texel space, the centre's trilinear weights on indices
+ *   shifted by -+1 and clamped to the edge, whatever useLinear says); m = 0.5f * sqrtf((G.x * G.x + G.y * G.y) + G.z *
+ *   G.z): at a grid point the m of vrhip_volume_statistics.
+ *  Lookup (vrhip_tf2d_lookup is this on the host), coord(x) = x > -1 ? (x < 2 ? x : 2) : -1 (a NaN reads -1):
+ *   ub = coord(s) * (float)n_v - 0.5f, fu = floorf(ub), a = ub - fu, i0 = clamp((int)fu, 0, n_v - 1),
+ *   i1 = clamp((int)fu + 1, 0, n_v - 1); inv_ghi = 1.0f / g_hi once, y = m * inv_ghi, vb = coord(y) * (float)n_g - 0.5f,
+ *   fv = floorf(vb), b = vb - fv, j0, j1 likewise on n_g; per channel e(j, i) = (float)T[j * n_v + i] / 255.0f,
+ *   r0 = lerpf(e(j0, i0), e(j0, i1), a), r1 = lerpf(e(j1, i0), e(j1, i1), a), c = lerpf(r0, r1, b), with
+ *   lerpf(p, q, w) = fmaf(w, q - p, p).
+ *  Shading and compositing: technique 0's lines.  illumType 1 and c.a > 0.1f: c.rgb = ((c * 0.15) + ((c * ndl) * 0.7))
+ *   + spec per channel with n = -normalize(G) -- (0.57735, 0.57735, 0.57735) negated when G == 0 -- from the taps that
+ *   gave m, ndl = max(0, n . lgt), spec = hvalid ? powr(max(n . hv, 0), 40) * 0.15 : 0.  Then x = bg.rgb - c.rgb,
+ *   opacity = 1 - powr(1 - c.a, 1 / samplingRate), result.rgb -= (x * opacity) * (1 - alpha), alpha += opacity *
+ *   (1 - alpha), from result = bg = backgroundColor and alpha = 0.  Pixel: (result.rgb, alpha), the accumulated alpha
+ *   (as the ray caster reports it).  A ray that misses the box: backgroundColor unchanged, alpha included.
+ *  Ignored: useGradient, contours, aerial, the 1-D transfer function and its prefix sum (neither read nor required).
+ *   VRHIP_ERR_UNSUPPORTED: illumType 2-5, imgEss, showEss, useAO, iteration > 0, RG / RGBA volumes, a set environment
+ *   map, vrhip_render_samples, vrhip_count_touched*, vrhip_count_fetched.  VRHIP_ERR_NODATA "No 2-D transfer function
+ *   set." from the render calls while technique 6 is selected and none is.
+ *  Cost: a sample whose value can only read table columns that are transparent in every row takes neither the
+ *   gradient nor the lookup; vrhip_set_object_ess: on, samples whose cell of the cell grid (vrhip_download_cells)
+ *   proves that are not fetched at all.  No bit of a pixel changes either way (backgroundColor finite).  Needs neither
+ *   ESS bricks nor the prefix sum.
+ *  vrhip_get_stats (vrhip_set_stats_enabled): samples_taken = values fetched, samples_shaded = gradient evaluations,
+ *   bricks_skipped = samples stepped over by the cell bound, rays_hit = rays with alpha > 0; the rest 0.
+ *  State: the 2-D table is state of its own.  Setting it touches nothing a technique 0-4 frame, a slice, depth, mesh,
+ *   statistics or filter call reads; vrhip_set_transfer_function does not touch it. */
+#define VRHIP_TECHNIQUE_TF2D 6u
+#define VRHIP_TF2D_MAX_NV 4096u
+#define VRHIP_TF2D_MAX_NG 256u
+#define VRHIP_TF2D_MAX_ENTRIES 65536u
 
 typedef struct vrhip_raycast_params {
     float samplingRate;
@@ -236,6 +282,24 @@ int vrhip_get_resolution(const vrhip_renderer *r, uint32_t res_xyzt[4]);
 int vrhip_set_transfer_function(vrhip_renderer *r, const uint8_t *rgba8, uint32_t n_entries);
 /* setTffPrefixSum (:898-916) */
 int vrhip_set_tff_prefix_sum(vrhip_renderer *r, const uint32_t *prefix, uint32_t n);
+/* The 2-D transfer function of technique 6 (VRHIP_TECHNIQUE_TF2D above): n_v * n_g RGBA8 entries, value fastest.
+ * VRHIP_ERR_INVALID: a NULL table, or what vrhip_tf2d_params_check refuses.  The table is converted (c / 255.0f) and
+ * its per-column opacity summary made on the host here; nothing else of the renderer changes. */
+int vrhip_set_transfer_function_2d(vrhip_renderer *r, const uint8_t *rgba8, uint32_t n_v, uint32_t n_g, float g_hi);
+/* host only, no renderer: VRHIP_OK, or VRHIP_ERR_INVALID for n_v outside 1..4096, n_g outside 1..256, n_v * n_g above
+ * 65536, or a g_hi that is not finite and > 0 */
+int vrhip_tf2d_params_check(uint32_t n_v, uint32_t n_g, float g_hi);
+/* host only: technique 6's lookup of (s, m) in the table, as stated above, four floats.  VRHIP_ERR_INVALID: a NULL
+ * pointer or refused parameters (out_rgba is not written). */
+int vrhip_tf2d_lookup(const uint8_t *rgba8, uint32_t n_v, uint32_t n_g, float g_hi, float s, float m, float out_rgba[4]);
+/* host only: boundary emphasis from a 1-D table of n_v RGBA8 entries -- the one 2-D table to be had without an
+ * editor.  Row j of out_rgba8 (n_v * n_g entries) is the 1-D table with its alpha scaled by the ramp
+ *   g_j = (((float)j + 0.5f) * g_hi) / (float)n_g,  w = (g_j - g0) / (g1 - g0),  w_j = w < 0 ? 0 : (w > 1 ? 1 : w),
+ *   x = (float)alpha * w_j,  q = floorf(x),  out alpha = (uint8_t)(q + (x - q >= 0.5f ? 1.0f : 0.0f))
+ * (fp32, each operation rounded on its own; x - q is exact: round to nearest, ties away from zero).  rgb is copied.
+ * VRHIP_ERR_INVALID: a NULL pointer, refused n_v / n_g / g_hi, g0 or g1 not finite, g0 < 0 or g1 <= g0. */
+int vrhip_tf2d_build_ramp(const uint8_t *tf1d_rgba8, uint32_t n_v, uint32_t n_g, float g_hi, float g0, float g1,
+                          uint8_t *out_rgba8);
 /* generateBricks host part + kernel for every timestep (:614-684, volumeraycast.cl:932-961);
  * also stores raycast.brickRes like :627-631. */
 int vrhip_build_bricks(vrhip_renderer *r);

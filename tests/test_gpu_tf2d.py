@@ -1,0 +1,478 @@
+"""Technique 6, ray casting through a 2-D transfer function (vr_tf2d.hip), against its CPU restatement
+(tests/ref/tf2d_ref.c, pinned to the oracle by tests/test_tf2d_ref.py) with a difference of exactly 0: frames of every
+voxel type, filter and shading mode with object-order ESS on and off (neither the marginal test nor the cell bound may
+change a bit), the work counters, every entry point that renders, the renderer's state around technique-6 frames, the
+rejections and the CLI."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import common, tf2d_ref
+from volumerenderercl_amd import FLOAT, TECH_RAYCAST, TECH_TF2D, UCHAR, USHORT, VolumeRenderCL, _lib, frontend
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "volumerenderercl_amd", "vrhip_render")
+SEEDS = [3499211612, 581869302, 3890346734]
+BG = [0.1, 0.9, 0.5, 0.25]
+VIEWS = common.views()
+G_HI = 0.12
+
+
+@pytest.fixture(scope="module")
+def vr():
+    r = VolumeRenderCL()
+    r.initialize()
+    yield r
+    r.close()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _bits_one_nan(a):
+    """The fp32 bit patterns, every NaN as one pattern: which NaN an invalid operation makes (a gradient next to a NaN
+    voxel) is the processor's choice, not the definition's."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    return np.where(np.isnan(a), np.uint32(0x7fc00000), a.view(np.uint32))
+
+
+def _same(a, b):
+    return np.array_equal(_bits(a), _bits(b))
+
+
+def _as(fmt, f):
+    if fmt == UCHAR:
+        return np.round(np.clip(f, 0, 1) * 255).astype(np.uint8)
+    if fmt == USHORT:
+        return np.round(np.clip(f, 0, 1) * 65535).astype(np.uint16)
+    return f.astype(np.float32)
+
+
+def _sphere(fmt, n=40):
+    """A ball whose value falls off linearly from the centre: a shell of every value, |gradient| ~ 0.055 per voxel
+    inside, 0 outside."""
+    g = np.linspace(-1, 1, n)
+    zz, yy, xx = np.meshgrid(g, g, g, indexing="ij")
+    return _as(fmt, np.clip(1.0 - np.sqrt(xx * xx + yy * yy + zz * zz) / 0.9, 0, 1))
+
+
+def _value_band_tff(n, lo, hi, alpha=160):
+    """A 1-D table that is transparent outside the entries [lo, hi)."""
+    t = np.zeros((n, 4), np.uint8)
+    t[:, 0] = np.linspace(30, 250, n)
+    t[:, 1] = np.linspace(220, 40, n)
+    t[:, 2] = 90
+    t[lo:hi, 3] = alpha
+    return t
+
+
+def band_table():
+    """256 x 8: opaque only for values in entries 70..150 AND gradient rows 2..5 (a ramp from tf2d_ramp with the rows
+    above cut off): most samples are transparent by value or by gradient."""
+    t = frontend.tf2d_ramp(_value_band_tff(256, 70, 150), 8, G_HI, 0.02, 0.05)
+    t[6:, :, 3] = 0
+    assert np.all(t[0, :, 3] == 0) and np.any(t[3, :, 3] > 0)
+    return t
+
+
+def dense_table():
+    """64 x 1, every entry opaque: every sample is composited and early termination ends the rays."""
+    t = np.zeros((1, 64, 4), np.uint8)
+    t[0, :, 0] = np.arange(64) * 4
+    t[0, :, 1] = 255 - np.arange(64) * 3
+    t[0, :, 2] = 77
+    t[0, :, 3] = 200
+    return t
+
+
+def mixed_table():
+    """7 x 5, random, a third of the entries transparent and columns 0 and 4 transparent in every row."""
+    rng = np.random.default_rng(21)
+    t = rng.integers(0, 256, (5, 7, 4), dtype=np.uint8)
+    t[rng.random((5, 7)) < 0.33, 3] = 0
+    t[:, [0, 4], 3] = 0
+    return t
+
+
+def _setup(vr, vol, fmt, table, g_hi=G_HI, tff=None):
+    vr.loadVolumeArrays([vol], fmt)
+    if tff is not None:
+        vr.setTransferFunction(tff)
+    vr.setTransferFunction2D(table, g_hi)
+    vr.setTechnique(TECH_TF2D)
+    vr.setStatsEnabled(False)
+    vr.params()[1].backgroundColor[:] = BG
+
+
+def _conf(vr, view="rot30", linear=True, ortho=False, rate=1.0, ess=True, seed=SEEDS[0], illum=1):
+    vr.setLinearInterpolation(linear)
+    vr.setCamOrtho(ortho)
+    vr.updateSamplingRate(rate)
+    vr.setBBox(-1, -1, -1, 1, 1, 1)
+    vr.setObjEss(ess)
+    vr.updateView(VIEWS[view] if isinstance(view, str) else view)
+    vr.setSeed(seed)
+    vr.setIteration(0)
+    vr.setIllumination(illum)
+
+
+def _ref(vr, vol, fmt, table, W, H, g_hi=G_HI, tile=None):
+    cam, rp, rc, _ = common.to_oracle_params(*vr.params())
+    rp.iteration = 0
+    return tf2d_ref.render_tile(vol, fmt, table, g_hi, cam, rp, rc, W=W, H=H, tile=tile)
+
+
+def _both_ess(vr, vol, fmt, table, W, H, what, bits=_bits, g_hi=G_HI, **conf):
+    """The frame with ESS on and off: both equal the restatement.  Returns the restatement's result."""
+    ref = None
+    for ess in (True, False):
+        _conf(vr, ess=ess, **conf)
+        img = vr.runRaycastNoGL(W, H)
+        li = vr.lastLaunchInfo()
+        assert li["technique"] == 6 and li["empty_skip"] == int(ess) and li["frames"] == 1 and li["views"] == 0, li
+        assert li["work_items"] == ((W + 7) // 8) * ((H + 7) // 8), li
+        if ref is None:
+            ref = _ref(vr, vol, fmt, table, W, H, g_hi)
+        bad = np.any(bits(img) != bits(ref[0]), axis=-1)
+        assert not bad.any(), "%s, ESS %s: %d pixels differ, first at %s" % (what, ess, bad.sum(), np.argwhere(bad)[0])
+    return ref
+
+
+@pytest.mark.parametrize("illum", [0, 1], ids=["flat", "shaded"])
+@pytest.mark.parametrize("linear", [True, False], ids=["linear", "nearest"])
+@pytest.mark.parametrize("fmt", [UCHAR, USHORT, FLOAT], ids=["uchar", "ushort", "float"])
+def test_frames_equal_restatement(vr, fmt, linear, illum):
+    """An unstructured volume that is no multiple of 8 on any axis with the mixed 7 x 5 table at 43 x 27, and the ball
+    at 40^3 with the gradient-band table (most samples transparent) and the dense table (early termination) at
+    64 x 48: raw bits, ESS on and off."""
+    noise = common.noise_volume((37, 29, 21), fmt, seed=4, smooth=False)
+    _setup(vr, noise, fmt, mixed_table())
+    ref = _both_ess(vr, noise, fmt, mixed_table(), 43, 27, "mixed", linear=linear, illum=illum, view="close", seed=SEEDS[1])
+    assert 0 < ref[3].sum() < ref[2].sum()
+    ball = _sphere(fmt)
+    for name, table, rate in (("band", band_table(), 1.5), ("dense", dense_table(), 1.0)):
+        _setup(vr, ball, fmt, table)
+        ref = _both_ess(vr, ball, fmt, table, 64, 48, name, linear=linear, illum=illum, rate=rate)
+        img, kind, samples, visible, _ = ref
+        assert np.any(kind == tf2d_ref.MARCHED) and visible.sum() > 0
+        if name == "band":
+            assert 2 * visible.sum() < samples.sum()          # most samples are transparent
+        else:
+            assert np.all(visible == samples) and np.any(img[..., 3] >= 0.98)   # all composited, early termination
+
+
+@pytest.mark.parametrize("linear", [True, False], ids=["linear", "nearest"])
+def test_float_volume_outside_unit_range_with_a_nan(vr, linear):
+    """Raw FLOAT values in [-1, 2] and one NaN voxel: the value axis clamps, a NaN value or gradient reads
+    coordinate -1, the NaN's cell is never skipped."""
+    vol = (common.noise_volume((37, 29, 21), FLOAT, seed=9, smooth=False) * 3.0 - 1.0).astype(np.float32)
+    vol[10, 14, 18] = np.nan
+    table = mixed_table()
+    table[:, 0, 3] = 120   # column 0 is what a NaN reads: not transparent
+    _setup(vr, vol, FLOAT, table, g_hi=0.5)
+    for illum in (0, 1):
+        ref = _both_ess(vr, vol, FLOAT, table, 43, 27, "float", bits=_bits_one_nan, g_hi=0.5, linear=linear, illum=illum)
+        assert np.isfinite(ref[0]).all() or illum == 1
+
+
+@pytest.mark.parametrize("linear", [True, False], ids=["linear", "nearest"])
+def test_negative_zero_background(vr, linear):
+    """backgroundColor components of -0.0 on the band scene, where the first samples of most rays are transparent
+    and, with ESS on, stepped over: the one case in which leaving out a transparent sample could change a bit
+    (-0 - (-0) = +0; vr_tf2d.hip's header).  A ray that misses the box keeps -0; a ray that marches has +0 from its
+    first sample on, whether it composites anything or not -- the restatement, which fetches every sample, shows
+    both, and the kernel equals it with ESS on and off."""
+    fmt = UCHAR
+    ball = _sphere(fmt)
+    table = band_table()
+    _setup(vr, ball, fmt, table)
+    try:
+        vr.params()[1].backgroundColor[:] = [-0.0, 0.9, -0.0, 0.25]
+        for illum in (0, 1):
+            img, kind, samples, visible, _ = _both_ess(vr, ball, fmt, table, 64, 48, "-0 background", linear=linear,
+                                                       illum=illum, rate=1.5)
+            red = _bits(img)[..., 0]
+            missed = kind == tf2d_ref.MISS
+            nothing = (kind == tf2d_ref.MARCHED) & (samples > 0) & (visible == 0)
+            assert missed.any() and np.all(red[missed] == 0x80000000)        # untouched: -0
+            assert nothing.any() and np.all(red[nothing] == 0)               # marched, all transparent: +0
+            assert np.all(_bits(img)[..., 2][nothing] == 0) and np.all(img[..., 3][nothing] == 0)
+    finally:
+        vr.params()[1].backgroundColor[:] = BG
+
+
+def test_counters(vr):
+    """ESS off: values fetched == the restatement's samples, gradient evaluations == its samples that read a column
+    which is not transparent in every row.  ESS on, on the band scene (the restatement shows more than half of the
+    samples transparent): samples are stepped over by the cell bound, strictly fewer values are fetched, every sample is
+    either fetched or stepped over, and the frame does not change."""
+    fmt = UCHAR
+    ball = _sphere(fmt)
+    table = band_table()
+    _setup(vr, ball, fmt, table)
+    W, H = 64, 48
+    vr.setStatsEnabled(True)
+    try:
+        frames, stats = {}, {}
+        for ess in (False, True):
+            _conf(vr, ess=ess, rate=1.5)
+            frames[ess] = vr.runRaycastNoGL(W, H)
+            stats[ess] = vr.getStats()
+            assert vr.lastLaunchInfo()["instrumented"] == 1
+        img, kind, samples, visible, marginal = _ref(vr, ball, fmt, table, W, H)
+        assert 2 * visible.sum() < samples.sum()                       # (checked here, on the CPU)
+        assert _same(frames[False], img) and _same(frames[True], img)
+        off, on = stats[False], stats[True]
+        assert off["samples_taken"] == int(samples.sum()) and off["bricks_skipped"] == 0
+        assert off["samples_shaded"] == on["samples_shaded"] == int(marginal.sum())
+        assert int(visible.sum()) <= off["samples_shaded"] < off["samples_taken"]
+        assert on["bricks_skipped"] > 0 and on["samples_taken"] < off["samples_taken"]
+        assert on["samples_taken"] + on["bricks_skipped"] == int(samples.sum())
+        hit = int(np.sum((kind == tf2d_ref.MARCHED) & (img[..., 3] > 0)))
+        assert off["rays_hit"] == on["rays_hit"] == hit > 0
+        for st in (off, on):
+            assert st["samples_nominal"] == 0 and st["bricks_visited"] == 0
+    finally:
+        vr.setStatsEnabled(False)
+
+
+def _dev(shape, fill=-7.0):
+    import torch
+    return torch.full(shape, fill, dtype=torch.float32, device="cuda")
+
+
+def _sync_np(t):
+    import torch
+    torch.cuda.synchronize()
+    return t.cpu().numpy()
+
+
+def test_entry_points(vr):
+    fmt = USHORT
+    ball = _sphere(fmt)
+    table = band_table()
+    _setup(vr, ball, fmt, table)
+    W, H, T = 64, 48, 16
+    _conf(vr, rate=1.5)
+    full = vr.runRaycastNoGL(W, H)
+    assert _same(full, _ref(vr, ball, fmt, table, W, H)[0])
+    # tiles
+    tiles_x = (W + T - 1) // T
+    ids = np.array([0, 5, 6, 11], dtype=np.uint32)
+    out = _dev((len(ids), T, T, 4))
+    vr.render_tiles(W, H, T, T, ids, out.data_ptr())
+    got = _sync_np(out)
+    assert vr.lastLaunchInfo()["technique"] == 6
+    for k, tid in enumerate(ids):
+        tx, ty = int(tid) % tiles_x, int(tid) // tiles_x
+        assert _same(got[k], full[ty * T:(ty + 1) * T, tx * T:(tx + 1) * T]), tid
+    # an 8-bit frame: the float frame through the project's one quantiser
+    _conf(vr, rate=1.5)
+    assert np.array_equal(vr.render_frame_rgba8(W, H), frontend.quantise_rgba8(full))
+    # one batch of three cameras
+    views = [VIEWS["default"], VIEWS["rot30"], VIEWS["close"]]
+    singles = []
+    for v, s in zip(views, SEEDS):
+        _conf(vr, view=v, seed=s, rate=1.5)
+        singles.append(vr.runRaycastNoGL(W, H))
+    _conf(vr, rate=1.5)
+    out = _dev((3, H, W, 4))
+    vr.render_batch(W, H, SEEDS[:3], out.data_ptr(), views=views)
+    got = _sync_np(out)
+    li = vr.lastLaunchInfo()
+    assert li["technique"] == 6 and li["frames"] == 3 and li["views"] == 1, li
+    for f in range(3):
+        assert _same(got[f], singles[f]), f
+    assert not _same(singles[0], singles[1])
+    # a twin that shares the voxels starts with the owner's 2-D table
+    twin = vr.shareVolumes()
+    try:
+        twin.setStatsEnabled(False)
+        _conf(twin, rate=1.5)
+        assert _same(twin.runRaycastNoGL(W, H), full)
+    finally:
+        twin.close()
+
+
+def test_state():
+    """A technique-0 frame, a slice and a depth image before and after technique-6 frames are bit-identical to those
+    of a renderer that never rendered technique 6 nor set a 2-D table; setting the 1-D table does not change a
+    technique-6 frame; setting the 2-D table does not change a technique-0 frame; the 1-D table is not required."""
+    fmt = UCHAR
+    vol = common.noise_volume((37, 29, 21), fmt, seed=12, smooth=False)
+    tff, tff2 = common.tffs()["default"], common.tffs()["opaque"]
+    W, H = 43, 27
+
+    def others(r):
+        r.setTechnique(TECH_RAYCAST)
+        out = []
+        for ess in (True, False):
+            _conf(r, ess=ess, rate=1.5)
+            out.append(r.runRaycastNoGL(W, H))
+            r.setIteration(0)
+        out.append(r.render_slices(W, H, frontend.axis_slice(2, 0.1)))
+        out.append(r.render_depth(W, H, "opacity", threshold=0.3)[0])
+        return out
+
+    plain = VolumeRenderCL()
+    plain.initialize()
+    r = VolumeRenderCL()
+    r.initialize()
+    try:
+        for x in (plain, r):
+            x.loadVolumeArrays([vol], fmt)
+            x.setStatsEnabled(False)
+            x.params()[1].backgroundColor[:] = BG
+        # no 1-D table at all: technique 6 renders
+        r.setTransferFunction2D(mixed_table(), G_HI)
+        r.setTechnique(TECH_TF2D)
+        _conf(r)
+        a = r.runRaycastNoGL(W, H)
+        assert _same(a, _ref(r, vol, fmt, mixed_table(), W, H)[0])
+        for x in (plain, r):
+            x.setTransferFunction(tff)
+            x.params()[1].backgroundColor[:] = BG
+        want = others(plain)
+        before = others(r)
+        r.setTechnique(TECH_TF2D)
+        _conf(r)
+        assert _same(r.runRaycastNoGL(W, H), a)              # the 1-D table was set in between: no change
+        r.setTransferFunction(tff2)
+        assert _same(r.runRaycastNoGL(W, H), a)
+        r.setTransferFunction(tff)
+        r.setTransferFunction2D(band_table(), G_HI)          # a new 2-D table shows
+        _conf(r)
+        b = r.runRaycastNoGL(W, H)
+        assert not _same(a, b) and _same(b, _ref(r, vol, fmt, band_table(), W, H)[0])
+        after = others(r)
+        for p, q, w in zip(before, after, want):
+            assert _same(p, w) and _same(q, w)
+    finally:
+        r.close()
+        plain.close()
+
+
+def test_rejections(vr):
+    vol = common.noise_volume((32, 32, 32), UCHAR, seed=1)
+    tff = common.tffs()["default"]
+    table = mixed_table()
+    _setup(vr, vol, UCHAR, table, tff=tff)
+    _conf(vr)
+    W, H = 48, 40
+    good = vr.runRaycastNoGL(W, H)
+
+    def frame_rc():
+        vr._push_params()
+        return vr.lib.vrhip_render_frame(vr.handle, W, H, None, 0)
+
+    def unsupported(call):
+        assert frame_rc() == _lib.ERR_UNSUPPORTED
+        with pytest.raises(RuntimeError) as e:
+            call()
+        assert str(e.value).strip()
+
+    for illum in (2, 3, 4, 5):
+        vr.setIllumination(illum)
+        unsupported(lambda: vr.runRaycastNoGL(W, H))
+    vr.setIllumination(1)
+    for setter in (vr.setImgEss, vr.setShowESS, vr.setAmbientOcclusion):
+        setter(True)
+        try:
+            unsupported(lambda: vr.runRaycastNoGL(W, H))
+        finally:
+            setter(False)
+    vr.setIteration(3)
+    unsupported(lambda: vr.runRaycastNoGL(W, H))
+    vr.setIteration(0)
+    vr.setEnvironmentMap(np.full((4, 8, 4), 0.5, np.float32))
+    try:
+        unsupported(lambda: vr.runRaycastNoGL(W, H))
+    finally:
+        vr.setEnvironmentMap(None)
+    sd = np.asarray(SEEDS[:2], np.uint32)
+    vr._push_params()
+    assert vr.lib.vrhip_render_samples(vr.handle, W, H, 0, 0, None, 0, sd.ctypes.data_as(C.c_void_p), 2, 0, None,
+                                       0) == _lib.ERR_UNSUPPORTED
+    n = C.c_uint64()
+    assert vr.lib.vrhip_count_touched(vr.handle, W, H, C.byref(n), None, 0) == _lib.ERR_UNSUPPORTED
+    assert vr.lib.vrhip_count_fetched(vr.handle, W, H, C.byref(n)) == _lib.ERR_UNSUPPORTED
+    ids = np.array([0, 1], np.uint32)
+    assert vr.lib.vrhip_count_touched_tiles(vr.handle, W, H, 16, 16, ids.ctypes.data_as(C.c_void_p), 2,
+                                            C.byref(n)) == _lib.ERR_UNSUPPORTED
+    # the setter refuses what vrhip_tf2d_params_check refuses, and keeps the table it has
+    for bad in (np.zeros((257, 1, 4), np.uint8), np.zeros((17, 4096, 4), np.uint8)):
+        with pytest.raises(ValueError):
+            vr.setTransferFunction2D(bad, G_HI)
+    for g in (0.0, -1.0, float("inf"), float("nan")):
+        with pytest.raises(ValueError):
+            vr.setTransferFunction2D(table, g)
+    _conf(vr)
+    assert _same(vr.runRaycastNoGL(W, H), good)
+    # RG / RGBA volumes
+    for ch in (2, 4):
+        vr.loadVolumeArrays([np.stack([vol] * ch, axis=-1)], UCHAR, channels=ch)
+        vr.setTransferFunction(tff)
+        _conf(vr)
+        unsupported(lambda: vr.runRaycastNoGL(W, H))
+    # 3 and 5 stay unassigned
+    _setup(vr, vol, UCHAR, table, tff=tff)
+    for tech in (3, 5):
+        vr.setTechnique(tech)
+        with pytest.raises(ValueError, match="Unknown rendering technique."):
+            vr.runRaycastNoGL(W, H)
+    vr.setTechnique(TECH_RAYCAST)
+    # no 2-D table: VRHIP_ERR_NODATA
+    r = VolumeRenderCL()
+    r.initialize()
+    try:
+        r.loadVolumeArrays([vol], UCHAR)
+        r.setTransferFunction(tff)
+        r.setTechnique(TECH_TF2D)
+        r._push_params()
+        assert r.lib.vrhip_render_frame(r.handle, W, H, None, 0) == _lib.ERR_NODATA
+        assert r.lib.vrhip_last_error(r.handle) == b"No 2-D transfer function set."
+    finally:
+        r.close()
+
+
+def test_cli_tf2d_ramp_and_file(vr, tmp_path):
+    """vrhip_render --tf2d-ramp on a synthetic 64^3 volume writes the Python route's frame, and --tf2d FILE the same
+    frame from the table as a file; two frames per launch of an orbit equal the frames one by one."""
+    W, H = 64, 48
+    view = VIEWS["rot30"]
+    n_g, g_hi, g0, g1 = 8, 0.2, 0.01, 0.06
+    scene = ["--synth", "shells", 64, "UCHAR", "--seed", 1234, "--size", W, H, "--view"] + [repr(float(np.float32(v))) for v in view]
+
+    def cli(args, name, suffix=".rgba.f32"):
+        out = str(tmp_path / name)
+        res = subprocess.run([EXE] + [str(a) for a in scene + args] + ["--out", out], capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0, res.stderr
+        return np.fromfile(out + suffix, dtype=np.float32).reshape(-1, H, W, 4)
+
+    one = cli(["--tf2d-ramp", n_g, g_hi, g0, g1], "ramp")[0]
+    vr.synthVolume("shells", (64, 64, 64), UCHAR)
+    tff = frontend.tff_from_stops()
+    vr.setTransferFunction(tff)
+    table = frontend.tf2d_ramp(tff, n_g, g_hi, g0, g1)
+    vr.setTransferFunction2D(table, g_hi)
+    vr.setTechnique(TECH_TF2D)
+    vr.setStatsEnabled(False)
+    vr.setBackground((1.0, 1.0, 1.0))
+    _conf(vr, view=view, rate=1.5, seed=1234)
+    img = vr.runRaycastNoGL(W, H)
+    assert _same(one, img) and np.any(img[..., 3] > 0)
+    assert _same(img, _ref(vr, vr.downloadVolume(0), UCHAR, table, W, H, g_hi=g_hi)[0])
+    path = str(tmp_path / "table.rgba")
+    table.tofile(path)
+    assert _same(cli(["--tf2d", path, table.shape[1], n_g, g_hi], "file")[0], img)
+    orbit = ["--tf2d-ramp", n_g, g_hi, g0, g1, "--orbit", 0, 1, 0, 4]
+    a = cli(orbit, "orbit", suffix=".frames.rgba.f32")
+    b = cli(orbit + ["--frames-per-launch", 2], "orbit_fpl", suffix=".frames.rgba.f32")
+    assert a.shape[0] == 4 and _same(a, b) and not _same(a[0], a[1])
+    vr.setTechnique(TECH_RAYCAST)

@@ -14,9 +14,12 @@ LIB_PATH = os.environ.get("VRHIP_LIB_PATH") or os.path.join(_HERE, "libvrhip.so"
 OK, ERR_INVALID, ERR_HIP, ERR_NODATA, ERR_UNSUPPORTED = range(5)
 UCHAR, USHORT, FLOAT = 0, 1, 2
 # rendering_params.technique: ray caster, path tracer, maximum intensity projection (VRHIP_TECHNIQUE_MIP), first-hit
-# isosurface (VRHIP_TECHNIQUE_ISO; 3 is unassigned)
+# isosurface (VRHIP_TECHNIQUE_ISO; 3 is unassigned), 2-D transfer function (VRHIP_TECHNIQUE_TF2D; 5 is unassigned)
 TECH_RAYCAST, TECH_PATHTRACE, TECH_MIP = 0, 1, 2
 TECH_ISO = 4
+TECH_TF2D = 6
+# the limits of a 2-D transfer function (vrhip_tf2d_params_check): those of the statistics histogram
+TF2D_MAX_NV, TF2D_MAX_NG, TF2D_MAX_ENTRIES = 4096, 256, 65536
 
 
 class CameraParams(C.Structure):
@@ -252,6 +255,11 @@ SYMBOLS = {
     "vrhip_get_resolution": (C.c_int, [_H, C.POINTER(C.c_uint32)]),
     "vrhip_set_transfer_function": (C.c_int, [_H, C.c_void_p, C.c_uint32]),
     "vrhip_set_tff_prefix_sum": (C.c_int, [_H, C.c_void_p, C.c_uint32]),
+    "vrhip_set_transfer_function_2d": (C.c_int, [_H, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float]),
+    "vrhip_tf2d_params_check": (C.c_int, [C.c_uint32, C.c_uint32, C.c_float]),
+    "vrhip_tf2d_lookup": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float,
+                                    C.POINTER(C.c_float)]),
+    "vrhip_tf2d_build_ramp": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "vrhip_build_bricks": (C.c_int, [_H]),
     "vrhip_get_brick_info": (C.c_int, [_H, _U3, C.POINTER(C.c_float), _U3]),
     "vrhip_download_bricks": (C.c_int, [_H, C.c_uint32, C.c_void_p, C.c_size_t]),

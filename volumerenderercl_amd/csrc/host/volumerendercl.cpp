@@ -356,7 +356,32 @@ void VolumeRenderCL::setBackground(std::array<float, 4> color)   // :1025-1030
 // projection or an isosurface does not accumulate, every frame of it is iteration 0 (the library rejects anything else).
 void VolumeRenderCL::advanceIteration()
 {
-    if (_rendering_params.technique != TECH_MIP && _rendering_params.technique != TECH_ISO) _rendering_params.iteration++;
+    if (_rendering_params.technique != TECH_MIP && _rendering_params.technique != TECH_ISO &&
+        _rendering_params.technique != TECH_TF2D)
+        _rendering_params.iteration++;
+}
+
+void VolumeRenderCL::setTransferFunction2D(const std::vector<unsigned char> &table, unsigned int nV, unsigned int nG,
+                                           float gHi)
+{
+    if (table.size() != size_t(4) * nV * nG)
+        throw std::invalid_argument("setTransferFunction2D: the table must hold 4 * nV * nG bytes.");
+    check("setTransferFunction2D", vrhip_set_transfer_function_2d(_r, table.data(), nV, nG, gHi));
+    _tf2d = table;
+    _tf2dNV = nV;
+    _tf2dNG = nG;
+    _tf2dGHi = gHi;
+    _rendering_params.iteration = 0;
+}
+
+std::vector<unsigned char> VolumeRenderCL::rampTransferFunction2D(const std::vector<unsigned char> &tff, unsigned int nG,
+                                                                  float gHi, float g0, float g1)
+{
+    const unsigned int nV = static_cast<unsigned int>(tff.size() / 4);
+    std::vector<unsigned char> out(size_t(4) * nV * nG);
+    if (tff.size() % 4 != 0 || vrhip_tf2d_build_ramp(tff.data(), nV, nG, gHi, g0, g1, out.data()) != VRHIP_OK)
+        throw std::invalid_argument("rampTransferFunction2D: invalid table size, gHi or ramp.");
+    return out;
 }
 
 void VolumeRenderCL::setTechnique(technique tech)   // :1042-1047
@@ -500,6 +525,7 @@ std::unique_ptr<VolumeRenderCL> VolumeRenderCL::shareVolumes()
         std::vector<unsigned int> prefix = _tffPrefixSum;
         twin->setTffPrefixSum(prefix);
     }
+    if (!_tf2d.empty()) twin->setTransferFunction2D(_tf2d, _tf2dNV, _tf2dNG, _tf2dGHi);
     twin->_rendering_params.iteration = _rendering_params.iteration;
     if (_roundBudget) twin->setRoundBudget(_roundBudget);
     return twin;

@@ -421,6 +421,16 @@ void write_rgba8(const std::string &out, const std::vector<unsigned char> &frame
         "                                           independent frames like --mip; combines with --orbit, --camera-path,\n"
         "                                           --frames-per-launch, --rgba8 and --ranks; not with --pathtrace, --mip,\n"
         "                                           --ao, --show-ess, --img-ess, --env)\n"
+        "         [--tf2d FILE NV NG GHI]          (technique 6, a two-dimensional transfer function TF2(value, gradient\n"
+        "                                           magnitude): FILE holds NV x NG raw RGBA8 entries, value fastest; GHI is\n"
+        "                                           the gradient magnitude at the table's upper edge -- the GHI of\n"
+        "                                           --stats-window, whose histogram bins the entries are the centres of;\n"
+        "                                           --illum 0 or 1; independent frames like --mip; combines with --orbit,\n"
+        "                                           --camera-path, --frames-per-launch and --rgba8; not with --pathtrace,\n"
+        "                                           --mip, --iso, --ao, --show-ess, --img-ess, --env, --ranks)\n"
+        "         [--tf2d-ramp NG GHI G0 G1]       (the same from the command's 1-D table: NG rows of it, their opacity\n"
+        "                                           scaled by a ramp over the gradient magnitude, 0 up to G0 and 1 from G1\n"
+        "                                           on -- boundary emphasis)\n"
         "         [--samples-per-launch K]         (--pathtrace: the N samples in launch sets of K -- vrhip_render_samples,\n"
         "                                           the same image bit for bit; 0 = the library's default set size, the\n"
         "                                           default; 1 = one launch per sample, as before; with --bench: one\n"
@@ -613,6 +623,11 @@ int main(int argc, char **argv)
     double iso_value = 0.5;
     int iso_refine = 4;
     bool have_iso_refine = false;
+    // technique 6 (--tf2d FILE NV NG GHI, --tf2d-ramp NG GHI G0 G1)
+    bool tf2d = false, tf2d_ramp = false;
+    std::string tf2d_file;
+    long tf2d_nv = 0, tf2d_ng = 0;
+    double tf2d_ghi = 0.0, tf2d_g0 = 0.0, tf2d_g1 = 0.0;
     double extinction = 100.0;
     int downsample = 0;
     std::string state_file, tf_stops, tf_easing = "linear", dump_tf;
@@ -682,6 +697,22 @@ int main(int argc, char **argv)
         else if (a == "--mip") mip = true;
         else if (a == "--iso") { need(i, 1); iso = true; iso_value = std::atof(argv[++i]); }
         else if (a == "--iso-refine") { need(i, 1); have_iso_refine = true; iso_refine = std::atoi(argv[++i]); }
+        else if (a == "--tf2d") {
+            need(i, 4);
+            tf2d = true;
+            tf2d_file = argv[++i];
+            tf2d_nv = std::atol(argv[++i]);
+            tf2d_ng = std::atol(argv[++i]);
+            tf2d_ghi = std::atof(argv[++i]);
+        }
+        else if (a == "--tf2d-ramp") {
+            need(i, 4);
+            tf2d_ramp = true;
+            tf2d_ng = std::atol(argv[++i]);
+            tf2d_ghi = std::atof(argv[++i]);
+            tf2d_g0 = std::atof(argv[++i]);
+            tf2d_g1 = std::atof(argv[++i]);
+        }
         else if (a == "--device-ingest") device_ingest = true;
         else if (a == "--downsample") { need(i, 1); downsample = std::atoi(argv[++i]); }
         else if (a == "--state") { need(i, 1); state_file = argv[++i]; }
@@ -782,6 +813,17 @@ int main(int argc, char **argv)
     if (mip && pathtrace) usage();
     if (iso && (pathtrace || mip || use_ao_flag || show_ess_flag || img_ess || !env_file.empty())) usage();
     if (have_iso_refine && (!iso || iso_refine < 0 || iso_refine > 16)) usage();
+    if (tf2d || tf2d_ramp) {
+        if (tf2d && tf2d_ramp) usage();
+        if (pathtrace || mip || iso || use_ao_flag || show_ess_flag || img_ess || !env_file.empty() || ranks > 0) usage();
+        if (tf2d && (tf2d_file.empty() || tf2d_nv < 1 || tf2d_nv > long(VRHIP_TF2D_MAX_NV))) usage();
+        if (tf2d_ng < 1 || tf2d_ng > long(VRHIP_TF2D_MAX_NG) || (tf2d && tf2d_nv * tf2d_ng > long(VRHIP_TF2D_MAX_ENTRIES))) usage();
+        if (!std::isfinite(tf2d_ghi) || !(float(tf2d_ghi) > 0.f)) usage();
+        if (tf2d_ramp && (!std::isfinite(tf2d_g0) || !std::isfinite(tf2d_g1) || !(float(tf2d_g0) >= 0.f) ||
+                          !(float(tf2d_g1) > float(tf2d_g0))))
+            usage();
+    }
+    const bool tf2d_any = tf2d || tf2d_ramp;
     if (rgba8 && ranks > 0) {
         std::cerr << "--rgba8 cannot be combined with --ranks: the C++ tile gather carries float pixels "
                      "(8-bit frames over several GPUs: the Python TileDriver, pixel_format=\"rgba8\")" << std::endl;
@@ -791,7 +833,7 @@ int main(int argc, char **argv)
     if ((have_slab || have_stack || slice_value) && !slicing) usage();
     if (slicing) {
         if (have_slice_axis && have_slice_plane) usage();
-        if (mip || iso || pathtrace || have_orbit || have_path_arg || ranks > 0) usage();
+        if (mip || iso || tf2d_any || pathtrace || have_orbit || have_path_arg || ranks > 0) usage();
         if (have_slice_axis && (slice_axis < 0 || !std::isfinite(slice_pos))) usage();
         for (double c : slice_vec) if (!std::isfinite(c)) usage();
         if (have_slab && (slab_n < 1 || slab_n > int(VRHIP_SLICE_MAX_SAMPLES) || !std::isfinite(slab_t) ||
@@ -807,7 +849,8 @@ int main(int argc, char **argv)
     if ((have_depth_refine || have_depth_rect) && !depth) usage();
     if (depth) {
         if (depth_mode != "iso" && depth_mode != "max" && depth_mode != "opacity") usage();
-        if (pathtrace || mip || iso || slicing || have_slab || have_stack || slice_value || ranks > 0 || frames_per_launch > 0)
+        if (pathtrace || mip || iso || tf2d_any || slicing || have_slab || have_stack || slice_value || ranks > 0 ||
+            frames_per_launch > 0)
             usage();
         // one depth image of one camera: what asks for several frames, or for a frame's own state, has nothing to act on
         if (have_orbit || have_path_arg || frames != 1 || rgba8 || img_ess) usage();
@@ -825,7 +868,7 @@ int main(int argc, char **argv)
     if (!filters.empty() && (ranks > 0 || downsample)) usage();
     if (stats) {
         // numbers about the volume, not a picture of it: as for --mesh, and not with it
-        if (mesh || pathtrace || mip || iso || have_iso_refine || slicing || have_slab || have_stack || slice_value || depth ||
+        if (mesh || pathtrace || mip || iso || tf2d_any || have_iso_refine || slicing || have_slab || have_stack || slice_value || depth ||
             ranks > 0 || frames_per_launch > 0 || have_orbit || have_path_arg || frames != 1 || rgba8 || img_ess || downsample ||
             !dump_tf.empty() || bench || independent)
             usage();
@@ -846,7 +889,7 @@ int main(int argc, char **argv)
         mesh_ply = ext == ".ply";
         if (mesh_indexed && !mesh_ply) usage();   // (STL is a triangle list)
         // triangles of the volume, not a picture of it: what selects, shapes or multiplies frames has nothing to act on
-        if (pathtrace || mip || iso || have_iso_refine || slicing || have_slab || have_stack || slice_value || depth || ranks > 0 ||
+        if (pathtrace || mip || iso || tf2d_any || have_iso_refine || slicing || have_slab || have_stack || slice_value || depth || ranks > 0 ||
             frames_per_launch > 0 || have_orbit || have_path_arg || frames != 1 || rgba8 || img_ess || downsample ||
             !dump_tf.empty() || bench || independent)
             usage();
@@ -980,6 +1023,23 @@ int main(int argc, char **argv)
             vr.setTechnique(VolumeRenderCL::TECH_ISO);
             vr.setIsoValue(float(iso_value));
             vr.setIsoRefinement(unsigned(iso_refine));
+        }
+        if (tf2d_any) {
+            std::vector<unsigned char> table2;
+            unsigned nv = unsigned(tf2d_nv);
+            if (tf2d) {
+                std::ifstream f(tf2d_file, std::ios::binary);
+                table2.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+                if (!f.good() && !f.eof()) table2.clear();
+                if (table2.size() != size_t(4) * size_t(tf2d_nv) * size_t(tf2d_ng))
+                    throw std::runtime_error("--tf2d: " + tf2d_file + " does not hold NV * NG RGBA8 entries");
+            } else {
+                nv = unsigned(table.size() / 4);
+                table2 = VolumeRenderCL::rampTransferFunction2D(table, unsigned(tf2d_ng), float(tf2d_ghi), float(tf2d_g0),
+                                                                float(tf2d_g1));
+            }
+            vr.setTechnique(VolumeRenderCL::TECH_TF2D);
+            vr.setTransferFunction2D(table2, nv, unsigned(tf2d_ng), float(tf2d_ghi));
         }
         if (pin) vr.setSeed(seed);
         vr.updateOutputImg(W, H, 0);

@@ -65,6 +65,17 @@ struct TfView {
     uint32_t prefix_n;
 };
 
+// The 2-D transfer function of technique 6 (vrhip_set_transfer_function_2d), all of it made on the host at set time.
+struct Tf2dView {
+    const float4 *table;     // n_g rows of n_v entries, value fastest, c / 255.0f
+    // Marginal opacity, as its prefix sum: nz[i] = the number of columns i' < i with max_j table[j][i'].a != 0
+    // (n_v + 1 words).  Column i is transparent in every row <=> nz[i + 1] == nz[i]; columns i0..i1 all are
+    // <=> nz[i1 + 1] == nz[i0].
+    const uint32_t *nz;
+    uint32_t n_v, n_g;
+    float inv_ghi;           // 1.0f / g_hi, computed once
+};
+
 // ESS decision per brick, precomputed from (bricks, TF, prefix sum): bit = 1 when the
 // reference's test `TF(max).a < 1e-6 && prefix[min] == prefix[max]` (volumeraycast.cl:
 // 777-787) holds.  x-fastest bit index; word n_words holds the decision for the (0,0) value
@@ -334,6 +345,7 @@ struct RaycastLaunch {
     // nullptr: every sample is fetched
     const float2 *cell_minmax;
     int cell_minmax_fine;
+    Tf2dView tf2d;             // technique 6: its table (cell_minmax as for techniques 2 and 4)
 };
 
 // hipLaunchKernelGGL, or -- with an event -- the launch whose completion the event is bound to
@@ -423,6 +435,8 @@ hipError_t vr_launch_cell_leap_radius(const CellView &grid, const float *cbound,
 hipError_t vr_launch_mip(const RaycastLaunch &a, hipStream_t stream);
 // technique 4 (first-hit isosurface): one launch of the same shape; vr_iso.hip
 hipError_t vr_launch_iso(const RaycastLaunch &a, hipStream_t stream);
+// technique 6 (two-dimensional transfer function): one launch of the same shape; vr_tf2d.hip
+hipError_t vr_launch_tf2d(const RaycastLaunch &a, hipStream_t stream);
 // slice views (vrhip_render_slices): n_slices images of W x H pixels, one wave per 8x8 patch of every slice, into
 // out_dev[n_slices][H][W]; slices_dev: the n_slices parameter blocks in device memory; vr_slice.hip
 hipError_t vr_launch_slices(const VolView &vol, int format, const TfView &tf, const vrhip_slice_params *slices_dev,
@@ -552,7 +566,8 @@ hipError_t vr_launch_filter(const FilterLaunch &a, void *dst, unsigned long long
 // the frame launch for a.render.technique
 inline hipError_t vr_launch_frame(const RaycastLaunch &a, hipStream_t stream)
 {
-    return a.render.technique == VRHIP_TECHNIQUE_ISO   ? vr_launch_iso(a, stream)
+    return a.render.technique == VRHIP_TECHNIQUE_TF2D  ? vr_launch_tf2d(a, stream)
+           : a.render.technique == VRHIP_TECHNIQUE_ISO ? vr_launch_iso(a, stream)
            : a.render.technique == VRHIP_TECHNIQUE_MIP ? vr_launch_mip(a, stream)
            : a.render.technique == 1                   ? vr_launch_pathtrace(a, stream)
                                                        : vr_launch_raycast(a, stream);

@@ -113,6 +113,12 @@ struct vrhip_renderer {
     uint32_t tff_n = 0;
     DevBuf<uint32_t> prefix;
     uint32_t prefix_n = 0;
+    // the 2-D transfer function of technique 6 (Tf2dView): state of its own, made whole by
+    // vrhip_set_transfer_function_2d and read by technique 6's frames alone
+    DevBuf<float4> tf2d;
+    DevBuf<uint32_t> tf2d_nz;
+    uint32_t tf2d_nv = 0, tf2d_ng = 0;
+    float tf2d_inv_ghi = 0.f;
 
     uint32_t brick_tex[3] = {0, 0, 0}, brick_edge[3] = {0, 0, 0};
     float brick_res[3] = {1, 1, 1};
@@ -448,6 +454,17 @@ inline TfView make_tf_view(const vrhip_renderer *r)
     return t;
 }
 
+inline Tf2dView make_tf2d_view(const vrhip_renderer *r)
+{
+    Tf2dView t;
+    t.table = r->tf2d;
+    t.nz = r->tf2d_nz;
+    t.n_v = r->tf2d_nv;
+    t.n_g = r->tf2d_ng;
+    t.inv_ghi = r->tf2d_inv_ghi;
+    return t;
+}
+
 // what make_ray derives the camera from: the frame size and the reference's padded launch size
 inline void set_frame_geometry(FrameView *f, uint32_t width, uint32_t height)
 {
@@ -496,6 +513,10 @@ bool mip_skips(const vrhip_renderer *r);
 //     fp_failed_bytes: a size not to try again)      |                     | (fp_failed_bytes: any new voxels)
 //   patch classes                                    | ensure_patch_classes| their byte key (patch_class_key), which
 //                                                    |                     | holds skip_version and queue_version
+//   2-D table, its column summary (tf2d, tf2d_nz,    | vrhip_set_transfer_ | the call's arguments alone: built whole at
+//     tf2d_nv / _ng / _inv_ghi)                      |   function_2d       | set time, never stale, nothing derives
+//                                                    |                     | from it (technique 6 reads it as it is,
+//                                                    |                     | with the cell (min,max) like 2 and 4)
 //
 // A voxel write into ANY slot makes the renderer-wide tables stale, not only one into the current step (the code
 // never looked at which).  fp_candidate / fp_candidate_frames count frames, and survive everything but a change
@@ -553,6 +574,16 @@ inline void tf_changed(vrhip_renderer *r)
 {
     r->skip_dirty = true;
     cells_tables_stale(r);
+}
+
+// The 2-D transfer function (technique 6): the table is being replaced (n_v = 0: none is set until tf2d_set), then
+// is whole.  No other derived state depends on it, and tf_changed does not touch it.
+inline void tf2d_unset(vrhip_renderer *r) { r->tf2d_nv = r->tf2d_ng = 0; r->tf2d_inv_ghi = 0.f; }
+inline void tf2d_set(vrhip_renderer *r, uint32_t n_v, uint32_t n_g, float inv_ghi)
+{
+    r->tf2d_nv = n_v;
+    r->tf2d_ng = n_g;
+    r->tf2d_inv_ghi = inv_ghi;
 }
 
 // vrhip_build_bricks has run: every slot's bricks match its voxels

@@ -206,6 +206,8 @@ struct Vol {
     // in texel space -- the centre's filter weights with indices shifted by -+1 and clamped to
     // the edge -- so the 4x4x4 neighbourhood is loaded once: 32 voxel loads and one set of
     // coordinate arithmetic instead of 6 x (8 loads + coordinates).  DESIGN.md "Numerics".
+    // (vr_tf2d.hip's tf2d_central_diff is a copy of the taps, blends and difference below, stopped before the
+    // normalisation; technique 6 is held to technique 0 bit for bit through it: change neither without the other.)
     VR_DEV f3 neg_gradient(float px, float py, float pz) const
     {
         float ub = px * fw - 0.5f, vb = py * fh - 0.5f, sb = pz * fd - 0.5f;

@@ -118,7 +118,11 @@ bool ray_skip_empty(const vrhip_renderer *r)
 }
 
 // the techniques that are one launch over the cells' (min, max): maximum intensity projection, first-hit isosurface
-bool minmax_technique(uint32_t t) { return t == VRHIP_TECHNIQUE_MIP || t == VRHIP_TECHNIQUE_ISO; }
+// ... and the 2-D transfer function, which reads them the same way and no table made from the 1-D one
+bool minmax_technique(uint32_t t)
+{
+    return t == VRHIP_TECHNIQUE_MIP || t == VRHIP_TECHNIQUE_ISO || t == VRHIP_TECHNIQUE_TF2D;
+}
 
 // Sharers of `owner` lose their (borrowed) volumes: nothing of theirs points into the owner any more.
 void detach_sharers(vrhip_renderer *owner)
@@ -215,15 +219,18 @@ int check_renderable(vrhip_renderer *r, uint32_t width, uint32_t height)
                VRHIP_ERR_INVALID, "Invalid output image size.");
     VR_REQUIRE(r, !r->vols.empty() && r->timestep < r->vols.size() && r->vols[r->timestep].dev,
                VRHIP_ERR_NODATA, "No volume data is loaded.");
-    VR_REQUIRE(r, r->tff && r->tff_n, VRHIP_ERR_NODATA, "No transfer function set.");
+    // (technique 6 neither reads nor requires the 1-D table: its own is asked for below)
+    VR_REQUIRE(r, (r->tff && r->tff_n) || r->render.technique == VRHIP_TECHNIQUE_TF2D, VRHIP_ERR_NODATA,
+               "No transfer function set.");
     if (r->use_ess && r->render.technique == 0) {
         VR_REQUIRE(r, r->bricks_valid && r->vols[r->timestep].bricks, VRHIP_ERR_NODATA,
                    "ESS bricks not built: call vrhip_build_bricks after the volume upload.");
         VR_REQUIRE(r, r->prefix && r->prefix_n, VRHIP_ERR_NODATA,
                    "No transfer function prefix sum set.");
     }
-    VR_REQUIRE(r, r->render.technique <= VRHIP_TECHNIQUE_MIP || r->render.technique == VRHIP_TECHNIQUE_ISO, VRHIP_ERR_INVALID,
-               "Unknown rendering technique.");   // (3 is unassigned)
+    VR_REQUIRE(r, r->render.technique <= VRHIP_TECHNIQUE_MIP || r->render.technique == VRHIP_TECHNIQUE_ISO ||
+                      r->render.technique == VRHIP_TECHNIQUE_TF2D,
+               VRHIP_ERR_INVALID, "Unknown rendering technique.");   // (3 and 5 are unassigned)
     // the path-tracing branch of the kernel returns before illumType is looked at (:686-706); technique 2 ignores it
     VR_REQUIRE(r, r->render.illumType <= 5 || r->render.technique != 0, VRHIP_ERR_INVALID,
                "Unknown illumination type.");
@@ -255,6 +262,19 @@ int check_renderable(vrhip_renderer *r, uint32_t width, uint32_t height)
                    "isosurface: frames do not accumulate (iteration must be 0).");
         VR_REQUIRE(r, r->channels == 1, VRHIP_ERR_UNSUPPORTED, "isosurface: RG / RGBA volumes are not supported.");
         VR_REQUIRE(r, !r->env, VRHIP_ERR_UNSUPPORTED, "isosurface: environment maps are not supported.");
+    }
+    if (r->render.technique == VRHIP_TECHNIQUE_TF2D) {   // what the 2-D transfer function does not define
+        const vrhip_rendering_params &rp = r->render;
+        VR_REQUIRE(r, r->tf2d && r->tf2d_nz && r->tf2d_nv && r->tf2d_ng, VRHIP_ERR_NODATA, "No 2-D transfer function set.");
+        VR_REQUIRE(r, rp.illumType <= 1, VRHIP_ERR_UNSUPPORTED,
+                   "2-D transfer function: illumType 0 (flat) and 1 (central differences) only.");
+        VR_REQUIRE(r, !rp.imgEss && !rp.showEss, VRHIP_ERR_UNSUPPORTED,
+                   "2-D transfer function: image-order ESS and showEss are not supported.");
+        VR_REQUIRE(r, !r->raycast.useAO, VRHIP_ERR_UNSUPPORTED, "2-D transfer function: ambient occlusion is not supported.");
+        VR_REQUIRE(r, rp.iteration == 0, VRHIP_ERR_UNSUPPORTED,
+                   "2-D transfer function: frames do not accumulate (iteration must be 0).");
+        VR_REQUIRE(r, r->channels == 1, VRHIP_ERR_UNSUPPORTED, "2-D transfer function: RG / RGBA volumes are not supported.");
+        VR_REQUIRE(r, !r->env, VRHIP_ERR_UNSUPPORTED, "2-D transfer function: environment maps are not supported.");
     }
     // technique 1 and the traffic / downsampling helpers read channel 0 only, like the kernel's
     // .x readers; nothing else to check for CL_RG / CL_RGBA volumes
@@ -621,6 +641,7 @@ void fill_launch(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t ou
             a->cell_minmax = cell_minmax_of(r, a->cell_minmax_fine != 0);
         }
     }
+    if (r->render.technique == VRHIP_TECHNIQUE_TF2D) a->tf2d = make_tf2d_view(r);
     a->format = r->format;
     a->use_ess = r->use_ess ? 1 : 0;
     a->instr = r->stats_enabled ? 1 : 0;
@@ -766,7 +787,9 @@ int prepare_render(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t 
     }
     if (r->render.technique == 1 ? r->pt_cull : minmax_technique(r->render.technique) ? mip_skips(r) : ray_skip_empty(r)) {
         // (techniques 2 and 4 read the (min, max) of the grid the empty bits live on: built with them)
-        rc = ensure_cells(r, r->render.technique == 1, r->render.technique != 1);
+        // (technique 6 may have no 1-D transfer function to make the tables from: the pairs and the geometry alone)
+        rc = ensure_cells(r, r->render.technique == 1, r->render.technique != 1,
+                          r->render.technique != VRHIP_TECHNIQUE_TF2D);
         if (rc) return rc;
     }
     return ensure_queue(r, width, height, tile_w, tile_h, tile_ids, n_tiles, n_frames, frame_stride);
@@ -783,6 +806,8 @@ int count_touched_impl(vrhip_renderer *r, uint32_t width, uint32_t height, uint3
                "vrhip_count_touched / vrhip_count_fetched: not supported with maximum intensity projection.");
     VR_REQUIRE(r, r->render.technique != VRHIP_TECHNIQUE_ISO, VRHIP_ERR_UNSUPPORTED,
                "vrhip_count_touched / vrhip_count_fetched: not supported with isosurface rendering.");
+    VR_REQUIRE(r, r->render.technique != VRHIP_TECHNIQUE_TF2D, VRHIP_ERR_UNSUPPORTED,
+               "vrhip_count_touched / vrhip_count_fetched: not supported with the 2-D transfer function.");
     int rc = prepare_render(r, width, height, tile_w, tile_h, tile_ids, n_tiles);
     if (rc) return rc;
     const size_t mb = (size_t)((r->res[0] + 3) / 4) * ((r->res[1] + 3) / 4) * ((r->res[2] + 3) / 4);
@@ -1258,6 +1283,37 @@ int vrhip_set_transfer_function(vrhip_renderer *r, const uint8_t *rgba8, uint32_
     return VRHIP_OK;
 }
 
+int vrhip_set_transfer_function_2d(vrhip_renderer *r, const uint8_t *rgba8, uint32_t n_v, uint32_t n_g, float g_hi)
+{
+    if (!r) return VRHIP_ERR_INVALID;
+    VR_REQUIRE(r, rgba8, VRHIP_ERR_INVALID, "Empty 2-D transfer function.");
+    VR_REQUIRE(r, vrhip_tf2d_params_check(n_v, n_g, g_hi) == VRHIP_OK, VRHIP_ERR_INVALID,
+               "2-D transfer function: n_v must be 1..4096, n_g 1..256, their product at most 65536, g_hi finite and > 0.");
+    if (set_device(r)) return VRHIP_ERR_HIP;
+    // the table as float4 (c / 255.0f, like the 1-D one) and the columns' opacity summary (Tf2dView::nz)
+    const size_t n = (size_t)n_v * n_g;
+    std::vector<float4> table(n);
+    std::vector<uint32_t> nz(n_v + 1, 0u);
+    for (size_t k = 0; k < n; ++k) {
+        table[k].x = (float)rgba8[4 * k + 0] / 255.0f;
+        table[k].y = (float)rgba8[4 * k + 1] / 255.0f;
+        table[k].z = (float)rgba8[4 * k + 2] / 255.0f;
+        table[k].w = (float)rgba8[4 * k + 3] / 255.0f;
+        if (rgba8[4 * k + 3]) nz[k % n_v + 1] = 1u;
+    }
+    for (uint32_t i = 0; i < n_v; ++i) nz[i + 1] += nz[i];
+    const volatile float inv_ghi = 1.0f / g_hi;   // (volatile: rounded to fp32 here, whatever the host's flags)
+    VR_HIP(r, hipStreamSynchronize(r->stream));
+    tf2d_unset(r);
+    int rc = grow(r, r->tf2d, n * sizeof(float4));
+    if (!rc) rc = grow(r, r->tf2d_nz, nz.size() * sizeof(uint32_t));
+    if (rc) return rc;
+    VR_HIP(r, hipMemcpy(r->tf2d, table.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    VR_HIP(r, hipMemcpy(r->tf2d_nz, nz.data(), nz.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    tf2d_set(r, n_v, n_g, inv_ghi);
+    return VRHIP_OK;
+}
+
 int vrhip_set_tff_prefix_sum(vrhip_renderer *r, const uint32_t *prefix, uint32_t n)
 {
     if (!r) return VRHIP_ERR_INVALID;
@@ -1465,7 +1521,7 @@ int vrhip_render_batch_views(vrhip_renderer *r, uint32_t width, uint32_t height,
     VR_REQUIRE(r, (rp.technique == 0 || minmax_technique(rp.technique)) && rp.iteration == 0 && !rp.imgEss &&
                       !r->raycast.useAO,
                VRHIP_ERR_UNSUPPORTED,
-               "vrhip_render_batch: technique 0, 2 or 4 only, iteration 0, no image-order ESS, no ambient occlusion");
+               "vrhip_render_batch: technique 0, 2, 4 or 6 only, iteration 0, no image-order ESS, no ambient occlusion");
     const uint32_t packed = tile_ids ? n_tiles * tile_w * tile_h : width * height;
     VR_REQUIRE(r, out_frame_stride == 0 || out_frame_stride >= packed, VRHIP_ERR_INVALID,
                "vrhip_render_batch: frame stride smaller than a frame");

@@ -522,6 +522,50 @@ def otsu_threshold(hist_row, v_lo, v_hi):
     return float(v_lo) + k * width
 
 
+# ---- 2-D transfer functions (include/vrhip.h "technique == 6"; VolumeRenderCL.setTransferFunction2D): tables of shape
+# (n_g, n_v, 4) uint8, row j = gradient bin j of volume_statistics(..., bins_g=n_g, g_hi=g_hi), value fastest.
+
+def _tf1d(tff):
+    tff = np.ascontiguousarray(tff, dtype=np.uint8).reshape(-1, 4)
+    if tff.shape[0] < 1:
+        raise ValueError("empty transfer function")
+    return tff
+
+
+def tf2d_from_1d(tff, n_g):
+    """n_g rows, each the 1-D table: TF2(s, m) = TF(s) whatever the gradient -- technique 6 then renders technique
+    0's image (object-order ESS off)."""
+    return np.ascontiguousarray(np.broadcast_to(_tf1d(tff)[None], (int(n_g),) + _tf1d(tff).shape))
+
+
+def tf2d_ramp(tff, n_g, g_hi, g0, g1):
+    """Boundary emphasis: n_g rows of the 1-D table, their alpha scaled by a ramp over the gradient magnitude that is
+    0 up to g0 and 1 from g1 on (vrhip_tf2d_build_ramp: the expression is in include/vrhip.h)."""
+    from . import _lib
+    tff = _tf1d(tff)
+    out = np.zeros((int(n_g), tff.shape[0], 4), np.uint8)
+    rc = _lib.load().vrhip_tf2d_build_ramp(tff.ctypes.data, tff.shape[0], int(n_g), float(g_hi), float(g0), float(g1),
+                                           out.ctypes.data)
+    if rc != _lib.OK:
+        raise ValueError("tf2d_ramp: table sizes 1..4096 x 1..256 (at most 65536 entries), g_hi finite and > 0, "
+                         "0 <= g0 < g1 finite")
+    return out
+
+
+def tf2d_lookup(table, g_hi, s, m):
+    """Technique 6's lookup of the table at value s and gradient magnitude m (vrhip_tf2d_lookup): float32 RGBA."""
+    import ctypes as C
+    from . import _lib
+    table = np.ascontiguousarray(table, dtype=np.uint8)
+    if table.ndim != 3 or table.shape[2] != 4:
+        raise ValueError("the 2-D transfer function must have shape (n_g, n_v, 4)")
+    out = (C.c_float * 4)()
+    rc = _lib.load().vrhip_tf2d_lookup(table.ctypes.data, table.shape[1], table.shape[0], float(g_hi), float(s), float(m), out)
+    if rc != _lib.OK:
+        raise ValueError("tf2d_lookup: invalid table size or g_hi")
+    return np.array(out[:], dtype=np.float32)
+
+
 # ---- volume filters (include/vrhip.h "volume filters"; VolumeRenderCL.filter_volume)
 
 def gaussian_taps(sigma, radius=None):

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib, frontend
 from ._lib import (CameraParams, IsoParams, PathtraceParams, RaycastParams, RenderingParams, Stats,
-                   UCHAR, USHORT, FLOAT, TECH_MIP, TECH_ISO)
+                   UCHAR, USHORT, FLOAT, TECH_MIP, TECH_ISO, TECH_TF2D)
 
 NP_DTYPE = {UCHAR: np.uint8, USHORT: np.uint16, FLOAT: np.float32}
 _MT19937_DEFAULT_SEED = 5489   # std::mt19937 default constructor
@@ -131,6 +131,8 @@ class VolumeRenderCL:
             twin.setTransferFunction(self._tff)
             if getattr(self, "_prefix", None) is not None:
                 twin.setTffPrefixSum(self._prefix)
+        if getattr(self, "_tf2d", None) is not None:
+            twin.setTransferFunction2D(*self._tf2d)
         twin._rendering.iteration = self._rendering.iteration
         if getattr(self, "_round_budget", None) is not None:
             twin.setRoundBudget(self._round_budget)
@@ -222,8 +224,9 @@ class VolumeRenderCL:
         self._push_params()
 
     def _advance_iteration(self):
-        # a maximum intensity projection or an isosurface does not accumulate: every frame of it is iteration 0
-        if self._rendering.technique not in (TECH_MIP, TECH_ISO):
+        # a maximum intensity projection, an isosurface or a 2-D transfer function frame does not accumulate: every
+        # frame of it is iteration 0
+        if self._rendering.technique not in (TECH_MIP, TECH_ISO, TECH_TF2D):
             self._rendering.iteration += 1
 
     def runRaycast(self, width, height, out_dev_ptr=None):
@@ -1009,8 +1012,9 @@ class VolumeRenderCL:
         self._rendering.useGradient = 1 if v else 0
 
     def setTechnique(self, tech):
-        """TECH_RAYCAST (0), TECH_PATHTRACE (1), TECH_MIP (2, maximum intensity projection) or TECH_ISO (4, first-hit
-        isosurface: setIsoValue, setIsoRefinement); include/vrhip.h."""
+        """TECH_RAYCAST (0), TECH_PATHTRACE (1), TECH_MIP (2, maximum intensity projection), TECH_ISO (4, first-hit
+        isosurface: setIsoValue, setIsoRefinement) or TECH_TF2D (6, 2-D transfer function: setTransferFunction2D);
+        include/vrhip.h."""
         self._rendering.technique = int(tech)
         self._rendering.iteration = 0
 
@@ -1026,6 +1030,19 @@ class VolumeRenderCL:
         """TECH_ISO: bisection rounds between the last sample below and the first at or above the threshold (0-16).
         Default 4."""
         self._iso.refineSteps = int(steps)
+
+    def setTransferFunction2D(self, table, g_hi):
+        """TECH_TF2D: the 2-D transfer function TF2(value, gradient magnitude).  table: uint8 [n_g, n_v, 4] (row j =
+        gradient bin j, value fastest); g_hi: the gradient magnitude at the table's upper edge, the g_hi of
+        volume_statistics, whose bin centres the entries sit on (frontend.tf2d_from_1d, frontend.tf2d_ramp make
+        tables).  State of its own: setTransferFunction does not touch it and is not needed by TECH_TF2D."""
+        table = np.ascontiguousarray(table, dtype=np.uint8)
+        if table.ndim != 3 or table.shape[2] != 4:
+            raise ValueError("the 2-D transfer function must have shape (n_g, n_v, 4)")
+        self._check(self._lib.vrhip_set_transfer_function_2d(self._h, table.ctypes.data, table.shape[1], table.shape[0],
+                                                             float(g_hi)))
+        self._tf2d = (table.copy(), float(g_hi))   # (shareVolumes hands it to the twin)
+        self._rendering.iteration = 0
 
     def setBBox(self, bl_x, bl_y, bl_z, tr_x, tr_y, tr_z):
         self._camera.bbox_bl[:] = [bl_x, bl_y, bl_z, 0]
