@@ -487,3 +487,31 @@ def test_cli_mip_orbit(vr, tmp_path):
         _conf(vr, view=view, rate=1.5, seed=1234)
         assert _same(vr.runRaycastNoGL(W, H), one[f]), "view %d" % f
     vr.setTechnique(TECH_RAYCAST)
+
+
+def test_cli_two_modes_one_scene(vr, tmp_path):
+    """One tiny scene through two of vrhip_render's output modes, one after the other -- rendered frames (--mip --orbit)
+    and slice views -- with no option of a third mode (depth, mesh, statistics) given: each run's files are the Python
+    arrays of the same scene."""
+    W, H, n = 40, 24, 3
+    scene = ["--synth", "sphere", 32, "UCHAR", "--size", W, H]
+    frames = _cli(scene + ["--mip", "--seed", 1234, "--orbit", 0, 1, 0, n], tmp_path, "frames", W, H)
+    slices = _cli(scene + ["--slice-axis", "Z", 0.25, "--slice-stack", 2], tmp_path, "slices", W, H)
+    assert frames.shape[0] == n and slices.shape[0] == 2
+    for name in ("frames", "slices"):   # the last frame again, alone
+        last = np.fromfile(str(tmp_path / name) + ".rgba.f32", dtype=np.float32).reshape(H, W, 4)
+        assert _same(last, (frames if name == "frames" else slices)[-1])
+        assert not os.path.exists(str(tmp_path / name) + ".depth.f32")
+    vr.synthVolume("sphere", (32, 32, 32), UCHAR)
+    vr.setTransferFunction(frontend.tff_from_stops())
+    vr.setStatsEnabled(False)
+    vr.setBackground((1.0, 1.0, 1.0))   # (as the CLI sets it: alpha 0)
+    _conf(vr, view=frontend.view_matrix(), rate=1.5, seed=1234)   # (the whole box, linear filtering)
+    want = vr.render_slices(W, H, frontend.slice_stack(frontend.axis_slice("z", 0.0), 2, 2.0))
+    assert _same(slices, want) and np.unique(want.reshape(-1, 4), axis=0).shape[0] > 1
+    vr.setTechnique(TECH_MIP)
+    for f, view in enumerate(frontend.orbit_views((0, 1, 0), n)):
+        _conf(vr, view=view, rate=1.5, seed=1234)
+        assert _same(vr.runRaycastNoGL(W, H), frames[f]), "view %d" % f
+    assert np.unique(frames.reshape(-1, 4), axis=0).shape[0] > 1
+    vr.setTechnique(TECH_RAYCAST)
