@@ -46,7 +46,9 @@ public:
     // TECH_ISO: first-hit isosurface (VRHIP_TECHNIQUE_ISO, vrhip.h; no reference counterpart; 3 is unassigned)
     // TECH_TF2D: ray casting through a 2-D transfer function (VRHIP_TECHNIQUE_TF2D, vrhip.h; no reference counterpart;
     //   5 is unassigned)
-    enum technique { TECH_RAYCAST = 0, TECH_PATHTRACE = 1, TECH_MIP = 2, TECH_ISO = 4, TECH_TF2D = 6 };
+    // TECH_PREINT: ray casting with pre-integrated classification of the 1-D transfer function
+    //   (VRHIP_TECHNIQUE_PREINT, vrhip.h; no reference counterpart; 7 is unassigned)
+    enum technique { TECH_RAYCAST = 0, TECH_PATHTRACE = 1, TECH_MIP = 2, TECH_ISO = 4, TECH_TF2D = 6, TECH_PREINT = 8 };
 
     VolumeRenderCL();
     ~VolumeRenderCL();
@@ -101,6 +103,10 @@ public:
     // a ramp over the gradient magnitude that is 0 up to g0 and 1 from g1 on (vrhip_tf2d_build_ramp).  Host only.
     static std::vector<unsigned char> rampTransferFunction2D(const std::vector<unsigned char> &tff, unsigned int nG,
                                                              float gHi, float g0, float g1);
+    // TECH_PREINT (no parameters of its own): the classification of the slab between the sample values sf (front) and
+    // sb (back) with the RGBA8 table `tff`: (Cbar.rgb, abar) (vrhip_preint_slab).  raw: a FLOAT volume's values.  Host
+    // only.  Throws on a table that is empty, above 4096 entries or no multiple of 4 bytes, or a refused value.
+    static std::array<float, 4> preintSlab(const std::vector<unsigned char> &tff, float sf, float sb, bool raw = false);
     void setBBox(float bl_x, float bl_y, float bl_z, float tr_x, float tr_y, float tr_z);
     void setTimestep(const size_t t);
 

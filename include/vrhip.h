@@ -56,7 +56,8 @@ typedef struct vrhip_rendering_params {
     uint32_t useGradient;
     uint32_t technique;  /* 0 ray cast, 1 path tracing, 2 maximum intensity projection (VRHIP_TECHNIQUE_MIP),
                             4 first-hit isosurface (VRHIP_TECHNIQUE_ISO), 6 two-dimensional transfer function
-                            (VRHIP_TECHNIQUE_TF2D); 3 and 5 are unassigned and rejected */
+                            (VRHIP_TECHNIQUE_TF2D), 8 pre-integrated classification (VRHIP_TECHNIQUE_PREINT);
+                            3, 5 and 7 are unassigned and rejected */
     uint32_t seed;
     uint32_t iteration;
 } vrhip_rendering_params; /* 64 bytes */
@@ -154,6 +155,74 @@ typedef struct vrhip_iso_params {
 #define VRHIP_TF2D_MAX_NV 4096u
 #define VRHIP_TF2D_MAX_NG 256u
 #define VRHIP_TF2D_MAX_ENTRIES 65536u
+
+/* rendering_params.technique == 8: emission-absorption ray casting with PRE-INTEGRATED classification (Engel, Kraus,
+ * Ertl 2001, by integral functions; no reference counterpart).  Techniques 0 and 6 classify a ray by
+ * point samples and never see what the transfer function does between two of them; this one classifies the SLAB
+ * between two consecutive samples by the transfer function integrated over the values in between, so a narrow peak
+ * that the data crosses between two samples is always seen.  No new parameters: it reads the 1-D transfer function of
+ * vrhip_set_transfer_function.  The values 3, 5 and 7 are unassigned: "Unknown rendering technique.".
+ *  Ray: exactly technique 0's with object-order ESS off, as for technique 6: t_0 = max(0, tnear), sample k at
+ *   cam + dir * (t_k - offset); composite slab k; stop when the accumulated alpha >= 0.98f; t_{k+1} = t_k + stepSize;
+ *   go on while t_{k+1} < tfar (a step that no longer changes t ends the sequence).
+ *  Sample value: s_k = the filtered, normalised channel-0 value (useLinear: trilinear or nearest; FLOAT: the raw
+ *   value); its table coordinate u_k = coord(s_k) * (float)n - 0.5f, fp32, with coord(x) = x for UCHAR / USHORT and
+ *   x > -1 ? (x < 2 ? x : 2) : -1 for FLOAT (a NaN reads -1): the ray caster's read.  Entry i of the n-entry table
+ *   E (c / 255.0f) sits at u = i.
+ *  c(u): the ray caster's read as a function of a real u -- linear on every segment j = [j, j + 1], 0 <= j <= n - 2,
+ *   between E[j] and E[j + 1]; constant E[0] on the tail (-inf, 0] (segment -1) and E[n - 1] on [n - 1, +inf)
+ *   (segment n - 1).  Segment j has the end entries p = E[clamp(j, 0, n - 1)], q = E[clamp(j + 1, 0, n - 1)].
+ *  Slab k: uf = u_{k-1}, ub = u_k; for k = 0 uf = ub.
+ *   uf == ub (fp32 compare): the slab's colour IS the ray caster's read at s_k: fu = floorf(ub), a = ub - fu,
+ *    lerpf(E[i0], E[i1], a) per channel with i0 = clamp((int)fu, 0, n - 1), i1 = clamp((int)fu + 1, 0, n - 1),
+ *    lerpf(p, q, w) = fmaf(w, q - p, p).  A volume that is constant along a ray renders technique 0's pixel bit for
+ *    bit.
+ *   else, with lo = min(uf, ub), hi = max(uf, ub): abar = the mean of c.a over [lo, hi]; Cbar = the mean of
+ *    c.rgb * c.a over [lo, hi] divided by abar -- the opacity-weighted colour -- and 0 where abar is 0.
+ *   Self-attenuation INSIDE a slab is not modelled (the paper's approximation by integral functions; the full 2-D
+ *   table depends on the step length): a slab that crosses a peak of opacity 1 gets the peak's share of the value
+ *   interval as its opacity, not 1.
+ *  Arithmetic of the means, ONE evaluation order, in double until stated otherwise (each operation rounded on its own,
+ *   no contraction).  part(j, u0, u1), the integral over [u0, u1] inside segment j: h = u1 - u0; on a tail w0 = w1 = 0,
+ *   else w0 = u0 - j, w1 = u1 - j; wm = 0.5 * (w0 + w1); v = 1 - w for each; a(w) = p.a * v + q.a * w,
+ *   c(w) = p.c * v + q.c * w per colour channel;
+ *     A = h * a(wm);   M_c = (h * (1.0 / 6.0)) * ((c(w0) * a(w0) + 4.0 * (c(wm) * a(wm))) + c(w1) * a(w1))
+ *   (midpoint and Simpson's rule: exact for the linear and the quadratic integrand).  Prefix table, n entries of four
+ *   doubles: P[0] = 0, P[i] = P[i - 1] + part(i - 1, i - 1, i).  jl = clamp((int)floorf(lo), -1, n - 1), jh likewise:
+ *     jl == jh: S = part(jl, lo, hi)         -- an interval inside one segment is the closed form alone; two nearly
+ *                                               equal prefix values are never subtracted to get a short interval
+ *     else:     S = (part(jl, lo, jl + 1) + (P[jh] - P[jl + 1])) + part(jh, jh, hi)   per component
+ *   r = 1.0 / (hi - lo); abar = (float)(S.A * r), m_c = (float)(S.M_c * r); from here fp32: Cbar_c = abar > 0 ?
+ *   m_c / abar : 0.  Every term is a sum of products of non-negative numbers, so an interval over which every entry
+ *   that c reads (clamp(jl, 0, n - 1) .. clamp(jh + 1, 0, n - 1)) has alpha 0 gives abar = +0 EXACTLY, whatever the
+ *   colours: leaving such slabs out rests on it.
+ *  Shading and compositing: technique 0's lines on (Cbar, abar).  illumType 1 and abar > 0.1f: C = ((C * 0.15) +
+ *   ((C * ndl) * 0.7)) + spec per channel with the ray caster's central-difference normal at sample k's position
+ *   (technique 6's wording).  opacity = 1 - powr(1 - abar, 1 / samplingRate), result.rgb -= ((bg.rgb - C) * opacity)
+ *   * (1 - alpha), alpha += opacity * (1 - alpha), from result = bg = backgroundColor and alpha = 0.  Pixel:
+ *   (result.rgb, alpha).  A ray that misses the box: backgroundColor unchanged, alpha included.
+ *  Ignored: useGradient, contours, aerial, the prefix sum of vrhip_set_tff_prefix_sum (not required).
+ *   VRHIP_ERR_UNSUPPORTED: illumType 2-5, imgEss, showEss, useAO, iteration > 0, RG / RGBA volumes, a set environment
+ *   map, vrhip_render_samples, vrhip_count_touched*, vrhip_count_fetched.  VRHIP_ERR_NODATA "No transfer function
+ *   set." while none is.
+ *  Cost: a slab that can only read transparent entries is neither classified nor composited; vrhip_set_object_ess: on,
+ *   a sample is not fetched when the cell grid (vrhip_download_cells) proves the slab before it and the slab after it
+ *   transparent: both of a slab's cells have usable bounds and the HULL of their two value ranges reads transparent
+ *   entries only (two transparent ranges on either side of a peak do not make a transparent slab).  No bit of a
+ *   pixel changes either way (backgroundColor finite).  Needs neither ESS bricks nor the prefix sum.
+ *  vrhip_get_stats (vrhip_set_stats_enabled): samples_taken = values fetched, samples_shaded = slabs classified --
+ *   those that can read an entry which is not transparent, whether or not their abar turns out 0 --
+ *   bricks_skipped = samples stepped over without a fetch, rays_hit = rays with alpha > 0; the rest 0.
+ *  State: the integral table and the prefix count are made on the host from the 1-D table when a technique-8 frame
+ *   first needs them after vrhip_set_transfer_function, and read by technique 8 alone.  Selecting the technique or
+ *   building them touches nothing that any other technique, a slice, depth, mesh, statistics or filter call reads --
+ *   with the one exception every frame of every technique shares: the renderer has ONE frame buffer, which a frame
+ *   overwrites and which technique 0 at iteration k > 0 accumulates onto.  A progressive accumulation that is
+ *   started after a technique-8 frame is unchanged bit for bit; one that CONTINUES across a technique-8 frame (or a
+ *   technique 2, 4 or 6 frame) accumulates onto that frame.  Restart it (iteration 0), as the C++ and Python
+ *   setTechnique do. */
+#define VRHIP_TECHNIQUE_PREINT 8u
+#define VRHIP_PREINT_MAX_ENTRIES 4096u   /* the limit of vrhip_set_transfer_function */
 
 typedef struct vrhip_raycast_params {
     float samplingRate;
@@ -300,6 +369,16 @@ int vrhip_tf2d_lookup(const uint8_t *rgba8, uint32_t n_v, uint32_t n_g, float g_
  * VRHIP_ERR_INVALID: a NULL pointer, refused n_v / n_g / g_hi, g0 or g1 not finite, g0 < 0 or g1 <= g0. */
 int vrhip_tf2d_build_ramp(const uint8_t *tf1d_rgba8, uint32_t n_v, uint32_t n_g, float g_hi, float g0, float g1,
                           uint8_t *out_rgba8);
+/* Technique 8 (VRHIP_TECHNIQUE_PREINT above) on the host: no renderer, no device.
+ * vrhip_preint_slab: the slab classification of the n-entry table tff_rgba (4 n floats in [0, 1], the renderer's
+ * c / 255.0f) between the sample values sf (front, s_{k-1}) and sb (back, s_k): out = (Cbar.rgb, abar), the device's
+ * result bit for bit.  raw != 0: FLOAT-volume values (any float, NaN included); raw == 0: normalised values, which
+ * must lie in [-1, 2].  VRHIP_ERR_INVALID: a NULL pointer, n outside 1..4096, an entry outside [0, 1] or a refused
+ * value (out is not written).  It builds the tables on every call.
+ * vrhip_preint_tables: what the renderer uploads -- prefix: the n x 4 doubles P above; nz: n + 1 words, nz[i] = the
+ * number of entries i' < i with alpha != 0 (entries i0..i1 all transparent <=> nz[i1 + 1] == nz[i0]). */
+int vrhip_preint_slab(const float *tff_rgba, uint32_t n, int raw, float sf, float sb, float out[4]);
+int vrhip_preint_tables(const float *tff_rgba, uint32_t n, double *prefix, uint32_t *nz);
 /* generateBricks host part + kernel for every timestep (:614-684, volumeraycast.cl:932-961);
  * also stores raycast.brickRes like :627-631. */
 int vrhip_build_bricks(vrhip_renderer *r);

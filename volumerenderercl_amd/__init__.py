@@ -4,9 +4,9 @@ interface.  The product is `libvrhip.so` (csrc/, C ABI in include/vrhip.h); this
 the thin host-side mirror used by tests, bench.py and the multi-GPU tile driver."""
 from . import _lib, frontend
 from ._lib import (CameraParams, DepthInfo, DepthParams, IndexedMeshInfo, IsoParams, MeshInfo, MeshParams, PathtraceParams, RaycastParams, RenderingParams, SliceParams, Stats,
-                   UCHAR, USHORT, FLOAT, TECH_RAYCAST, TECH_PATHTRACE, TECH_MIP, TECH_ISO, TECH_TF2D)
+                   UCHAR, USHORT, FLOAT, TECH_RAYCAST, TECH_PATHTRACE, TECH_MIP, TECH_ISO, TECH_TF2D, TECH_PREINT)
 from .renderer import VolumeRenderCL
 
 __all__ = ["VolumeRenderCL", "frontend", "_lib", "CameraParams", "RenderingParams",
            "RaycastParams", "PathtraceParams", "IsoParams", "SliceParams", "DepthParams", "DepthInfo", "MeshParams", "MeshInfo", "IndexedMeshInfo", "Stats", "UCHAR", "USHORT", "FLOAT",
-           "TECH_RAYCAST", "TECH_PATHTRACE", "TECH_MIP", "TECH_ISO", "TECH_TF2D"]
+           "TECH_RAYCAST", "TECH_PATHTRACE", "TECH_MIP", "TECH_ISO", "TECH_TF2D", "TECH_PREINT"]

@@ -18,6 +18,8 @@ UCHAR, USHORT, FLOAT = 0, 1, 2
 TECH_RAYCAST, TECH_PATHTRACE, TECH_MIP = 0, 1, 2
 TECH_ISO = 4
 TECH_TF2D = 6
+# pre-integrated classification (VRHIP_TECHNIQUE_PREINT; 7 is unassigned)
+TECH_PREINT = 8
 # the limits of a 2-D transfer function (vrhip_tf2d_params_check): those of the statistics histogram
 TF2D_MAX_NV, TF2D_MAX_NG, TF2D_MAX_ENTRIES = 4096, 256, 65536
 
@@ -260,6 +262,8 @@ SYMBOLS = {
     "vrhip_tf2d_lookup": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float,
                                     C.POINTER(C.c_float)]),
     "vrhip_tf2d_build_ramp": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "vrhip_preint_slab": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float)]),
+    "vrhip_preint_tables": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vrhip_build_bricks": (C.c_int, [_H]),
     "vrhip_get_brick_info": (C.c_int, [_H, _U3, C.POINTER(C.c_float), _U3]),
     "vrhip_download_bricks": (C.c_int, [_H, C.c_uint32, C.c_void_p, C.c_size_t]),

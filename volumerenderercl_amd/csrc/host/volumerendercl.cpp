@@ -357,8 +357,19 @@ void VolumeRenderCL::setBackground(std::array<float, 4> color)   // :1025-1030
 void VolumeRenderCL::advanceIteration()
 {
     if (_rendering_params.technique != TECH_MIP && _rendering_params.technique != TECH_ISO &&
-        _rendering_params.technique != TECH_TF2D)
+        _rendering_params.technique != TECH_TF2D && _rendering_params.technique != TECH_PREINT)
         _rendering_params.iteration++;
+}
+
+std::array<float, 4> VolumeRenderCL::preintSlab(const std::vector<unsigned char> &tff, float sf, float sb, bool raw)
+{
+    std::vector<float> entries(tff.size());
+    for (size_t i = 0; i < tff.size(); ++i) entries[i] = static_cast<float>(tff[i]) / 255.0f;
+    std::array<float, 4> out{};
+    if (tff.empty() || tff.size() % 4 != 0 ||
+        vrhip_preint_slab(entries.data(), static_cast<uint32_t>(tff.size() / 4), raw ? 1 : 0, sf, sb, out.data()) != VRHIP_OK)
+        throw std::invalid_argument("preintSlab: invalid table size or sample value.");
+    return out;
 }
 
 void VolumeRenderCL::setTransferFunction2D(const std::vector<unsigned char> &table, unsigned int nV, unsigned int nG,

@@ -38,6 +38,13 @@
         "         [--tf2d-ramp NG GHI G0 G1]       (the same from the command's 1-D table: NG rows of it, their opacity\n"
         "                                           scaled by a ramp over the gradient magnitude, 0 up to G0 and 1 from G1\n"
         "                                           on -- boundary emphasis)\n"
+        "         [--preint]                       (technique 8, pre-integrated classification: the slab between two\n"
+        "                                           samples is coloured by the transfer function integrated over the\n"
+        "                                           values in between, so a narrow peak is never stepped over; the\n"
+        "                                           command's 1-D table (--tf); --illum 0 or 1; independent frames like\n"
+        "                                           --mip; combines with --orbit, --camera-path, --frames-per-launch and\n"
+        "                                           --rgba8; not with --pathtrace, --mip, --iso, --tf2d, --tf2d-ramp, --ao,\n"
+        "                                           --show-ess, --img-ess, --env, --ranks)\n"
         "         [--samples-per-launch K]         (--pathtrace: the N samples in launch sets of K -- vrhip_render_samples,\n"
         "                                           the same image bit for bit; 0 = the library's default set size, the\n"
         "                                           default; 1 = one launch per sample, as before; with --bench: one\n"
@@ -230,6 +237,7 @@ Options parse_args(int argc, char **argv)
         else if (a == "--pathtrace") te.pathtrace = true;
         else if (a == "--extinction") { need(i, 1); te.extinction = num(); }
         else if (a == "--mip") te.mip = true;
+        else if (a == "--preint") te.preint = true;
         else if (a == "--iso") { need(i, 1); te.iso = true; te.iso_value = num(); }
         else if (a == "--iso-refine") { need(i, 1); te.have_iso_refine = true; te.iso_refine = integer(); }
         else if (a == "--tf2d") { need(i, 4); t2.table = true; t2.file = argv[++i]; t2.nv = lng(); t2.ng = lng(); t2.ghi = num(); }
@@ -349,6 +357,8 @@ void validate(const Options &o)
         if (t2.ramp && (!std::isfinite(t2.g0) || !std::isfinite(t2.g1) || !(float(t2.g0) >= 0.f) || !(float(t2.g1) > float(t2.g0))))
             usage();
     }
+    // (--ranks: refused like technique 6's options, not wired through the C++ tile gather)
+    if (te.preint && (te.pathtrace || te.mip || te.iso || t2.any() || ray_caster_extras || ranks > 0)) usage();
     if (o.out.rgba8 && ranks > 0) {
         std::cerr << "--rgba8 cannot be combined with --ranks: the C++ tile gather carries float pixels "
                      "(8-bit frames over several GPUs: the Python TileDriver, pixel_format=\"rgba8\")" << std::endl;
@@ -358,7 +368,7 @@ void validate(const Options &o)
     if (slice_opt && !sl.any()) usage();
     if (sl.any()) {
         if (sl.have_axis && sl.have_plane) usage();
-        if (te.mip || te.iso || t2.any() || te.pathtrace || vw.have_orbit || vw.have_path_arg || ranks > 0) usage();
+        if (te.mip || te.iso || t2.any() || te.preint || te.pathtrace || vw.have_orbit || vw.have_path_arg || ranks > 0) usage();
         if (sl.have_axis && (sl.axis < 0 || !std::isfinite(sl.pos))) usage();
         for (double c : sl.vec) if (!std::isfinite(c)) usage();
         if (sl.have_slab && (sl.slab_n < 1 || sl.slab_n > int(VRHIP_SLICE_MAX_SAMPLES) || !std::isfinite(sl.slab_t) ||
@@ -377,7 +387,8 @@ void validate(const Options &o)
     if ((de.have_refine || de.have_rect) && !de.on) usage();
     if (de.on) {
         if (de.mode != "iso" && de.mode != "max" && de.mode != "opacity") usage();
-        if (te.pathtrace || te.mip || te.iso || t2.any() || sl.any() || slice_opt || ranks > 0 || ba.frames_per_launch > 0) usage();
+        if (te.pathtrace || te.mip || te.iso || t2.any() || te.preint || sl.any() || slice_opt || ranks > 0 || ba.frames_per_launch > 0)
+            usage();
         if (many_frames) usage();
         if (!std::isfinite(de.threshold) || de.refine < 0 || de.refine > 16) usage();
         if (de.have_rect) {
@@ -392,7 +403,7 @@ void validate(const Options &o)
     if (!o.filters.empty() && (ranks > 0 || o.volume.downsample)) usage();
     // numbers about the volume (--stats) or triangles of it (--mesh), not a picture: what selects, shapes or
     // multiplies frames has nothing to act on
-    const bool a_picture = te.pathtrace || te.mip || te.iso || t2.any() || te.have_iso_refine || sl.any() || slice_opt || de.on ||
+    const bool a_picture = te.pathtrace || te.mip || te.iso || t2.any() || te.preint || te.have_iso_refine || sl.any() || slice_opt || de.on ||
                            ranks > 0 || ba.frames_per_launch > 0 || many_frames || o.volume.downsample || !o.out.dump_tf.empty() ||
                            ba.bench || ba.independent;
     if (st.on) {

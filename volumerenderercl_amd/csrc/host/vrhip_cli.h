@@ -43,8 +43,8 @@ struct Options {
         double rate = 1.5;
         std::array<float, 4> bg = {{1, 1, 1, 1}};
     } render;
-    struct Technique {   // --pathtrace, --extinction, --mip, --iso, --iso-refine
-        bool pathtrace = false, mip = false, iso = false, have_iso_refine = false;
+    struct Technique {   // --pathtrace, --extinction, --mip, --iso, --iso-refine, --preint
+        bool pathtrace = false, mip = false, iso = false, have_iso_refine = false, preint = false;
         double extinction = 100.0, iso_value = 0.5;
         int iso_refine = 4;
     } tech;

@@ -603,6 +603,7 @@ bool setup_renderer(VolumeRenderCL &vr, Options &o, int dev)
         vr.setExtinction(o.tech.extinction);
     }
     if (o.tech.mip) vr.setTechnique(VolumeRenderCL::TECH_MIP);
+    if (o.tech.preint) vr.setTechnique(VolumeRenderCL::TECH_PREINT);
     if (o.tech.iso) {
         vr.setTechnique(VolumeRenderCL::TECH_ISO);
         vr.setIsoValue(float(o.tech.iso_value));

@@ -76,6 +76,14 @@ struct Tf2dView {
     float inv_ghi;           // 1.0f / g_hi, computed once
 };
 
+// Technique 8 (pre-integrated classification): the 1-D table and what vrhip_preint_tables makes of it on the host.
+struct PreintView {
+    const float4 *tff;       // the ray caster's table (TfView::tff), n entries
+    const double *prefix;    // n entries of four doubles: the integrals of alpha and of r, g, b x alpha over [0, i]
+    const uint32_t *nz;      // n + 1 words: nz[i] = the number of entries i' < i with alpha != 0
+    uint32_t n;
+};
+
 // ESS decision per brick, precomputed from (bricks, TF, prefix sum): bit = 1 when the
 // reference's test `TF(max).a < 1e-6 && prefix[min] == prefix[max]` (volumeraycast.cl:
 // 777-787) holds.  x-fastest bit index; word n_words holds the decision for the (0,0) value
@@ -346,6 +354,7 @@ struct RaycastLaunch {
     const float2 *cell_minmax;
     int cell_minmax_fine;
     Tf2dView tf2d;             // technique 6: its table (cell_minmax as for techniques 2 and 4)
+    PreintView preint;         // technique 8: the 1-D table and its integrals (cell_minmax likewise)
 };
 
 // hipLaunchKernelGGL, or -- with an event -- the launch whose completion the event is bound to
@@ -437,6 +446,8 @@ hipError_t vr_launch_mip(const RaycastLaunch &a, hipStream_t stream);
 hipError_t vr_launch_iso(const RaycastLaunch &a, hipStream_t stream);
 // technique 6 (two-dimensional transfer function): one launch of the same shape; vr_tf2d.hip
 hipError_t vr_launch_tf2d(const RaycastLaunch &a, hipStream_t stream);
+// technique 8 (pre-integrated classification): one launch of the same shape; vr_preint.hip
+hipError_t vr_launch_preint(const RaycastLaunch &a, hipStream_t stream);
 // slice views (vrhip_render_slices): n_slices images of W x H pixels, one wave per 8x8 patch of every slice, into
 // out_dev[n_slices][H][W]; slices_dev: the n_slices parameter blocks in device memory; vr_slice.hip
 hipError_t vr_launch_slices(const VolView &vol, int format, const TfView &tf, const vrhip_slice_params *slices_dev,
@@ -566,7 +577,8 @@ hipError_t vr_launch_filter(const FilterLaunch &a, void *dst, unsigned long long
 // the frame launch for a.render.technique
 inline hipError_t vr_launch_frame(const RaycastLaunch &a, hipStream_t stream)
 {
-    return a.render.technique == VRHIP_TECHNIQUE_TF2D  ? vr_launch_tf2d(a, stream)
+    return a.render.technique == VRHIP_TECHNIQUE_PREINT ? vr_launch_preint(a, stream)
+           : a.render.technique == VRHIP_TECHNIQUE_TF2D ? vr_launch_tf2d(a, stream)
            : a.render.technique == VRHIP_TECHNIQUE_ISO ? vr_launch_iso(a, stream)
            : a.render.technique == VRHIP_TECHNIQUE_MIP ? vr_launch_mip(a, stream)
            : a.render.technique == 1                   ? vr_launch_pathtrace(a, stream)

@@ -120,6 +120,14 @@ struct vrhip_renderer {
     uint32_t tf2d_nv = 0, tf2d_ng = 0;
     float tf2d_inv_ghi = 0.f;
 
+    // the 1-D table as uploaded to `tff` (n entries of four floats): what ensure_preint integrates, without a read-back
+    std::vector<float> tff_host;
+    // technique 8's integral table and prefix count (PreintView), made from tff_host by ensure_preint when a
+    // technique-8 frame first needs them; read by technique 8's frames alone
+    DevBuf<double> preint_prefix;
+    DevBuf<uint32_t> preint_nz;
+    bool preint_valid = false;
+
     uint32_t brick_tex[3] = {0, 0, 0}, brick_edge[3] = {0, 0, 0};
     float brick_res[3] = {1, 1, 1};
     bool bricks_valid = false;
@@ -465,6 +473,16 @@ inline Tf2dView make_tf2d_view(const vrhip_renderer *r)
     return t;
 }
 
+inline PreintView make_preint_view(const vrhip_renderer *r)
+{
+    PreintView t;
+    t.tff = r->tff;
+    t.prefix = r->preint_prefix;
+    t.nz = r->preint_nz;
+    t.n = r->tff_n;
+    return t;
+}
+
 // what make_ray derives the camera from: the frame size and the reference's padded launch size
 inline void set_frame_geometry(FrameView *f, uint32_t width, uint32_t height)
 {
@@ -517,6 +535,8 @@ bool mip_skips(const vrhip_renderer *r);
 //     tf2d_nv / _ng / _inv_ghi)                      |   function_2d       | set time, never stale, nothing derives
 //                                                    |                     | from it (technique 6 reads it as it is,
 //                                                    |                     | with the cell (min,max) like 2 and 4)
+//   technique 8's integral table and prefix count    | ensure_preint       | TF
+//     (preint_prefix, preint_nz; preint_valid)       |                     |
 //
 // A voxel write into ANY slot makes the renderer-wide tables stale, not only one into the current step (the code
 // never looked at which).  fp_candidate / fp_candidate_frames count frames, and survive everything but a change
@@ -574,7 +594,11 @@ inline void tf_changed(vrhip_renderer *r)
 {
     r->skip_dirty = true;
     cells_tables_stale(r);
+    r->preint_valid = false;
 }
+
+// ensure_preint has made technique 8's tables from the transfer function as it is
+inline void preint_built(vrhip_renderer *r) { r->preint_valid = true; }
 
 // The 2-D transfer function (technique 6): the table is being replaced (n_v = 0: none is set until tf2d_set), then
 // is whole.  No other derived state depends on it, and tf_changed does not touch it.

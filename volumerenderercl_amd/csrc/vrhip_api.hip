@@ -118,10 +118,12 @@ bool ray_skip_empty(const vrhip_renderer *r)
 }
 
 // the techniques that are one launch over the cells' (min, max): maximum intensity projection, first-hit isosurface
-// ... and the 2-D transfer function, which reads them the same way and no table made from the 1-D one
+// ... and the 2-D transfer function, which reads them the same way and no table made from the 1-D one; pre-integrated
+// classification likewise (its own tables come from the 1-D one, but not through the cells)
 bool minmax_technique(uint32_t t)
 {
-    return t == VRHIP_TECHNIQUE_MIP || t == VRHIP_TECHNIQUE_ISO || t == VRHIP_TECHNIQUE_TF2D;
+    return t == VRHIP_TECHNIQUE_MIP || t == VRHIP_TECHNIQUE_ISO || t == VRHIP_TECHNIQUE_TF2D ||
+           t == VRHIP_TECHNIQUE_PREINT;
 }
 
 // Sharers of `owner` lose their (borrowed) volumes: nothing of theirs points into the owner any more.
@@ -136,6 +138,28 @@ void detach_sharers(vrhip_renderer *owner)
 }
 
 } // namespace
+
+// Technique 8's tables (PreintView): made on the host from the host's copy of the 1-D table (tff_host, kept by
+// vrhip_set_transfer_function) when a technique-8 frame first needs them after that call (tf_changed makes them
+// stale).  Touches nothing else.  The stream is waited for only because a frame in flight may still read the old ones.
+int ensure_preint(vrhip_renderer *r)
+{
+    if (r->preint_valid && r->preint_prefix && r->preint_nz) return VRHIP_OK;
+    const uint32_t n = r->tff_n;
+    std::vector<double> prefix(4 * (size_t)n);
+    std::vector<uint32_t> nz(n + 1);
+    VR_REQUIRE(r, r->tff_host.size() == 4 * (size_t)n &&
+                      vrhip_preint_tables(r->tff_host.data(), n, prefix.data(), nz.data()) == VRHIP_OK, VRHIP_ERR_INVALID,
+               "pre-integrated classification: the transfer function could not be integrated.");
+    VR_HIP(r, hipStreamSynchronize(r->stream));
+    int rc = grow(r, r->preint_prefix, prefix.size() * sizeof(double));
+    if (!rc) rc = grow(r, r->preint_nz, nz.size() * sizeof(uint32_t));
+    if (rc) return rc;
+    VR_HIP(r, hipMemcpy(r->preint_prefix, prefix.data(), prefix.size() * sizeof(double), hipMemcpyHostToDevice));
+    VR_HIP(r, hipMemcpy(r->preint_nz, nz.data(), nz.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    preint_built(r);
+    return VRHIP_OK;
+}
 
 // (declared in vr_renderer.h: vrhip_depth_api.hip asks the same questions)
 // Technique 2 steps over samples that cannot raise the running maximum when object-order ESS is on, technique 4
@@ -229,8 +253,8 @@ int check_renderable(vrhip_renderer *r, uint32_t width, uint32_t height)
                    "No transfer function prefix sum set.");
     }
     VR_REQUIRE(r, r->render.technique <= VRHIP_TECHNIQUE_MIP || r->render.technique == VRHIP_TECHNIQUE_ISO ||
-                      r->render.technique == VRHIP_TECHNIQUE_TF2D,
-               VRHIP_ERR_INVALID, "Unknown rendering technique.");   // (3 and 5 are unassigned)
+                      r->render.technique == VRHIP_TECHNIQUE_TF2D || r->render.technique == VRHIP_TECHNIQUE_PREINT,
+               VRHIP_ERR_INVALID, "Unknown rendering technique.");   // (3, 5 and 7 are unassigned)
     // the path-tracing branch of the kernel returns before illumType is looked at (:686-706); technique 2 ignores it
     VR_REQUIRE(r, r->render.illumType <= 5 || r->render.technique != 0, VRHIP_ERR_INVALID,
                "Unknown illumination type.");
@@ -275,6 +299,20 @@ int check_renderable(vrhip_renderer *r, uint32_t width, uint32_t height)
                    "2-D transfer function: frames do not accumulate (iteration must be 0).");
         VR_REQUIRE(r, r->channels == 1, VRHIP_ERR_UNSUPPORTED, "2-D transfer function: RG / RGBA volumes are not supported.");
         VR_REQUIRE(r, !r->env, VRHIP_ERR_UNSUPPORTED, "2-D transfer function: environment maps are not supported.");
+    }
+    if (r->render.technique == VRHIP_TECHNIQUE_PREINT) {   // what pre-integrated classification does not define
+        const vrhip_rendering_params &rp = r->render;
+        VR_REQUIRE(r, rp.illumType <= 1, VRHIP_ERR_UNSUPPORTED,
+                   "pre-integrated classification: illumType 0 (flat) and 1 (central differences) only.");
+        VR_REQUIRE(r, !rp.imgEss && !rp.showEss, VRHIP_ERR_UNSUPPORTED,
+                   "pre-integrated classification: image-order ESS and showEss are not supported.");
+        VR_REQUIRE(r, !r->raycast.useAO, VRHIP_ERR_UNSUPPORTED,
+                   "pre-integrated classification: ambient occlusion is not supported.");
+        VR_REQUIRE(r, rp.iteration == 0, VRHIP_ERR_UNSUPPORTED,
+                   "pre-integrated classification: frames do not accumulate (iteration must be 0).");
+        VR_REQUIRE(r, r->channels == 1, VRHIP_ERR_UNSUPPORTED,
+                   "pre-integrated classification: RG / RGBA volumes are not supported.");
+        VR_REQUIRE(r, !r->env, VRHIP_ERR_UNSUPPORTED, "pre-integrated classification: environment maps are not supported.");
     }
     // technique 1 and the traffic / downsampling helpers read channel 0 only, like the kernel's
     // .x readers; nothing else to check for CL_RG / CL_RGBA volumes
@@ -642,6 +680,7 @@ void fill_launch(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t ou
         }
     }
     if (r->render.technique == VRHIP_TECHNIQUE_TF2D) a->tf2d = make_tf2d_view(r);
+    if (r->render.technique == VRHIP_TECHNIQUE_PREINT) a->preint = make_preint_view(r);
     a->format = r->format;
     a->use_ess = r->use_ess ? 1 : 0;
     a->instr = r->stats_enabled ? 1 : 0;
@@ -788,8 +827,13 @@ int prepare_render(vrhip_renderer *r, uint32_t width, uint32_t height, uint32_t 
     if (r->render.technique == 1 ? r->pt_cull : minmax_technique(r->render.technique) ? mip_skips(r) : ray_skip_empty(r)) {
         // (techniques 2 and 4 read the (min, max) of the grid the empty bits live on: built with them)
         // (technique 6 may have no 1-D transfer function to make the tables from: the pairs and the geometry alone)
+        // (technique 8 reads none of them either: it is held to building nothing another technique reads)
         rc = ensure_cells(r, r->render.technique == 1, r->render.technique != 1,
-                          r->render.technique != VRHIP_TECHNIQUE_TF2D);
+                          r->render.technique != VRHIP_TECHNIQUE_TF2D && r->render.technique != VRHIP_TECHNIQUE_PREINT);
+        if (rc) return rc;
+    }
+    if (r->render.technique == VRHIP_TECHNIQUE_PREINT) {
+        rc = ensure_preint(r);
         if (rc) return rc;
     }
     return ensure_queue(r, width, height, tile_w, tile_h, tile_ids, n_tiles, n_frames, frame_stride);
@@ -808,6 +852,8 @@ int count_touched_impl(vrhip_renderer *r, uint32_t width, uint32_t height, uint3
                "vrhip_count_touched / vrhip_count_fetched: not supported with isosurface rendering.");
     VR_REQUIRE(r, r->render.technique != VRHIP_TECHNIQUE_TF2D, VRHIP_ERR_UNSUPPORTED,
                "vrhip_count_touched / vrhip_count_fetched: not supported with the 2-D transfer function.");
+    VR_REQUIRE(r, r->render.technique != VRHIP_TECHNIQUE_PREINT, VRHIP_ERR_UNSUPPORTED,
+               "vrhip_count_touched / vrhip_count_fetched: not supported with pre-integrated classification.");
     int rc = prepare_render(r, width, height, tile_w, tile_h, tile_ids, n_tiles);
     if (rc) return rc;
     const size_t mb = (size_t)((r->res[0] + 3) / 4) * ((r->res[1] + 3) / 4) * ((r->res[2] + 3) / 4);
@@ -1278,6 +1324,7 @@ int vrhip_set_transfer_function(vrhip_renderer *r, const uint8_t *rgba8, uint32_
     const int rc = grow(r, r->tff, n_entries * sizeof(float4));
     if (rc) return rc;
     VR_HIP(r, hipMemcpy(r->tff, table.data(), n_entries * sizeof(float4), hipMemcpyHostToDevice));
+    r->tff_host.assign(&table[0].x, &table[0].x + 4 * (size_t)n_entries);   // (technique 8 integrates it: ensure_preint)
     r->tff_n = n_entries;
     tf_changed(r);
     return VRHIP_OK;
@@ -1521,7 +1568,7 @@ int vrhip_render_batch_views(vrhip_renderer *r, uint32_t width, uint32_t height,
     VR_REQUIRE(r, (rp.technique == 0 || minmax_technique(rp.technique)) && rp.iteration == 0 && !rp.imgEss &&
                       !r->raycast.useAO,
                VRHIP_ERR_UNSUPPORTED,
-               "vrhip_render_batch: technique 0, 2, 4 or 6 only, iteration 0, no image-order ESS, no ambient occlusion");
+               "vrhip_render_batch: technique 0, 2, 4, 6 or 8 only, iteration 0, no image-order ESS, no ambient occlusion");
     const uint32_t packed = tile_ids ? n_tiles * tile_w * tile_h : width * height;
     VR_REQUIRE(r, out_frame_stride == 0 || out_frame_stride >= packed, VRHIP_ERR_INVALID,
                "vrhip_render_batch: frame stride smaller than a frame");

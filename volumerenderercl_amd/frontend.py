@@ -566,6 +566,23 @@ def tf2d_lookup(table, g_hi, s, m):
     return np.array(out[:], dtype=np.float32)
 
 
+# ---- pre-integrated classification (include/vrhip.h "technique == 8")
+
+def preint_slab(tff, sf, sb, raw=False):
+    """Technique 8's classification of the slab between the sample values sf (front) and sb (back) with the 1-D table
+    tff (uint8 [n, 4], as setTransferFunction takes it): float32 (Cbar.rgb, abar), the opacity-weighted mean colour and
+    the mean opacity of the transfer function over the values in between (vrhip_preint_slab: host only, the device's
+    result bit for bit).  raw: the values are a FLOAT volume's (any float); otherwise normalised ones in [-1, 2]."""
+    import ctypes as C
+    from . import _lib
+    entries = (_tf1d(tff).astype(np.float32) / np.float32(255.0)).astype(np.float32)
+    out = (C.c_float * 4)()
+    rc = _lib.load().vrhip_preint_slab(entries.ctypes.data, entries.shape[0], 1 if raw else 0, float(sf), float(sb), out)
+    if rc != _lib.OK:
+        raise ValueError("preint_slab: tables of 1..4096 entries; values that are not raw must lie in [-1, 2]")
+    return np.array(out[:], dtype=np.float32)
+
+
 # ---- volume filters (include/vrhip.h "volume filters"; VolumeRenderCL.filter_volume)
 
 def gaussian_taps(sigma, radius=None):

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib, frontend
 from ._lib import (CameraParams, IsoParams, PathtraceParams, RaycastParams, RenderingParams, Stats,
-                   UCHAR, USHORT, FLOAT, TECH_MIP, TECH_ISO, TECH_TF2D)
+                   UCHAR, USHORT, FLOAT, TECH_MIP, TECH_ISO, TECH_TF2D, TECH_PREINT)
 
 NP_DTYPE = {UCHAR: np.uint8, USHORT: np.uint16, FLOAT: np.float32}
 _MT19937_DEFAULT_SEED = 5489   # std::mt19937 default constructor
@@ -224,9 +224,9 @@ class VolumeRenderCL:
         self._push_params()
 
     def _advance_iteration(self):
-        # a maximum intensity projection, an isosurface or a 2-D transfer function frame does not accumulate: every
-        # frame of it is iteration 0
-        if self._rendering.technique not in (TECH_MIP, TECH_ISO, TECH_TF2D):
+        # a maximum intensity projection, an isosurface, a 2-D transfer function or a pre-integrated frame does not
+        # accumulate: every frame of it is iteration 0
+        if self._rendering.technique not in (TECH_MIP, TECH_ISO, TECH_TF2D, TECH_PREINT):
             self._rendering.iteration += 1
 
     def runRaycast(self, width, height, out_dev_ptr=None):
@@ -1013,7 +1013,8 @@ class VolumeRenderCL:
 
     def setTechnique(self, tech):
         """TECH_RAYCAST (0), TECH_PATHTRACE (1), TECH_MIP (2, maximum intensity projection), TECH_ISO (4, first-hit
-        isosurface: setIsoValue, setIsoRefinement) or TECH_TF2D (6, 2-D transfer function: setTransferFunction2D);
+        isosurface: setIsoValue, setIsoRefinement), TECH_TF2D (6, 2-D transfer function: setTransferFunction2D) or
+        TECH_PREINT (8, pre-integrated classification of the 1-D transfer function: no parameters of its own);
         include/vrhip.h."""
         self._rendering.technique = int(tech)
         self._rendering.iteration = 0
