@@ -10,7 +10,7 @@ import pytest
 from oracle import vro
 from tests import common, scenes
 from tests.scenes import FLOAT_PALETTES
-from tests.test_gpu_parity import SEED, TOL, _random_scene, _setup
+from tests.test_gpu_parity import SEED, TOL, _setup
 from tests.test_oracle_float_range import _bricks_ref
 from volumerenderercl_amd import FLOAT, VolumeRenderCL, frontend
 
@@ -300,10 +300,10 @@ def test_cell_grids_float_range(palette, monkeypatch):
 
 @pytest.mark.parametrize("case", range(16))
 def test_randomised_float_range_scenes(vr, case):
-    """_random_scene with FLOAT forced, remapped v * scale + offset: scale in {1, 255, 4096, 1e7}, offset in
+    """scenes.random_scene with FLOAT forced, remapped v * scale + offset: scale in {1, 255, 4096, 1e7}, offset in
     {0, -scale / 2, -1024}."""
     rng = np.random.default_rng(20261016 + case)
-    vol, fmt, tff, view, kw, W, H = _random_scene(rng)
+    vol, fmt, tff, view, kw, W, H = scenes.random_scene(rng)
     if fmt != FLOAT:
         vol = vol.astype(np.float32) / np.float32(255.0 if fmt == 0 else 65535.0)
     scale = [1.0, 255.0, 4096.0, 1e7][case % 4]

@@ -2440,50 +2440,12 @@ def test_product_library_refuses_the_experiment_kernels(monkeypatch):
         monkeypatch.delenv(var)
 
 
-def _random_scene(rng):
-    """A scene drawn from the parameter space the reference's GUI can reach: voxel type, odd non-cubic resolution,
-    anisotropic slice thickness, empty halves, transfer-function stops, camera inside / outside / orthographic,
-    clip box, sampling rate, shading, ESS, filtering, jitter seed, odd viewports."""
-    fmt = [UCHAR, USHORT, FLOAT][int(rng.integers(3))]
-    res = tuple(int(v) for v in rng.integers(17, 70, size=3))
-    vol = common.noise_volume(res, fmt, seed=int(rng.integers(1 << 30)), smooth=bool(rng.integers(2)))
-    if rng.random() < 0.5:   # a slab of nothing: bricks to skip, cells to step over
-        ax, cut = int(rng.integers(3)), float(rng.uniform(0.2, 0.6))
-        sl = [slice(None)] * 3
-        n = vol.shape[ax]
-        sl[ax] = slice(0, int(n * cut)) if rng.random() < 0.5 else slice(int(n * (1 - cut)), n)
-        vol[tuple(sl)] = 0
-    pos = np.sort(rng.uniform(0.02, 0.98, size=int(rng.integers(1, 4))))
-    stops = [(0.0, (0, 0, 0, 0))]
-    for p in pos:
-        stops.append((float(p), tuple(int(v) for v in rng.integers(0, 256, size=3)) +
-                      (int(rng.integers(0, 256)) if rng.random() < 0.7 else 0,)))
-    stops.append((1.0, tuple(int(v) for v in rng.integers(0, 256, size=3)) + (int(rng.integers(0, 256)),)))
-    tff = frontend.tff_from_stops(stops)
-    q = frontend.quat_from_axis_angle(tuple(rng.normal(size=3)), float(rng.uniform(0, 360)))
-    z = float(rng.choice([rng.uniform(0.2, 0.9), rng.uniform(1.2, 4.0)]))
-    view = frontend.view_matrix(q, (float(rng.uniform(-0.3, 0.3)), float(rng.uniform(-0.3, 0.3)), z))
-    kw = {"illum": int(rng.integers(2)), "ess": bool(rng.random() < 0.75), "linear": bool(rng.random() < 0.85),
-          "ortho": bool(rng.random() < 0.2), "rate": float(rng.choice([0.5, 1.0, 1.5, 2.0, 3.1])),
-          "gradient_bg": bool(rng.random() < 0.3), "seed": int(rng.integers(1, 1 << 32))}
-    if rng.random() < 0.3:
-        lo = rng.uniform(-1.0, -0.2, size=3)
-        hi = rng.uniform(0.2, 1.0, size=3)
-        kw["bbox"] = tuple(float(v) for v in lo) + tuple(float(v) for v in hi)
-    if rng.random() < 0.3:
-        kw["thickness"] = tuple(float(v) for v in rng.choice([0.5, 1.0, 1.0, 2.0, 3.3], size=3))
-    if rng.random() < 0.25:
-        kw["background"] = tuple(float(v) for v in rng.uniform(0, 1, size=3)) + (1.0,)
-    W, H = int(rng.integers(33, 150)), int(rng.integers(33, 120))
-    return vol, fmt, tff, view, kw, W, H
-
-
 @pytest.mark.parametrize("case", range(48))
 def test_randomised_scenes_match_oracle(vr, case):
     """Scenes nobody wrote by hand (seeded: the same 48 every run): instrumented and production kernels against the
     oracle, image and work counters (_compare)."""
     rng = np.random.default_rng(20261004 + case)
-    vol, fmt, tff, view, kw, W, H = _random_scene(rng)
+    vol, fmt, tff, view, kw, W, H = scenes.random_scene(rng)
     _setup(vr, vol, fmt, tff, view, **kw)
     try:
         vr.updateOutputImg(W, H)
@@ -2500,7 +2462,7 @@ def test_randomised_scenes_with_the_rarer_modes_match_oracle(vr, case):
     """The same with the modes that live in kernel variants of their own: illumination 2-5, contours, the depth
     cue, ambient occlusion, showEss, nearest filtering, progressive accumulation over two iterations."""
     rng = np.random.default_rng(77261004 + case)
-    vol, fmt, tff, view, kw, W, H = _random_scene(rng)
+    vol, fmt, tff, view, kw, W, H = scenes.random_scene(rng)
     kw.update(illum=int(rng.integers(0, 6)), contours=bool(rng.random() < 0.3), aerial=bool(rng.random() < 0.3),
               ao=bool(rng.random() < 0.25), show_ess=bool(rng.random() < 0.25), linear=bool(rng.random() < 0.6))
     _setup(vr, vol, fmt, tff, view, **kw)
@@ -2515,7 +2477,7 @@ def test_randomised_scenes_with_the_rarer_modes_match_oracle(vr, case):
 def test_randomised_scenes_path_traced_match_oracle(vr, case):
     """The same through the path tracer (technique 1), with a random extinction."""
     rng = np.random.default_rng(55261004 + case)
-    vol, fmt, tff, view, kw, W, H = _random_scene(rng)
+    vol, fmt, tff, view, kw, W, H = scenes.random_scene(rng)
     kw = {k: v for k, v in kw.items() if k in ("seed", "bbox", "thickness", "background", "ortho", "gradient_bg")}
     kw["ext"] = float(rng.choice([10.0, 40.0, 100.0, 250.0]))
     _setup(vr, vol, fmt, tff, view, technique=1, **kw)
@@ -2533,7 +2495,7 @@ def test_randomised_batches_of_tile_subsets_equal_their_frames(vr, case):
     every frame equals the same region of the frame rendered alone, which _compare checks against the oracle."""
     import torch
     rng = np.random.default_rng(99261004 + case)
-    vol, fmt, tff, view, kw, W, H = _random_scene(rng)
+    vol, fmt, tff, view, kw, W, H = scenes.random_scene(rng)
     kw["linear"] = True if rng.random() < 0.8 else kw["linear"]
     _setup(vr, vol, fmt, tff, view, **kw)
     try:
@@ -2570,7 +2532,7 @@ def test_randomised_frame_sequences_match_oracle(vr, case):
     frames, with whatever shading / filtering the scene drew) or progressive accumulation (the running mean over
     three iterations with their own jitter seeds), ray caster or path tracer."""
     rng = np.random.default_rng(33261004 + case)
-    vol, fmt, tff, view, kw, W, H = _random_scene(rng)
+    vol, fmt, tff, view, kw, W, H = scenes.random_scene(rng)
     img_ess = case % 2 == 0
     technique = 1 if (not img_ess and rng.random() < 0.4) else 0
     if technique:

@@ -10,7 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import common, tf2d_ref
+from tests import common, scenes, tf2d_ref
 from volumerenderercl_amd import FLOAT, TECH_RAYCAST, TECH_TF2D, UCHAR, USHORT, VolumeRenderCL, _lib, frontend
 
 pytestmark = pytest.mark.gpu
@@ -56,9 +56,9 @@ def _as(fmt, f):
 
 def _sphere(fmt, n=40):
     """A ball whose value falls off linearly from the centre: a shell of every value, |gradient| ~ 0.055 per voxel
-    inside, 0 outside."""
-    g = np.linspace(-1, 1, n)
-    zz, yy, xx = np.meshgrid(g, g, g, indexing="ij")
+    inside, 0 outside.  n: the edge, or (x, y, z) voxels for a grid that is not cubic."""
+    nx, ny, nz = (n, n, n) if isinstance(n, int) else n
+    zz, yy, xx = np.meshgrid(np.linspace(-1, 1, nz), np.linspace(-1, 1, ny), np.linspace(-1, 1, nx), indexing="ij")
     return _as(fmt, np.clip(1.0 - np.sqrt(xx * xx + yy * yy + zz * zz) / 0.9, 0, 1))
 
 
@@ -100,8 +100,8 @@ def mixed_table():
     return t
 
 
-def _setup(vr, vol, fmt, table, g_hi=G_HI, tff=None):
-    vr.loadVolumeArrays([vol], fmt)
+def _setup(vr, vol, fmt, table, g_hi=G_HI, tff=None, thickness=(1.0, 1.0, 1.0)):
+    vr.loadVolumeArrays([vol], fmt, thickness)
     if tff is not None:
         vr.setTransferFunction(tff)
     vr.setTransferFunction2D(table, g_hi)
@@ -110,11 +110,11 @@ def _setup(vr, vol, fmt, table, g_hi=G_HI, tff=None):
     vr.params()[1].backgroundColor[:] = BG
 
 
-def _conf(vr, view="rot30", linear=True, ortho=False, rate=1.0, ess=True, seed=SEEDS[0], illum=1):
+def _conf(vr, view="rot30", linear=True, ortho=False, rate=1.0, ess=True, seed=SEEDS[0], illum=1, bbox=None):
     vr.setLinearInterpolation(linear)
     vr.setCamOrtho(ortho)
     vr.updateSamplingRate(rate)
-    vr.setBBox(-1, -1, -1, 1, 1, 1)
+    vr.setBBox(*(bbox or (-1, -1, -1, 1, 1, 1)))
     vr.setObjEss(ess)
     vr.updateView(VIEWS[view] if isinstance(view, str) else view)
     vr.setSeed(seed)
@@ -240,6 +240,188 @@ def test_counters(vr):
             assert st["samples_nominal"] == 0 and st["bricks_visited"] == 0
     finally:
         vr.setStatsEnabled(False)
+
+
+# ---- cameras, boxes, rates, odd sizes, table sizes, FLOAT palettes: what the skip's proof (vr_tf2d.hip's header)
+# rests on -- the cell found on the ray's cell line covers the filter's footprint -- under a clip box, a modelScale
+# that is not 1, an orthographic camera and an eye inside the box
+
+INSIDE = list(VIEWS["rot30"])
+INSIDE[3], INSIDE[7], INSIDE[11] = 0.1, -0.2, 0.3    # the eye inside the box: t_0 = 0
+CAMERAS = {
+    "orthographic": dict(view="close", ortho=True),
+    "inside": dict(view=INSIDE, seed=SEEDS[2]),
+    "clip_box": dict(bbox=(-0.5, -0.8, -1.0, 0.7, 0.6, 0.2)),
+    "rate_0.5": dict(rate=0.5),
+    "rate_4": dict(rate=4.0),
+}
+
+
+@pytest.mark.parametrize("cam", sorted(CAMERAS))
+def test_cameras_boxes_and_rates(vr, cam):
+    """The ball on 40 x 24 x 17 voxels (modelScale 1, 0.6, 0.425) with the band table, at 40 x 32 and 37 x 29."""
+    fmt = UCHAR
+    vol = _sphere(fmt, (40, 24, 17))
+    table = band_table()
+    _setup(vr, vol, fmt, table)
+    for W, H in ((40, 32), (37, 29)):
+        img, kind, samples, visible, marginal = _both_ess(vr, vol, fmt, table, W, H, cam, **CAMERAS[cam])
+        assert 0 < visible.sum() and marginal.sum() < samples.sum()   # something shows, something is stepped over
+        if cam == "inside":
+            assert np.all(kind == tf2d_ref.MARCHED)
+
+
+def _random_volume(fmt, res, seed):
+    """Uniform random voxels (tests/test_gpu_mip.py's): no structure for the skipping to lean on.  A third of the
+    volume is left low so that rays differ."""
+    rng = np.random.default_rng(seed)
+    x, y, z = res
+    f = rng.random((z, y, x), dtype=np.float32)
+    f[:, :, : x // 3] *= 0.25
+    return _as(fmt, f)
+
+
+@pytest.mark.parametrize("fmt,res,size,thickness", [
+    (UCHAR, (45, 38, 33), (90, 60), (1.0, 1.0, 1.0)),     # no multiple of 4 or of the cell edge; no multiple of 8
+    (FLOAT, (45, 38, 33), (90, 60), (1.0, 1.3, 2.0)),     # ... on an anisotropic grid
+    (USHORT, (40, 32, 1), (96, 60), (1.0, 1.0, 1.0)),     # one voxel thick
+    (FLOAT, (1, 37, 29), (61, 64), (1.0, 1.0, 1.0)),
+], ids=["odd_uchar", "odd_float_aniso", "thin_z_ushort", "thin_x_float"])
+def test_odd_sizes(vr, fmt, res, size, thickness):
+    """The sizes and thicknesses of tests/test_gpu_mip.py test_odd_sizes, which pass through the shared ray setup and
+    cell grid for techniques 2 and 4, with the mixed table (columns 0 and 4 transparent)."""
+    vol = _random_volume(fmt, res, 4)
+    table = mixed_table()
+    _setup(vr, vol, fmt, table, g_hi=0.5, thickness=thickness)
+    for linear in (True, False):
+        for cam in ("perspective", "orthographic"):
+            conf = dict(view="close", ortho=True) if cam == "orthographic" else dict(view="rot30")
+            _both_ess(vr, vol, fmt, table, size[0], size[1], "%s %s" % (cam, linear), g_hi=0.5, linear=linear, **conf)
+
+
+@pytest.mark.parametrize("n_v,n_g", [(1, 1), (2, 1), (1, 16), (4096, 16), (256, 256)])
+def test_table_sizes(vr, n_v, n_g):
+    """The extremes of vrhip_tf2d_params_check on the device: one entry, one row, one column, the widest value axis
+    with the largest table (65536 entries, the prefix array nz at its 4097), the tallest gradient axis."""
+    fmt = USHORT
+    vol = _sphere(fmt, 24)
+    rng = np.random.default_rng(n_v * 31 + n_g)
+    table = rng.integers(0, 256, (n_g, n_v, 4), dtype=np.uint8)
+    if n_v > 2:   # half of the columns transparent, column 0 -- the ball's surround -- among them: rays reach the ball
+        clear = rng.random(n_v) < 0.5
+        clear[0] = True
+        table[:, clear, 3] = 0
+    _setup(vr, vol, fmt, table)
+    ref = _both_ess(vr, vol, fmt, table, 37, 29, "%d x %d" % (n_v, n_g), rate=1.5, illum=0)
+    assert ref[3].sum() > 0
+    if n_v > 2:
+        assert ref[4].sum() < ref[2].sum()   # samples in transparent columns
+
+
+def float_table():
+    """The mixed 7 x 5 table with column 0 -- what a NaN and every value below 1 / 14 reads -- not transparent, but
+    thin (10 / 255): most rays get through the surround of the palettes' ball, which reads it, to the ball itself."""
+    t = mixed_table()
+    t[:, 0, 3] = 10
+    return t
+
+
+@pytest.mark.parametrize("linear", [True, False], ids=["linear", "nearest"])
+@pytest.mark.parametrize("palette", scenes.FLOAT_PALETTES)
+def test_float_palettes(vr, palette, linear):
+    """Raw FLOAT values far outside [0, 1] on both sides, and (specials) NaN, +-inf, -0.0, denormals and +-3e38: the
+    value axis clamps, a NaN value or gradient reads coordinate -1, a cell with a NaN voxel (b.x <= b.y fails) or with
+    a bound beyond FLT_MAX / 2 is never skipped.  Only specials can make a NaN pixel (a shaded sample whose gradient is
+    inf - inf), and only there every NaN counts as one."""
+    vol = scenes.float_volume(palette, (29, 24, 21))
+    table = float_table()
+    _setup(vr, vol, FLOAT, table, g_hi=0.5)
+    for illum in (0, 1):
+        ref = _both_ess(vr, vol, FLOAT, table, 37, 29, "%s illum %d" % (palette, illum),
+                        bits=_bits_one_nan if palette == "specials" else _bits, g_hi=0.5, linear=linear, illum=illum)
+        assert palette == "specials" or not np.isnan(ref[0]).any()
+        assert ref[3].sum() > 0
+
+
+def _counted_both_ess(vr, vol, table, W, H, what, bits, g_hi):
+    """The counted kernels with ESS off and on: both frames equal the restatement; test_counters' identities."""
+    vr.setStatsEnabled(True)
+    try:
+        frames, stats = {}, {}
+        for ess in (False, True):
+            _conf(vr, ess=ess)
+            frames[ess] = vr.runRaycastNoGL(W, H)
+            stats[ess] = vr.getStats()
+            assert vr.lastLaunchInfo()["instrumented"] == 1
+    finally:
+        vr.setStatsEnabled(False)
+    img, kind, samples, visible, marginal = _ref(vr, vol, FLOAT, table, W, H, g_hi)
+    for ess in (False, True):
+        bad = np.any(bits(frames[ess]) != bits(img), axis=-1)
+        assert not bad.any(), "%s, counted, ESS %s: %d pixels differ, first at %s" % (what, ess, bad.sum(), np.argwhere(bad)[0])
+    off, on = stats[False], stats[True]
+    assert off["samples_taken"] == int(samples.sum()) and off["bricks_skipped"] == 0
+    assert off["samples_shaded"] == on["samples_shaded"] == int(marginal.sum())
+    assert on["samples_taken"] + on["bricks_skipped"] == int(samples.sum())
+    return on
+
+
+def test_float_palettes_counted(vr):
+    """The counted kernels on all five palettes: frames equal with ESS on and off.  And ESS still skips on straddle:
+    with column 0 opaque it cannot -- every cell of that volume holds a value below 1 / 14 (the ball's zero surround
+    is -0.5), so every cell's range reads column 0 -- which is why the skip is asked for with the mixed table itself,
+    column 0 transparent: the cells that hold nothing but -0.5, a value BELOW the table's range, are stepped over."""
+    for palette in scenes.FLOAT_PALETTES:
+        vol = scenes.float_volume(palette, (29, 24, 21))
+        _setup(vr, vol, FLOAT, float_table(), g_hi=0.5)
+        _counted_both_ess(vr, vol, float_table(), 37, 29, palette, _bits_one_nan if palette == "specials" else _bits, 0.5)
+    vol = scenes.float_volume("straddle", (29, 24, 21))
+    _setup(vr, vol, FLOAT, mixed_table(), g_hi=0.5)
+    on = _counted_both_ess(vr, vol, mixed_table(), 37, 29, "straddle, column 0 transparent", _bits, 0.5)
+    assert on["bricks_skipped"] > 0 and on["samples_shaded"] > 0
+
+
+def test_volume_changes_under_a_resident_table(vr):
+    """Two time steps, setTimestep(1), then a device filter in place: after each change the technique-6 frame with
+    ESS on equals the restatement on the voxels downloaded from the device.  The 2-D table stays resident throughout;
+    a cell grid left over from the voxels before would show here and nowhere else."""
+    fmt = UCHAR
+    res = (40, 24, 17)
+    ball = _sphere(fmt, res)
+    noise = common.noise_volume(res, fmt, seed=3, smooth=False)
+    table = band_table()
+    W, H = 40, 32
+    vr.loadVolumeArrays([ball, noise], fmt)
+    vr.setTransferFunction2D(table, G_HI)
+    vr.setTechnique(TECH_TF2D)
+    vr.setStatsEnabled(False)
+    vr.params()[1].backgroundColor[:] = BG
+    try:
+        frames = []
+
+        def check(step, what):
+            _conf(vr, ess=True, rate=1.5)
+            img = vr.runRaycastNoGL(W, H)
+            li = vr.lastLaunchInfo()
+            assert li["technique"] == 6 and li["empty_skip"] == 1, li
+            vol = vr.downloadVolume(step)
+            ref = _ref(vr, vol, fmt, table, W, H)
+            bad = np.any(_bits(img) != _bits(ref[0]), axis=-1)
+            assert not bad.any(), "%s: %d pixels differ, first at %s" % (what, bad.sum(), np.argwhere(bad)[0])
+            assert ref[3].sum() > 0 and ref[4].sum() < ref[2].sum()
+            frames.append(img)
+            return vol
+
+        assert np.array_equal(check(0, "step 0"), ball)
+        vr.setTimestep(1)
+        assert np.array_equal(check(1, "step 1"), noise)
+        vr.filter_volume("separable", taps=frontend.gaussian_taps(1.2, 3))
+        assert not np.array_equal(check(1, "step 1, filtered in place"), noise)
+        vr.filter_volume("median3")
+        check(1, "step 1, median")
+        assert not _same(frames[0], frames[1]) and not _same(frames[1], frames[2]) and not _same(frames[2], frames[3])
+    finally:
+        vr.setTimestep(0)
 
 
 def _dev(shape, fill=-7.0):
