@@ -297,6 +297,31 @@ public:
     void medianFilter();   // the current step, in place
     size_t getTimestep() const { return _timestep; }   // the step setTimestep last selected
     filter_info lastFilterInfo();
+    // ---- volume morphology (no reference counterpart; vrhip.h "volume morphology"): grey-scale erosion, dilation,
+    // opening, closing, gradient and the top-hat transforms of channel 0 of the current time step, computed on the
+    // device into time step dstTimestep -- the current one: in place; the number of steps: a new one (which
+    // getResolution() does not count).  The structuring element is a box or a ball (an ellipsoid) of radius 0..8 per
+    // axis (x, y, z); neighbours are clamped to the volume.  The ESS bricks are rebuilt when a transfer function is
+    // set, as after a load.
+    enum class MorphOp { Erode = 0, Dilate, Open, Close, Gradient, TopHat, BlackHat };
+    struct MorphParams {
+        MorphOp op = MorphOp::Erode;
+        bool ball = true;
+        std::array<unsigned int, 3> radius = {{1, 1, 1}};
+    };
+    struct morph_info {
+        std::array<uint64_t, 2> blocks = {{0, 0}}, blocksFetched = {{0, 0}}, blocksSkipped = {{0, 0}};
+        uint64_t scratchBytes = 0;
+        unsigned int sweeps = 0;
+        bool emptySkip = false, inPlace = false;
+    };
+    void morphVolume(const MorphParams &params, size_t dstTimestep);
+    // the current step, in place, the same radius on every axis
+    void erode(unsigned int radius, bool ball = true);
+    void dilate(unsigned int radius, bool ball = true);
+    void open(unsigned int radius, bool ball = true);
+    void close(unsigned int radius, bool ball = true);
+    morph_info lastMorphInfo();
     // ---- the progressive path tracer (technique 1), many samples per call (vrhip_render_samples): seeds.size()
     // consecutive iterations of the accumulated image -- sample k with jitter seed seeds[k] at iteration
     // (current iteration + k) -- in as few launch sets as possible, bit for bit what seeds.size() runRaycastNoGL calls

@@ -780,6 +780,82 @@ typedef struct vrhip_filter_info {
 } vrhip_filter_info;                                 /* 40 bytes */
 int vrhip_last_filter_info(const vrhip_renderer *r, vrhip_filter_info *out);
 
+/* ---- volume morphology: grey-scale erosion, dilation, opening, closing, gradient and the top-hat transforms, computed
+ * on the device (DESIGN.md "Volume morphology").  Not a technique: vrhip_morph_volume reads channel 0 of the CURRENT
+ * time step and writes the whole of time step dst_timestep, in the volume's own format and resolution.  Minimum and
+ * maximum are exact and independent of the order of evaluation; tests/ref/morph_ref.c restates the contract on the CPU.
+ *  Structuring element B: the integer offsets (dx, dy, dz) with |d_a| <= R_a = radius[a].  VRHIP_MORPH_BOX takes all
+ *   of them; VRHIP_MORPH_BALL those with dx^2 R'y^2 R'z^2 + dy^2 R'x^2 R'z^2 + dz^2 R'x^2 R'y^2 <= R'x^2 R'y^2 R'z^2,
+ *   R'_a = max(R_a, 1), in integer arithmetic: radius (1,1,1) is the 6-neighbourhood and the centre, 7 offsets;
+ *   (2,2,2) has 33, (4,4,4) 257, (8,8,8) 2109, (2,0,3) 19.  Radius (0,0,0) is the identity element.
+ *   vrhip_morph_element lists B as triples (dx, dy, dz), z, then y, then x ascending; *n is the number of offsets
+ *   whatever the capacity (in triples), and VRHIP_ERR_INVALID is returned, with nothing written to offsets_xyz, where
+ *   it is below *n (offsets_xyz may be NULL with capacity 0).
+ *  Keys: UCHAR and USHORT compare the raw integer.  FLOAT compares the order-preserving 32-bit key of the raw word
+ *   that the volume filters' median uses -- the sign bit flipped for words with a clear sign bit, all bits for the
+ *   others, every NaN mapped to 0xffffffff: every NaN is the largest key.
+ *  Erosion at p is the smallest key, dilation the largest, over the clamped positions clamp(p + o), o in B.  B is
+ *   symmetric and down-closed in |o|, so these are the voxels p + o that lie inside the volume.
+ *  Ops: ERODE; DILATE; OPEN = dilation of the erosion; CLOSE = erosion of the dilation; GRADIENT = dilation - erosion;
+ *   TOPHAT = f - OPEN; BLACKHAT = CLOSE - f (f the source).  With this border rule erosion <= open <= f <= close <=
+ *   dilation at every voxel, so on UCHAR / USHORT the three differences are plain unsigned subtractions of the raw
+ *   integers and never wrap; on FLOAT each is one fp32 subtraction of the two stored words read as floats (for f the
+ *   source's raw word).
+ *  Store.  UCHAR / USHORT: the integer.  FLOAT: the word of the key, or the difference; a zero of either sign is
+ *   stored as +0 and any NaN as 0x7fc00000 (the filters' store).  The intermediate of a two-sweep op is stored by the
+ *   same rule and the second sweep reads those stored words.  Voxels of an existing micro-brick beyond the volume are
+ *   written 0, as an upload does; no sweep reads them as data.
+ *  Sweeps and scratch.  ERODE, DILATE and GRADIENT take one sweep over the blocks of VRHIP_MESH_BLOCK^3 voxels (the
+ *   gradient takes both extremes from one staged tile); the others two, through one full-size intermediate in the
+ *   volume's own type; the second sweep of TOPHAT / BLACKHAT reads the intermediate for the extreme and the source for
+ *   f.  In place the result goes to a scratch that takes the slot's place (swapped in; copied where other renderers
+ *   hold the slot's address), except that OPEN / CLOSE in place without sharers write their second sweep straight
+ *   into the slot.  Full-size scratches held at once: into another step 0 (one sweep) or 1 (two); in place 1 or 2
+ *   (OPEN / CLOSE without sharers: 1).  All of it is freed before the call returns.
+ *  Destination, sharers and staleness: as vrhip_filter_volume.  dst_timestep is an existing step (the current one: in
+ *   place) or the number of steps, which appends one.  Afterwards it is a step like an uploaded one: its bricks, cells
+ *   and footprint are stale and vrhip_build_bricks is due as after an upload; renderers that share this one's volumes
+ *   are treated as by an upload.
+ *  vrhip_set_object_ess: on, the first sweep does not fetch a block where the coarse cells that cover the block
+ *   dilated by R_a voxels per axis and clamped to the volume all hold the same finite min == max == c; the second
+ *   sweep asks the same of the block dilated by 2 R_a (the intermediate is then c on everything it reads, and so is
+ *   f).  A skipped block is written c for ERODE / DILATE / OPEN / CLOSE and for the intermediate (FLOAT, c == 0: +0)
+ *   and 0 for GRADIENT / TOPHAT / BLACKHAT.  A cell with a NaN holds (-inf, +inf) and proves nothing.  No byte of the
+ *   destination changes with the switch.
+ *  vrhip_last_morph_info: per sweep the blocks, how many were fetched and skipped (sweep[1] is 0 for a one-sweep op);
+ *   the sweeps; the device scratch the call held at its peak (full-size scratches and 32 bytes of counters); whether
+ *   the cell grid was handed over; whether it ran in place.
+ *  State: reads the volume, the time step and the object-ESS switch.  Nothing that a render, slice, depth, mesh,
+ *   statistics or filter call of ANOTHER step reads later changes, beyond what an upload into dst_timestep changes.
+ *  VRHIP_ERR_INVALID: a NULL argument; an unknown op or shape; a radius above VRHIP_MORPH_MAX_RADIUS; reserved != 0;
+ *   dst_timestep above the number of steps.  VRHIP_ERR_UNSUPPORTED: RG / RGBA volumes; a renderer whose volumes are
+ *   borrowed (vrhip_share_volumes) -- checked before anything is touched.  VRHIP_ERR_NODATA: no volume;
+ *   vrhip_last_morph_info before the first call. */
+enum { VRHIP_MORPH_ERODE = 0, VRHIP_MORPH_DILATE = 1, VRHIP_MORPH_OPEN = 2, VRHIP_MORPH_CLOSE = 3,
+       VRHIP_MORPH_GRADIENT = 4, VRHIP_MORPH_TOPHAT = 5, VRHIP_MORPH_BLACKHAT = 6 };
+enum { VRHIP_MORPH_BOX = 0, VRHIP_MORPH_BALL = 1 };
+#define VRHIP_MORPH_MAX_RADIUS 8u
+typedef struct vrhip_morph_params {
+    uint32_t op, shape;      /* VRHIP_MORPH_* */
+    uint32_t radius[3];      /* x, y, z: 0..8 */
+    uint32_t reserved[3];    /* must be 0 */
+} vrhip_morph_params;                                /* 32 bytes */
+int vrhip_morph_volume(vrhip_renderer *r, const vrhip_morph_params *p, uint32_t dst_timestep);
+/* the checks of vrhip_morph_volume that need neither a renderer nor a volume -- op, shape, radii, reserved: VRHIP_OK
+ * or VRHIP_ERR_INVALID (a NULL p too).  Host only. */
+int vrhip_morph_params_check(const vrhip_morph_params *p);
+/* the offsets of B, 3 int8 per offset.  Host only. */
+int vrhip_morph_element(const vrhip_morph_params *p, int8_t *offsets_xyz, uint32_t capacity, uint32_t *n);
+typedef struct vrhip_morph_sweep_info {
+    uint64_t blocks, blocks_fetched, blocks_skipped;
+} vrhip_morph_sweep_info;                            /* 24 bytes */
+typedef struct vrhip_morph_info {
+    vrhip_morph_sweep_info sweep[2];
+    uint64_t scratch_bytes;
+    uint32_t sweeps, empty_skip, in_place, reserved;
+} vrhip_morph_info;                                  /* 72 bytes */
+int vrhip_last_morph_info(const vrhip_renderer *r, vrhip_morph_info *out);
+
 /* createEnvironmentMap (volumerendercl.cpp:1121-1150): float RGBA texels, row-major, width*height*4
  * floats (the host layer decodes the Radiance .hdr file).  The kernel samples it in place of the
  * background colour when it is wider than one texel (volumeraycast.cl:506-510, :655-656);

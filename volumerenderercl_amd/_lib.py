@@ -170,6 +170,33 @@ class FilterInfo(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+# vrhip_morph_params.op / .shape and the largest radius (volume morphology, vrhip_morph_volume)
+MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE, MORPH_GRADIENT, MORPH_TOPHAT, MORPH_BLACKHAT = range(7)
+MORPH_BOX, MORPH_BALL = 0, 1
+MORPH_MAX_RADIUS = 8
+
+
+class MorphParams(C.Structure):
+    """vrhip_morph_params: the op, the shape and the radii of a vrhip_morph_volume call."""
+    _fields_ = [("op", C.c_uint32), ("shape", C.c_uint32), ("radius", C.c_uint32 * 3), ("reserved", C.c_uint32 * 3)]
+
+
+class MorphSweepInfo(C.Structure):
+    _fields_ = [("blocks", C.c_uint64), ("blocks_fetched", C.c_uint64), ("blocks_skipped", C.c_uint64)]
+
+
+class MorphInfo(C.Structure):
+    """vrhip_morph_info: what the last vrhip_morph_volume did."""
+    _fields_ = [("sweep", MorphSweepInfo * 2), ("scratch_bytes", C.c_uint64), ("sweeps", C.c_uint32),
+                ("empty_skip", C.c_uint32), ("in_place", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        d = {n: int(getattr(self, n)) for n in ("scratch_bytes", "sweeps", "empty_skip", "in_place")}
+        for n, _ in MorphSweepInfo._fields_:
+            d[n] = [int(getattr(self.sweep[s], n)) for s in range(2)]
+        return d
+
+
 class Stats(C.Structure):
     _fields_ = [("samples_taken", C.c_uint64), ("samples_nominal", C.c_uint64),
                 ("samples_shaded", C.c_uint64), ("bricks_visited", C.c_uint64),
@@ -198,6 +225,7 @@ assert C.sizeof(DepthParams) == 32 and C.sizeof(DepthInfo) == 32
 assert C.sizeof(MeshParams) == 48 and C.sizeof(MeshInfo) == 32 and C.sizeof(IndexedMeshInfo) == 64
 assert C.sizeof(StatsParams) == 64 and C.sizeof(VolumeStats) == 72 and C.sizeof(StatsInfo) == 48
 assert C.sizeof(FilterParams) == 140 and C.sizeof(FilterInfo) == 40
+assert C.sizeof(MorphParams) == 32 and C.sizeof(MorphInfo) == 72
 
 _H = C.c_void_p
 _U3 = C.POINTER(C.c_uint32)
@@ -294,6 +322,10 @@ SYMBOLS = {
     "vrhip_filter_params_check": (C.c_int, [C.POINTER(FilterParams)]),
     "vrhip_filter_gaussian_taps": (C.c_int, [C.c_double, C.c_uint32, C.POINTER(C.c_float)]),
     "vrhip_last_filter_info": (C.c_int, [_H, C.POINTER(FilterInfo)]),
+    "vrhip_morph_volume": (C.c_int, [_H, C.POINTER(MorphParams), C.c_uint32]),
+    "vrhip_morph_params_check": (C.c_int, [C.POINTER(MorphParams)]),
+    "vrhip_morph_element": (C.c_int, [C.POINTER(MorphParams), C.POINTER(C.c_int8), C.c_uint32, _U3]),
+    "vrhip_last_morph_info": (C.c_int, [_H, C.POINTER(MorphInfo)]),
     "vrhip_render_tiles": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_void_p, C.c_uint32, C.c_void_p]),
     "vrhip_set_environment_map": (C.c_int, [_H, C.c_void_p, C.c_uint32, C.c_uint32]),

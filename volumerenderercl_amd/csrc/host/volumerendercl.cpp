@@ -895,6 +895,56 @@ VolumeRenderCL::filter_info VolumeRenderCL::lastFilterInfo()
     return out;
 }
 
+void VolumeRenderCL::morphVolume(const MorphParams &params, size_t dstTimestep)
+{
+    if (!_volLoaded) throw std::runtime_error("No volume data is loaded.");
+    vrhip_morph_params p{};
+    p.op = uint32_t(params.op);
+    p.shape = params.ball ? VRHIP_MORPH_BALL : VRHIP_MORPH_BOX;
+    for (size_t a = 0; a < 3; ++a) p.radius[a] = params.radius[a];
+    if (vrhip_morph_params_check(&p) != VRHIP_OK) throw std::invalid_argument("morphVolume: op or radius out of range");
+    check("morphVolume", vrhip_morph_volume(_r, &p, uint32_t(dstTimestep)));
+    if (!_tff.empty()) generateBricks();
+    if (dstTimestep == _timestep) _rendering_params.iteration = 0;
+}
+
+void VolumeRenderCL::erode(unsigned int radius, bool ball)
+{
+    morphVolume(MorphParams{MorphOp::Erode, ball, {{radius, radius, radius}}}, _timestep);
+}
+
+void VolumeRenderCL::dilate(unsigned int radius, bool ball)
+{
+    morphVolume(MorphParams{MorphOp::Dilate, ball, {{radius, radius, radius}}}, _timestep);
+}
+
+void VolumeRenderCL::open(unsigned int radius, bool ball)
+{
+    morphVolume(MorphParams{MorphOp::Open, ball, {{radius, radius, radius}}}, _timestep);
+}
+
+void VolumeRenderCL::close(unsigned int radius, bool ball)
+{
+    morphVolume(MorphParams{MorphOp::Close, ball, {{radius, radius, radius}}}, _timestep);
+}
+
+VolumeRenderCL::morph_info VolumeRenderCL::lastMorphInfo()
+{
+    vrhip_morph_info mi{};
+    check("lastMorphInfo", vrhip_last_morph_info(_r, &mi));
+    morph_info out;
+    for (size_t s = 0; s < 2; ++s) {
+        out.blocks[s] = mi.sweep[s].blocks;
+        out.blocksFetched[s] = mi.sweep[s].blocks_fetched;
+        out.blocksSkipped[s] = mi.sweep[s].blocks_skipped;
+    }
+    out.scratchBytes = mi.scratch_bytes;
+    out.sweeps = mi.sweeps;
+    out.emptySkip = mi.empty_skip != 0;
+    out.inPlace = mi.in_place != 0;
+    return out;
+}
+
 void VolumeRenderCL::renderSlicesRGBA8(size_t width, size_t height, const std::vector<slice_params> &slices,
                                        float *dev_frames, unsigned char *out, bool outIsDevice)
 {

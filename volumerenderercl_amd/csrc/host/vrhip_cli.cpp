@@ -147,6 +147,11 @@
         "                                           median: the 3x3x3 median; taps: FILE holds three lines, for x, y and\n"
         "                                           z, of 1 to 9 weights each, the weight at distance 0 first; honours\n"
         "                                           --timestep where that is allowed; not with --ranks, --downsample)\n"
+        "         [--morph OP box|ball RX RY RZ]   (grey-scale morphology of the loaded time step on the device, in place:\n"
+        "                                           OP erode, dilate, open, close, gradient, tophat or blackhat; the\n"
+        "                                           structuring element a box or a ball of radius 0-8 voxels per axis;\n"
+        "                                           repeatable; --filter and --morph steps run in command-line order,\n"
+        "                                           under the rules of --filter)\n"
         "writes PREFIX.rgba.f32 (W*H*4 float32, row 0 = top), PREFIX.ppm and prints one JSON line\n";
     std::exit(2);
 }
@@ -294,7 +299,28 @@ Options parse_args(int argc, char **argv)
                     std::exit(2);
                 }
             } else usage();
+            o.steps.push_back(VolumeStep{false, o.filters.size()});
             o.filters.push_back(fs);
+        }
+        else if (a == "--morph") {
+            need(i, 5);
+            static const char *const ops[] = {"erode", "dilate", "open", "close", "gradient", "tophat", "blackhat"};
+            const std::string op = argv[++i], shape = argv[++i];
+            MorphSpec ms;
+            size_t k = 0;
+            while (k < 7 && op != ops[k]) ++k;
+            if (k == 7 || (shape != "box" && shape != "ball")) usage();
+            ms.params.op = VolumeRenderCL::MorphOp(k);
+            ms.params.ball = shape == "ball";
+            for (size_t ax = 0; ax < 3; ++ax) {
+                const char *text = argv[++i];
+                char *end = nullptr;
+                const long rad = std::strtol(text, &end, 10);
+                if (end == text || *end || rad < 0 || rad > 8) usage();
+                ms.params.radius[ax] = unsigned(rad);
+            }
+            o.steps.push_back(VolumeStep{true, o.morphs.size()});
+            o.morphs.push_back(ms);
         }
         else if (a == "--frames") { need(i, 1); ba.frames = integer(); }
         else if (a == "--independent") ba.independent = true;
@@ -400,7 +426,7 @@ void validate(const Options &o)
     if ((me.normals || me.have_region || me.indexed) && !me.on) usage();
     if (o.volume.have_timestep && !me.on && !st.on) usage();
     if (st.have_opt && !st.on) usage();
-    if (!o.filters.empty() && (ranks > 0 || o.volume.downsample)) usage();
+    if ((!o.filters.empty() || !o.morphs.empty()) && (ranks > 0 || o.volume.downsample)) usage();
     // numbers about the volume (--stats) or triangles of it (--mesh), not a picture: what selects, shapes or
     // multiplies frames has nothing to act on
     const bool a_picture = te.pathtrace || te.mip || te.iso || t2.any() || te.preint || te.have_iso_refine || sl.any() || slice_opt || de.on ||

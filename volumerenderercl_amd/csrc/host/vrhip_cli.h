@@ -17,6 +17,17 @@ struct FilterSpec {
     VolumeRenderCL::FilterParams taps;      // TAPS
 };
 
+// --morph: one entry per occurrence, in the order given
+struct MorphSpec {
+    VolumeRenderCL::MorphParams params;
+};
+
+// --filter and --morph run in command-line order: entry k of that order is filters[index] or morphs[index]
+struct VolumeStep {
+    bool morph = false;
+    size_t index = 0;
+};
+
 struct Options {
     struct Volume {      // volume source (--dat, --synth, --device-ingest, --downsample, --timestep)
         std::string dat, synth_kind, synth_fmt = "UCHAR";
@@ -83,6 +94,8 @@ struct Options {
         double window[3] = {0.0, 1.0, 1.0};
     } stats;
     std::vector<FilterSpec> filters;   // --filter
+    std::vector<MorphSpec> morphs;     // --morph
+    std::vector<VolumeStep> steps;     // the two in command-line order
     struct Batch {       // batching / launch sets (--frames, --independent, --frames-per-launch ..., --samples-per-launch, --bench)
         int frames = 1, frames_per_launch = 0, frames_in_flight = 2, round_budget = 48, samples_per_launch = 0;
         bool independent = false, bench = false;

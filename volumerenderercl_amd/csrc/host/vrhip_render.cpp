@@ -433,9 +433,15 @@ bool write_stats_json(const std::string &path, const VolumeRenderCL::stats_param
     return bool(f);
 }
 
-void apply_filters(VolumeRenderCL &vr, const std::vector<FilterSpec> &filters)
+// the --filter and --morph steps, in command-line order
+void apply_volume_steps(VolumeRenderCL &vr, const Options &o)
 {
-    for (const FilterSpec &fs : filters) {
+    for (const VolumeStep &step : o.steps) {
+        if (step.morph) {
+            vr.morphVolume(o.morphs.at(step.index).params, vr.getTimestep());
+            continue;
+        }
+        const FilterSpec &fs = o.filters.at(step.index);
         if (fs.kind == FilterSpec::GAUSS) vr.gaussianFilter(fs.sigma, fs.radius);
         else if (fs.kind == FilterSpec::MEDIAN) vr.medianFilter();
         else vr.filterVolume(fs.taps, vr.getTimestep());
@@ -546,7 +552,7 @@ void setup_volume_only(VolumeRenderCL &vr, const Options &o)
     open_volume(vr, o, o.ranks.device);
     vr.setObjEss(o.render.ess);
     if (o.volume.have_timestep) vr.setTimestep(size_t(o.volume.timestep));
-    apply_filters(vr, o.filters);
+    apply_volume_steps(vr, o);
 }
 
 // Everything the front end sets on a renderer; returns false when there is no frame to render.  A --state file
@@ -557,9 +563,9 @@ bool setup_renderer(VolumeRenderCL &vr, Options &o, int dev)
     Options::View &vw = o.view;
     Options::Render &rn = o.render;
     open_volume(vr, o, dev);
-    if (!o.filters.empty()) {
+    if (!o.steps.empty()) {
         vr.setObjEss(rn.ess);
-        apply_filters(vr, o.filters);
+        apply_volume_steps(vr, o);
     }
     if (o.volume.downsample) {   // volumeDownsampling (volumerendercl.cpp:238-341) and nothing else
         const std::string base = vr.volumeDownsampling(0, o.volume.downsample);

@@ -574,6 +574,27 @@ inline size_t vr_filter_blocks(const VolView &v)
 }
 // counters are zero before the launch
 hipError_t vr_launch_filter(const FilterLaunch &a, void *dst, unsigned long long *counters, hipStream_t stream);
+// volume morphology (vrhip_morph_volume): one sweep over every block of 8^3 voxels of `vol` (x fastest) into `dst`, a
+// micro-bricked volume of the same layout and type that is not `vol.data`.  vol is what the sweep takes its extremes
+// of: the source, or the intermediate of a two-sweep op; f, for the two difference modes only, the source's voxels
+// in the same layout.  cell_minmax: the (min, max) of the SOURCE's coarse cells, or nullptr: every block is fetched;
+// skip_scale 1 for a first sweep, 2 for a second (the constant test's dilation in radii).  vr_morph.hip
+enum { kMorphMin = 0, kMorphMax, kMorphMaxMin, kMorphFMinusMax, kMorphMinMinusF };
+struct MorphLaunch {
+    VolView vol;
+    const void *f;
+    int format;            // vrhip_format
+    uint32_t mode;         // kMorph*
+    uint32_t shape;        // VRHIP_MORPH_BOX / _BALL
+    uint32_t radius[3];
+    uint32_t skip_scale;
+    const float2 *cell_minmax;
+    int cell_shift, cell_cx, cell_cy, cell_cz;
+    int num_cus;
+};
+// counters[]: 64-bit words the launch adds to, zero before it
+enum { kMorphFetched = 0, kMorphSkipped, kMorphCounters };
+hipError_t vr_launch_morph(const MorphLaunch &a, void *dst, unsigned long long *counters, hipStream_t stream);
 // the frame launch for a.render.technique
 inline hipError_t vr_launch_frame(const RaycastLaunch &a, hipStream_t stream)
 {

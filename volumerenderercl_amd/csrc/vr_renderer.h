@@ -285,6 +285,13 @@ struct vrhip_renderer {
     vrhip_filter_info filter_info;
     bool have_filter_info = false;
 
+    // volume morphology (vrhip_morph_volume, vrhip_morph_api.hip): the counters of a call's two sweeps in device
+    // memory, and what the last call did (vrhip_last_morph_info).  The intermediate and the in-place scratch live only
+    // inside a call.  No render, slice, depth, mesh, statistics or filter entry point reads them.
+    DevBuf<unsigned long long> morph_ws;
+    vrhip_morph_info morph_info;
+    bool have_morph_info = false;
+
     // device-side ingest (vrhip_ingest_raw, vrhip_volume_histogram): the running maximum and the 256 64-bit
     // histogram counters in device memory, the events around its kernels (all created on first use)
     size_t ingest_slab_bytes = (size_t)256 << 20;   // VRHIP_INGEST_SLAB_BYTES: staging per slab

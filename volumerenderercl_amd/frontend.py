@@ -605,6 +605,43 @@ def gaussian_taps(sigma, radius=None):
     return np.array([v / total for v in t], dtype=np.float32)
 
 
+# ---- volume morphology (include/vrhip.h "volume morphology"; VolumeRenderCL.morph_volume)
+
+MORPH_OPS = {"erode": 0, "dilate": 1, "open": 2, "close": 3, "gradient": 4, "tophat": 5, "blackhat": 6}   # VRHIP_MORPH_*
+MORPH_SHAPES = {"box": 0, "ball": 1}
+
+
+def morph_params(op, radius, shape="ball"):
+    """A MorphParams from names: op one of MORPH_OPS, shape "box" or "ball", radius 0..8, one for all axes or (x, y, z)."""
+    from . import _lib
+    if op not in MORPH_OPS:
+        raise ValueError("morph: op must be one of %s" % ", ".join(MORPH_OPS))
+    if shape not in MORPH_SHAPES:
+        raise ValueError("morph: shape must be 'box' or 'ball'")
+    radius = [radius] * 3 if np.isscalar(radius) else list(radius)
+    if len(radius) != 3 or any(not 0 <= int(v) <= _lib.MORPH_MAX_RADIUS or int(v) != v for v in radius):
+        raise ValueError("morph: a radius is an integer 0..8, one for all axes or one per axis")
+    p = _lib.MorphParams()
+    p.op = MORPH_OPS[op]
+    p.shape = MORPH_SHAPES[shape]
+    p.radius[:] = [int(v) for v in radius]
+    return p
+
+
+def morph_element(shape, radius):
+    """The offsets (dx, dy, dz) of the structuring element (vrhip_morph_element), int8 [n, 3], z, y, x ascending."""
+    import ctypes as C
+    from . import _lib
+    p = morph_params("erode", radius, shape)
+    n = C.c_uint32(0)
+    lib = _lib.load()
+    lib.vrhip_morph_element(C.byref(p), None, 0, C.byref(n))   # (the count; refused for its capacity)
+    out = np.zeros((n.value, 3), np.int8)
+    if lib.vrhip_morph_element(C.byref(p), out.ctypes.data_as(C.POINTER(C.c_int8)), n.value, C.byref(n)) != _lib.OK:
+        raise ValueError("morph_element: the library refuses the arguments")
+    return out
+
+
 # ---- slice views (include/vrhip.h "slice views"; VolumeRenderCL.render_slices).  The contract is the 80-byte
 # vrhip_slice_params block; the helpers below compute in float64 and store float32.
 

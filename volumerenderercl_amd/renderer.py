@@ -711,6 +711,44 @@ class VolumeRenderCL:
         self._check(self._lib.vrhip_last_filter_info(self._h, C.byref(fi)))
         return fi.as_dict()
 
+    # ---- volume morphology (include/vrhip.h "volume morphology")
+    def morph_volume(self, op, radius, shape="ball", dst=None):
+        """Grey-scale morphology of channel 0 of the current time step on the device (vrhip_morph_volume) into time step
+        dst -- None: the current one, in place; the number of steps: a new one.  op: "erode", "dilate", "open", "close",
+        "gradient", "tophat" or "blackhat"; shape "box" or "ball"; radius 0..8, one for all axes or (x, y, z);
+        neighbours clamped to the volume (frontend.morph_element lists the structuring element).  The destination is
+        a step like an uploaded one: the ESS bricks are rebuilt here, as loadVolumeData does, when a transfer function
+        is set.  Returns dst."""
+        if not self._vol_loaded:
+            raise RuntimeError("No volume data is loaded.")
+        p = frontend.morph_params(op, radius, shape)
+        if self._lib.vrhip_morph_params_check(C.byref(p)) != _lib.OK:
+            raise ValueError("morph_volume: op, shape or radius out of range")
+        dst = self._timestep if dst is None else int(dst)
+        self._check(self._lib.vrhip_morph_volume(self._h, C.byref(p), dst))
+        if dst >= self._res[3]:
+            self._res[3] = dst + 1
+        if self._histograms:
+            h = self.volumeHistogram(dst)
+            if dst < len(self._histograms):
+                self._histograms[dst] = h
+            else:
+                self._histograms.append(h)
+        if getattr(self, "_tff", None) is not None:
+            self._generate_bricks()
+        if dst == self._timestep:
+            self._rendering.iteration = 0
+        return dst
+
+    def lastMorphInfo(self):
+        """What the last morph_volume did (vrhip_last_morph_info): per sweep (lists of two) blocks (of 8^3 voxels),
+        blocks_fetched and blocks_skipped (constant by the cell grid, object-order ESS on); sweeps (1 or 2),
+        scratch_bytes (device memory the call held: full-size scratches and the counters), empty_skip (1: the cell
+        grid was handed to the kernel), in_place -- as a dict."""
+        mi = _lib.MorphInfo()
+        self._check(self._lib.vrhip_last_morph_info(self._h, C.byref(mi)))
+        return mi.as_dict()
+
     # ---- volume
     def loadVolumeData(self, props, ingest="host"):
         """volumerendercl.cpp:765-805. `props` is a datraw.Properties (dat_file_name or
